@@ -15,9 +15,12 @@ collective except ONE gather per step of the compact results (counts, keypoints,
     1-GPU number.
 `--scaling weak` (default): 32 frames per GPU per step.  `--scaling strong`: 256 frames per step in all, 256/N per GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, timed with HIP events
-on the library's stream inside the timed region), `cpu_baseline` (the CPU oracle, rank 0, N=1 only, bounded sample),
-`sustained` (>= 200 further steps: per-step spread, clocks) and, for N > 1, `ranks` / `rccl` (what the process group saw).
+Prints ONE JSON line on rank 0: the headline (`value`, `ms_per_step` of the `--steps` timed steps) and, for N > 1, `ranks` /
+`rccl` (what the process group saw).  A plain run does only that: set-up, warm-up, the timed steps, the outputs of the last
+timed step (`--dump-outputs DIR`) and the line.  `--full` adds what takes runs or checks of its own: `roofline` (dominant kernel,
+timed with HIP events on the library's stream inside the timed region, after an untimed per-stage pass), `cpu_baseline` (the CPU
+oracle, rank 0, N=1 only, bounded sample, which also checks the timed loop's outputs), `sustained` (>= 200 further steps:
+per-step spread, clocks), the variants, the PCIe-inclusive and pool runs and the `latency` object.
 """
 import argparse
 import json
@@ -357,6 +360,43 @@ class AuxMismatch(RuntimeError):
     as out["invalid_aux"] with a non-zero exit status -- unlike infrastructure failures (OOM, missing driver), which only leave an `error` string"""
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - (1 << 16)      # 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, n=None, S=None):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as out_dir/<name>.npy -- floating-point results
+    as float32, integers (counts, keypoint coordinates, match indices) as float64, which holds them exactly.  Rows past a frame's keypoint
+    count `n` (kxy / score / desc) or a pair's match count `S` (pairs / ms) are zeroed: the library leaves them unspecified.  Above 64 MB
+    in all, the largest arrays keep a fixed, seeded sample of their rows (<name>.npy) next to the sampled row indices (<name>_rows.npy).
+    -> {"dir", "files", "bytes"} for the result line."""
+    a = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        a[name] = v.astype(np.float32 if v.dtype.kind == "f" else np.float64)      # astype copies: the masking below stays local
+    for cnt, names in ((n, ("kxy", "score", "desc")), (S, ("pairs", "ms"))):
+        if cnt is None:
+            continue
+        cnt = np.asarray(cnt).reshape(-1, 1)
+        for name in names:
+            if name in a:
+                a[name][np.arange(a[name].shape[1])[None, :] >= cnt] = 0
+    total = sum(v.nbytes for v in a.values())
+    for name in sorted(a, key=lambda k: -a[k].nbytes):
+        if total <= DUMP_LIMIT_BYTES:
+            break
+        v = a[name]
+        flat = v.reshape(-1, v.shape[-1]) if v.ndim >= 2 else v.reshape(-1, 1)
+        row_bytes = flat.shape[1] * flat.itemsize + 8                              # + its float64 row index
+        keep = int(min(flat.shape[0], max(0, DUMP_LIMIT_BYTES - (total - v.nbytes)) // row_bytes))
+        rows = np.sort(np.random.default_rng(0).choice(flat.shape[0], keep, replace=False))
+        a[name], a[name + "_rows"] = flat[rows], rows.astype(np.float64)
+        total += a[name].nbytes + a[name + "_rows"].nbytes - v.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in a.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in a), "bytes": int(total)}
+
+
 def stereo_frames(synth, T=8):
     """T synthetic 752x480 stereo pairs (EuRoC size): one scene, the right view shifted by a 24-px disparity, the camera moving 8 px
     per frame.  -> (lefts, rights): lists of u8 [480,752]"""
@@ -372,7 +412,7 @@ def stereo_frames(synth, T=8):
     return lefts, rights
 
 
-def run_stereo_stream(ctx, capi, synth, torch, dev, kmax, steps, warmup, with_stages=True):
+def run_stereo_stream(ctx, capi, synth, torch, dev, kmax, steps, warmup, with_stages=True, dump_dir=None):
     """BASELINE configs[4]: a 752x480 stereo stream through ONE device-resident entry point per stereo frame,
     rfe_stereo_frame_dev: both views through SuperPoint as a batch of 2 (src/Frame.cc:142-147), Frame::ComputeStereoMatches
     (src/Frame.cc:1159-1446) and one LightGlue match of the left view against the previous left view
@@ -415,11 +455,18 @@ def run_stereo_stream(ctx, capi, synth, torch, dev, kmax, steps, warmup, with_st
     if with_stages:
         out["ms_per_step_with_stage_events"] = round(dt_prof / steps * 1e3, 4)
         out["stages_ms_per_step"] = {k: round(v[0] / steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
+    if dump_dir:        # the last stereo frame: both views' keypoints, the left view's stereo matches, the temporal match list
+        nl = int(res["n"][0])
+        ur, dp = res["u_right"].copy(), res["depth"].copy()
+        ur[nl:], dp[nl:] = 0, 0
+        out["dump_outputs"] = dump_outputs(dump_dir, {"n": res["n"], "kxy": res["kxy"], "score": res["score"], "desc": res["desc"], "u_right": ur,
+                                                      "depth": dp, "S": [res["S"]], "pairs": res["pairs"][None], "ms": res["ms"][None]},
+                                           n=res["n"], S=[res["S"]])
     return out
 
 
 def bench_stereo_stream(args, ctx, capi, synth, torch, dev, rank):
-    out = run_stereo_stream(ctx, capi, synth, torch, dev, args.kmax, args.steps, args.warmup)
+    out = run_stereo_stream(ctx, capi, synth, torch, dev, args.kmax, args.steps, args.warmup, dump_dir=args.dump_outputs if rank == 0 else None)
     if rank == 0:
         print(json.dumps(out))
 
@@ -690,6 +737,13 @@ def main():
     ap.add_argument("--kmax", type=int, default=KMAX, help="keypoint capacity per frame (default 1024)")
     ap.add_argument("--frames-per-gpu", type=int, default=FRAMES_PER_GPU,
                     help="frames (= pairs) each GPU owns per step; 32 = BASELINE configs[3] (256 frames over 8 GPUs), other values are exploratory")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline (c4): per-stage table + roofline, sustained loop, variants, PCIe-inclusive and pool runs, "
+                         "`latency`, CPU baselines with the oracle check of the timed loop's outputs; the --no-* / --sustained-steps / "
+                         "--latency-steps options select among these.  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in "
+                         "all; entries past a frame's keypoint count or a pair's match count are zeroed)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -830,21 +884,22 @@ def main():
             gather()
             fence()
             collective_warmup += 1
-    # Stage table: a separate, untimed pass with events around EVERY stage (each event pair keeps neighbouring kernels
-    # from overlapping their launch / drain: ~2 % of a batched step).  It also names the dominant kernel.
-    full_steps = args.steps if args.workload != "c4" else min(args.steps, 3)
-    ctx.profile_filter(None)
-    ctx.profile(True)
-    ctx.profile_reset()
-    t0 = time.perf_counter()
-    for _ in range(full_steps):
-        step()
-    fence()
-    dt = time.perf_counter() - t0
-    prof_full = ctx.profile_read()
-    ctx.profile(False)
-    prof_dom = None
-    if args.workload == "c4":
+    prof_full, prof_dom, full_steps = None, None, 0
+    if args.full or args.workload != "c4":
+        # Stage table: a separate, untimed pass with events around EVERY stage (each event pair keeps neighbouring kernels
+        # from overlapping their launch / drain: ~2 % of a batched step).  It also names the dominant kernel.
+        full_steps = args.steps if args.workload != "c4" else min(args.steps, 3)
+        ctx.profile_filter(None)
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        for _ in range(full_steps):
+            step()
+        fence()
+        dt = time.perf_counter() - t0
+        prof_full = ctx.profile_read()
+        ctx.profile(False)
+    if args.workload == "c4" and args.full:
         # Timed region: exactly K steps, HIP events only around the dominant kernel (its average launch duration feeds
         # the roofline object and is measured here, live, on the stream the kernels run on).
         dom_stage = max(prof_full.items(), key=lambda kv: kv[1][0])[0]
@@ -860,6 +915,14 @@ def main():
         prof_dom = ctx.profile_read()
         ctx.profile(False)
         ctx.profile_filter(None)
+    elif args.workload == "c4":
+        # Timed region of a plain run: exactly K steps between two fences, no events
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        dt = time.perf_counter() - t0
     prof = prof_full
     per_rank_ms = [dt / max(args.steps, 1) * 1e3]
     if pg:
@@ -868,6 +931,20 @@ def main():
         dist.all_reduce(tall)                      # every rank's own clock around the same barrier-bracketed region
         per_rank_ms = [float(v) / args.steps * 1e3 for v in tall.tolist()]
         dt = float(tall.max().item())              # MAX over ranks
+
+    def dump_last_step():
+        """--dump-outputs (rank 0): what a caller of the timed path holds after its last step -- with N > 1 ranks the results rank 0 gathered"""
+        if pg and world > 1:
+            own = shard.owned
+            per_frame = lambda k: torch.cat([gather.rank_view(r, k)[:own] for r in range(world - 1)] + [gather.rank_view(world - 1, k)]).cpu().numpy()
+            per_pair = lambda k: torch.cat([gather.rank_view(r, k)[:own] for r in range(world)]).cpu().numpy()
+            arr = {k: per_frame(k) for k in ("n", "kxy") + (("score", "desc") if args.gather_desc else ())}
+            arr.update({k: per_pair(k) for k in ("S", "pairs", "ms")})
+        else:
+            arr = {k: getattr(pack, k).cpu().numpy() for k in ("n", "kxy", "score", "desc") + (("S", "pairs", "ms") if args.workload != "c2" else ())}
+        return dump_outputs(args.dump_outputs, arr, n=arr["n"], S=arr.get("S"))
+
+    dumped = dump_last_step() if args.dump_outputs and rank == 0 and args.workload == "c4" else None
 
     if args.workload != "c4":      # latency configurations: a short line, no roofline object (not the metric's workload)
         # the per-stage HIP events cost a few microseconds each, which shows at these step times: the headline of a
@@ -879,13 +956,15 @@ def main():
             step()
         fence()
         dt = time.perf_counter() - t0
+        dumped = dump_last_step() if args.dump_outputs and rank == 0 else None
         if rank == 0:
             unit = "frames/s" if args.workload == "c2" else "pairs/s"
             print(json.dumps({"metric": f"BASELINE configs[{1 if args.workload == 'c2' else 2}] latency run", "value": round(args.steps / dt, 2),
                               "unit": unit, "ms_per_step": round(dt / args.steps * 1e3, 4), "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "kmax": KMAX, "mean_keypoints": float(n.float().mean().item()),
                               "ms_per_step_with_stage_events": round(dt_prof / args.steps * 1e3, 4),
-                              "stages_ms_per_step": {k: round(v[0] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}}))
+                              "stages_ms_per_step": {k: round(v[0] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
+                              **({"dump_outputs": dumped} if dumped else {})}))
         ctx.close()
         return
 
@@ -893,7 +972,7 @@ def main():
     # runs the same step (gather included) `--sustained-steps` more times with one event per step on the stream (no host
     # synchronisation inside the loop) and reports the spread and the clocks the chip settled at.
     sustained = None
-    if args.sustained_steps > 0:
+    if args.full and args.sustained_steps > 0:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.sustained_steps + 1)]
         fence()
         clk0 = gpu_clocks(dev_index)
@@ -925,7 +1004,7 @@ def main():
     fp16x2_out = None
     perf_notes = {}        # timing observations of auxiliary runs: information only, never an exit status
     aux_mismatch = []      # CORRECTNESS mismatches of auxiliary runs (never swallowed like infrastructure failures): -> out["invalid_aux"], exit status 5
-    if world == 1 and not args.no_variants and args.workload == "c4" and not args.lg_fp16x2:
+    if args.full and world == 1 and not args.no_variants and args.workload == "c4" and not args.lg_fp16x2:
         variants = {}
         try:
 
@@ -1042,7 +1121,7 @@ def main():
             step(); fence()
 
     pcie = None
-    if world == 1 and not args.no_pcie:
+    if args.full and world == 1 and not args.no_pcie:
         try:
             # PCIe-inclusive variant (never the headline `value`): frames start in pinned host memory, results end there.
             # Double buffered: a copy stream uploads batch k+1 and downloads the results of batch k-1 while batch k computes.
@@ -1096,7 +1175,7 @@ def main():
             fence()
 
     pool_line = None
-    if world == 1 and not args.no_pool and args.workload == "c4":
+    if args.full and world == 1 and not args.no_pool and args.workload == "c4":
         # The same 33-frame step through the C-ABI pool a C / C++ host would use (rfe_pool_*, rover-slam_amd/csrc/rfe_pool.hip): HOST frames in,
         # HOST results out (pageable memory, no overlap between calls), one member on this device, its rows gathered into the root buffer
         # through RCCL when librccl could be opened (self send / receive), copies otherwise.  Never the headline value.
@@ -1141,7 +1220,7 @@ def main():
             os.close(_saved1)
 
     latency = None
-    if world == 1 and not args.no_latency and args.workload == "c4" and not args.lg_fp16x2:
+    if args.full and world == 1 and not args.no_latency and args.workload == "c4" and not args.lg_fp16x2:
         # The reference's own call pattern (batch 1) on the driver's clock: configs[1] / [2] / [4], device-resident and through the C++
         # drop-in classes with host pointers.  Never the headline value.
         latency = {"note": "BASELINE configs[1] / [2] / [4]: batch-1 latency in ms per call (c2 = one frame, c3 = one pair incl. both extractions, "
@@ -1185,7 +1264,7 @@ def main():
 
     bad_exit = 0
     gathered_ok = None
-    if pg and rank == 0:   # the gathered payload of the last step really holds every rank's results
+    if args.full and pg and rank == 0:   # the gathered payload of the last step really holds every rank's results
         gn = sharding.assemble(gather, shard.owned)[0]
         gathered_ok = bool(gn.numel() == world * shard.owned + 1 and torch.equal(gather.rank_view(0, "n").cpu(), n.cpu()) and int((gn > 0).sum()) == gn.numel())
 
@@ -1193,17 +1272,18 @@ def main():
         lens = n.cpu().numpy()
         total_frames = FRAMES_PER_GPU * world * args.steps
         value = total_frames / dt
-        # dominant kernel = the stage with the largest accumulated time in the full pass; its events come from the timed region
-        dom_name, (dom_ms, dom_calls) = next(iter(prof_dom.items()))
-        fl = stage_flops(dom_name, B, lens, dom_calls // args.steps)
-        avg_ms = dom_ms / max(dom_calls, 1)
-        achieved = fl / (avg_ms * 1e-3) / 1e12 if fl else None
-        traffic, traffic_src = pmc_traffic(dom_name)
-        stages = {}
-        for k, (msv, calls) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
-            f = stage_flops(k, B, lens, calls // full_steps)
-            stages[k] = {"ms_per_step": round(msv / full_steps, 4), "launches_per_step": calls // full_steps,
-                         "tflops": round(f / (msv / calls * 1e-3) / 1e12, 2) if f else None}
+        if args.full:
+            # dominant kernel = the stage with the largest accumulated time in the full pass; its events come from the timed region
+            dom_name, (dom_ms, dom_calls) = next(iter(prof_dom.items()))
+            fl = stage_flops(dom_name, B, lens, dom_calls // args.steps)
+            avg_ms = dom_ms / max(dom_calls, 1)
+            achieved = fl / (avg_ms * 1e-3) / 1e12 if fl else None
+            traffic, traffic_src = pmc_traffic(dom_name)
+            stages = {}
+            for k, (msv, calls) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
+                f = stage_flops(k, B, lens, calls // full_steps)
+                stages[k] = {"ms_per_step": round(msv / full_steps, 4), "launches_per_step": calls // full_steps,
+                             "tflops": round(f / (msv / calls * 1e-3) / 1e12, 2) if f else None}
         fold = ctx.get_option(capi.OPT_LG_FOLD_WO)
         out = {
             "metric": "frames/s SuperPoint+LightGlue 640x480", "value": round(value, 2), "unit": "frames/s",
@@ -1222,26 +1302,31 @@ def main():
             "per_rank_ms_per_step": {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3), "all": [round(v, 3) for v in per_rank_ms],
                                      "outlier": bool(max(per_rank_ms) > 1.05 * min(per_rank_ms)),
                                      "outlier_rule": "max / min > 1.05: one rank's own clock over the barrier-bracketed region is 5 % off the fastest (a slow GPU, a noisy host core)"},
-            "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 2) if achieved else None,
-                         "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_TFLOPS, 4) if achieved else None,
-                         "traffic": traffic, "traffic_unit": "bytes/launch (rocprofv3 PMC, separate pass)",
-                         "traffic_source": traffic_src, "avg_launch_ms": round(avg_ms, 4), "launches": dom_calls,
-                         "flops_per_launch": fl},
-            "stages": stages,
-            "stages_note": f"separate untimed pass of {full_steps} steps with events around every stage (costs ~2 %); the timed "
-                           "region instruments the dominant kernel only",
         }
+        if args.full:
+            out["roofline"] = {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 2) if achieved else None,
+                               "peak": PEAK_F32_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_TFLOPS, 4) if achieved else None,
+                               "traffic": traffic, "traffic_unit": "bytes/launch (rocprofv3 PMC, separate pass)",
+                               "traffic_source": traffic_src, "avg_launch_ms": round(avg_ms, 4), "launches": dom_calls,
+                               "flops_per_launch": fl}
+            out["stages"] = stages
+            out["stages_note"] = (f"separate untimed pass of {full_steps} steps with events around every stage (costs ~2 %); the timed "
+                                  "region instruments the dominant kernel only")
         if args.lg_fp16x2:
             out["dtype"] = "f32; LightGlue Linears + attention as fp16 hi + lo split products on the f16 matrix pipe, fp32 accumulation (RFE_OPT_LG_FP16X2)"
             out["diagnostic"] = "--lg-fp16x2 1: a profiling run of the OPTION, not the headline configuration (default runs keep the option off and report it as variants.fp16x2)"
-            if dom_name.startswith("lg_") and achieved:
+            if args.full and dom_name.startswith("lg_") and achieved:
                 pk = 2500.0 / 3.0   # f16 dense peak / three products per fp32 product
                 out["roofline"].update({"peak": round(pk, 1), "frac": round(achieved / pk, 4), "unit": "TFLOP/s fp32-equivalent"})
         if rccl is not None:
             out["rccl"] = rccl
             out["rccl"]["untimed_collective_warmup_rounds"] = collective_warmup
             out["gather"] = {"collectives_per_step": 1, "payload_bytes_per_rank": gather.nbytes, "with_descriptors": bool(args.gather_desc),
-                             "receive_buffer": "preallocated once on rank 0", "last_step_payload_verified": gathered_ok}
+                             "receive_buffer": "preallocated once on rank 0"}
+            if args.full:
+                out["gather"]["last_step_payload_verified"] = gathered_ok
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if sustained is not None:
             out["sustained"] = sustained
         if variants is not None:
@@ -1255,7 +1340,7 @@ def main():
         elif pcie is not None:
             out["pcie_inclusive"] = {"value": round(pcie, 2), "unit": "frames/s",
                                      "note": "same step with H2D of the 33 u8 frames and D2H of all results (descriptors included) per step, pinned host memory, double buffered on a copy stream; not the headline value"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             gpu = {k: v.cpu().numpy() for k, v in (("n", n), ("kxy", kxy), ("score", score), ("desc", desc), ("S", S), ("pairs", pairs), ("ms", ms))}
             gpu["fold"] = fold
             if fp16x2_out is not None:

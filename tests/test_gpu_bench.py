@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def _bench(*argv, env=None):
 
 
 def test_bench_line_contract_single_gpu():
-    d = _bench("--steps", "3", "--warmup", "1", "--sustained-steps", "20", "--no-cpu-baseline")
+    d = _bench("--full", "--steps", "3", "--warmup", "1", "--sustained-steps", "20", "--no-cpu-baseline")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "sustained"):
         assert k in d, k
@@ -52,7 +53,7 @@ def test_bench_line_contract_single_gpu():
 
 
 def test_bench_gpus2_over_gloo_on_one_gpu():
-    d = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--sustained-steps", "0", env={"RFE_BENCH_BACKEND": "gloo"})
+    d = _bench("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--sustained-steps", "0", env={"RFE_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["ranks"] == 2 and "child processes" in d["launcher"]
     assert d["rccl"]["world_size"] == 2 and d["rccl"]["allreduce_sum_of_ones"] == 2 and len(d["rccl"]["devices"]) == 2
     assert d["gather"]["collectives_per_step"] == 1 and d["gather"]["last_step_payload_verified"] is True
@@ -65,9 +66,33 @@ def test_bench_rccl_code_path_at_world_size_one():
     """RCCL needs one GPU per rank, so the N-rank run belongs to the driver's 8-GPU box; what CAN run here is the same code path
     at world size 1 (RFE_BENCH_FORCE_PG=1): process group on the "nccl" backend bound to the device, object all-gather, device
     all-reduce, barrier-bracketed timing and the per-step dist.gather of the packed results into the preallocated buffer."""
-    d = _bench("--steps", "2", "--warmup", "1", "--sustained-steps", "4", "--no-cpu-baseline", "--no-pcie", env={"RFE_BENCH_FORCE_PG": "1"})
+    d = _bench("--full", "--steps", "2", "--warmup", "1", "--sustained-steps", "4", "--no-cpu-baseline", "--no-pcie", env={"RFE_BENCH_FORCE_PG": "1"})
     assert d["n_gpus"] == 1 and d["rccl"]["backend"] == "nccl" and d["rccl"]["world_size"] == 1 and d["rccl"]["allreduce_sum_of_ones"] == 1
     assert d["gather"]["collectives_per_step"] == 1 and d["gather"]["last_step_payload_verified"] is True
     assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
     assert d["rccl"]["untimed_collective_warmup_rounds"] >= 3          # the timed region never holds a communicator's first collectives
     assert "r04_pairing_step_time_ratio" not in d.get("perf_notes", {})  # no step-time comparison against a loop that holds collectives
+
+
+def test_bench_plain_line_and_outputs(tmp_path):
+    """A plain run (no --full): the headline fields only, `steps` timed steps, and --dump-outputs writes the last timed step's results as
+    float32 / float64 .npy files within 64 MB, zero past every frame's keypoint count and every pair's match count"""
+    out = tmp_path / "outputs"
+    d = _bench("--steps", "4", "--warmup", "1", "--dump-outputs", str(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "frames/s"
+    for k in ("roofline", "stages", "sustained", "variants", "pcie_inclusive", "pool_c_abi", "latency", "cpu_baseline"):
+        assert k not in d, k
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    a = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(a) == {"n", "kxy", "score", "desc", "S", "pairs", "ms"} and sorted(d["dump_outputs"]["files"]) == sorted(f + ".npy" for f in a)
+    assert sum(os.path.getsize(out / (f + ".npy")) for f in a) <= 64 * 10 ** 6
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["n"].shape == (33,) and a["desc"].shape == (33, 1024, 256) and a["S"].shape == (32,) and a["pairs"].shape == (32, 1024, 2)
+    n, S = a["n"].astype(int), a["S"].astype(int)
+    assert (n > 0).all() and (n <= 1024).all() and S.sum() > 0
+    for i in range(33):
+        assert not a["desc"][i, n[i]:].any() and not a["kxy"][i, n[i]:].any() and np.isfinite(a["desc"][i, :n[i]]).all()
+    for q in range(32):
+        assert not a["pairs"][q, S[q]:].any() and not a["ms"][q, S[q]:].any() and (a["ms"][q, :S[q]] > 0.1).all()

@@ -21,6 +21,7 @@ torch = pytest.importorskip("torch")
 from rover_slam_amd import onnx_weights as OW, weights as Wt  # noqa: E402
 import onnx_export as X  # noqa: E402  (tools/, on sys.path through conftest.py)
 from onnx_export import SuperPointPublished, LightGluePublished  # noqa: E402,F401
+from tolerances import LG_SCORE_TOL_SMALL  # noqa: E402
 
 _load_sp, _load_lg, _lg_inputs = X.load_sp, X.load_lg, X.lg_inputs
 
@@ -109,4 +110,6 @@ def test_lightglue_published_forward_matches_oracle(oracle):
     assert np.abs(x0[0].numpy() - r["x0"]).max() < 1e-4 and np.abs(x1[0].numpy() - r["x1"]).max() < 1e-4
     assert np.abs(scores[0].numpy() - r["scores"]).max() < 1e-5 * np.abs(r["scores"]).max()
     assert r["S"] > 10 and np.array_equal(pairs.numpy().astype(np.int32), r["pairs"])
-    assert np.abs(ms.numpy() - r["ms"]).max() < 1e-4
+    # match scores of the seeded (ill-conditioned) set at <= 256 keypoints: the stated fp32 bar (tests/tolerances.py); torch-CPU's BLAS picks
+    # other kernels, and so another summation order, on other host CPUs (1.1e-4 measured on one)
+    assert np.abs(ms.numpy() - r["ms"]).max() < LG_SCORE_TOL_SMALL

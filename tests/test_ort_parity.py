@@ -35,7 +35,9 @@ def test_harness_runs_end_to_end_on_graph_execution(tmp_path, golden_dir, case, 
     out = capsys.readouterr().out
     assert rc == 0, out
     assert "same_set=True" in out and "same_set=False" not in out and "identical=True" in out and "within the bars" in out
-    # the recording equals the committed fixture (integers exactly, floats to the run-to-run noise of multi-threaded torch-CPU kernels)
+    # the recording equals the committed fixture: integers exactly, floats to the run-to-run noise of multi-threaded torch-CPU kernels -- except the
+    # LightGlue match scores, the one output whose fp32 rounding is amplified 1e2-1e4 x (tests/tolerances.py): on a host CPU where torch's BLAS
+    # takes other kernels (another summation order) they move by up to 1.6e-4, so they are held to the case's own stated bar against the oracle
     a, b = np.load(rec), np.load(os.path.join(golden_dir, f"onnx_{case}.npz"))
     assert sorted(a.files) == sorted(b.files)
     assert str(a["sp_onnx_weights_sha256"]) == str(b["sp_onnx_weights_sha256"]) and str(a["lg_onnx_weights_sha256"]) == str(b["lg_onnx_weights_sha256"])
@@ -43,7 +45,8 @@ def test_harness_runs_end_to_end_on_graph_execution(tmp_path, golden_dir, case, 
         if a[k].dtype.kind in "iu":
             assert np.array_equal(a[k], b[k]), k
         elif a[k].dtype.kind == "f":
-            assert a[k].shape == b[k].shape and np.abs(a[k] - b[k]).max() <= 2e-6, k
+            bar = G.CASES[case]["mscore_tol"] if "mscores" in k else 2e-6
+            assert a[k].shape == b[k].shape and np.abs(a[k] - b[k]).max() <= bar, k
     # the replay backend (what the GPU box runs) accepts the committed fixture and reaches the same verdict on the oracle
     assert P.main(G.harness_args(case, sp, lg) + ["--backend", "replay", "--replay", os.path.join(golden_dir, f"onnx_{case}.npz")]) == 0
 

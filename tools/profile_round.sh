@@ -11,9 +11,9 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 python3 tools/stamp.py --box $OUT/stamp.json
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 400 $OUT/bench.err
-B="--no-cpu-baseline --no-variants --no-pool --no-latency --sustained-steps 0"
+B="--full --no-cpu-baseline --no-variants --no-pool --no-latency --sustained-steps 0"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python3 $R/bench.py --steps 3 --warmup 1 $B > $OUT/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o f -- python3 $R/bench.py --steps 2 --warmup 1 $B > $OUT/pmc_fetch.log 2>&1
@@ -30,7 +30,7 @@ bash tools/pmc_wait.sh ${TAG}_wait --steps 2 --warmup 1 > /dev/null 2>&1
 bash tools/pmc_wait.sh ${TAG}_wait_c3 --workload c3 --steps 10 --warmup 2 > /dev/null 2>&1
 if [ -z "$QUICK" ]; then
   # RFE_OPT_LG_FP16X2 = 1 (default off; never the headline): the option's own evidence, from the same binary
-  python bench.py --steps 20 --warmup 3 --lg-fp16x2 1 --no-pool --no-pcie > $OUT/bench_fp16x2.json 2>> $OUT/bench.err
+  python bench.py --full --steps 20 --warmup 3 --lg-fp16x2 1 --no-pool --no-pcie > $OUT/bench_fp16x2.json 2>> $OUT/bench.err
   (cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/trace_fp16x2 -o t -- python3 $R/bench.py --steps 3 --warmup 1 $B --no-pcie --lg-fp16x2 1 > $OUT/trace_fp16x2.log 2>&1)
   python3 tools/rocpd_stats.py $(find $OUT/trace_fp16x2 -name "*_results.db" | head -1) > $OUT/stats_fp16x2.md
   (cd /tmp && rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES --kernel-trace -d $OUT/pmc_sq_fp16x2 -o s -- python3 $R/bench.py --steps 2 --warmup 1 $B --no-pcie --lg-fp16x2 1 > $OUT/pmc_sq_fp16x2.log 2>&1)
