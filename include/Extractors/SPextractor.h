@@ -5,7 +5,9 @@
 #ifndef SPEXTRACTOR_H
 #define SPEXTRACTOR_H
 #include <cassert>
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "superpoint_onnx.h"
@@ -58,10 +60,15 @@ public:
         cv::Mat image = _image.getMat();
         assert(image.type() == CV_8UC1);           // SPextractor.cc:525
         if (nlevels == 1) return ExtractSingleLayer(image, _keypoints, _descriptors);
+#if defined(RFE_SP_PYRAMID) && RFE_SP_PYRAMID
+        // opt-in (-DRFE_SP_PYRAMID=1): SuperPoint on every level of the scale pyramid, merged as ExtractMultiLayers merges (SPextractor.cc:640-651)
+        return ExtractMultiLayers(image, _keypoints, _descriptors);
+#else
         // nlevels > 1: the reference's ExtractMultiLayers never calls the model (SPextractor.cc:629,634 are
-        // commented out) and returns an empty result; reproduced.
+        // commented out) and returns an empty result; reproduced unless the integrator opts in with RFE_SP_PYRAMID=1.
         _keypoints.clear();
         return 0;
+#endif
     }
 
     int inline GetLevels() { return nlevels; }
@@ -87,6 +94,33 @@ protected:
         featureExtractor->Extract_u8_direct(image.ptr<unsigned char>(0), image.rows, image.cols, (int)image.step, vKeyPoints, Descriptors);
         return (int)vKeyPoints.size();
     }
+
+#if defined(RFE_SP_PYRAMID) && RFE_SP_PYRAMID
+    // The frame's budget nfeatures is split over the levels by the constructor (mnFeaturesPerLevel, which the reference computes and never
+    // uses); each level is also capped by the model file's max_keypoints.  mvImagePyramid receives the level images, as ComputePyramid fills it.
+    int ExtractMultiLayers(const cv::Mat& image, std::vector<cv::KeyPoint>& vKeyPoints, cv::Mat& Descriptors) {
+        featureExtractor->lastmatch = lastmatchnum;
+        vKeyPoints.clear();
+        std::vector<int32_t> kmax((size_t)nlevels), lh((size_t)nlevels), lw((size_t)nlevels);
+        std::vector<float> ls((size_t)nlevels);
+        for (int l = 0; l < nlevels; ++l) kmax[l] = std::min(mnFeaturesPerLevel[l], featureExtractor->max_keypoints);
+        if (rfe_pyramid_geometry(image.rows, image.cols, nlevels, (float)scaleFactor, lh.data(), lw.data(), ls.data()) != RFE_OK) return 0;
+        size_t total = 0;
+        for (int l = 0; l < nlevels; ++l) total += (size_t)lh[l] * lw[l];
+        if (levelBuf_.size() < total) levelBuf_.resize(total);
+        if (featureExtractor->Extract_pyramid_u8(image.ptr<unsigned char>(0), image.rows, image.cols, (int)image.step, nlevels, (float)scaleFactor,
+                                                 kmax.data(), vKeyPoints, Descriptors, levelBuf_.data()) != EXIT_SUCCESS)
+            return 0;
+        size_t off = 0;
+        for (int l = 0; l < nlevels; ++l) {   // a fresh Mat per level and frame, like ComputePyramid's
+            mvImagePyramid[l] = cv::Mat(lh[l], lw[l], CV_8U);
+            for (int r = 0; r < lh[l]; ++r) std::memcpy(mvImagePyramid[l].ptr<unsigned char>(r), levelBuf_.data() + off + (size_t)r * lw[l], (size_t)lw[l]);
+            off += (size_t)lh[l] * lw[l];
+        }
+        return (int)vKeyPoints.size();
+    }
+    std::vector<unsigned char> levelBuf_;   // the library's level buffer [sum_l H_l * W_l]
+#endif
 
     int nfeatures;
     double scaleFactor;

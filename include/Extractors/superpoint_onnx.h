@@ -117,6 +117,40 @@ public:
         return EXIT_SUCCESS;
     }
 
+    // SuperPoint on a scale pyramid (rfe_extract_pyramid_u8, for SPextractor::ExtractMultiLayers): kmax[l] keypoints at most on level l, the
+    // rows of every level in level order; pt = level-l pixel * mvScaleFactor[l] (level-0 pixels), octave = l, response = score, size 10 (what the
+    // per-level post-processing sets; the reference's ExtractMultiLayers changes only octave and pt).  Descriptors: N x 256 CV_32F.  levels:
+    // optional, receives the level images [sum_l H_l * W_l] (level 0 first, tight pitch).
+    int Extract_pyramid_u8(const unsigned char* img, int H, int W, int stride, int nlevels, float scaleFactor, const int32_t* kmax,
+                           std::vector<cv::KeyPoint>& vKeyPoints, cv::Mat& Descriptors, unsigned char* levels = nullptr) {
+        extractor_outputtensors.clear();
+        if (!ExtractorSession) { std::cerr << "[ERROR] Extractor inference failed : no session" << std::endl; return EXIT_FAILURE; }
+        int K = 0;
+        for (int l = 0; l < nlevels && kmax; ++l) K += kmax[l] > 0 ? kmax[l] : 0;
+        const size_t rows = (size_t)(K > 0 ? K : 1);
+        if (stage_kpts_.size() < rows * 2) stage_kpts_.resize(rows * 2);
+        if (stage_score_.size() < rows) stage_score_.resize(rows);
+        if (stage_oct_.size() < rows) stage_oct_.resize(rows);
+        cv::Mat d((int)rows, 256, CV_32F);
+        int32_t n = 0;
+        auto t0 = std::chrono::high_resolution_clock::now();
+        const int rc = rfe_extract_pyramid_u8(ExtractorSession, img, H, W, stride, 1, nlevels, scaleFactor, kmax, detection_threshold, &n, nullptr,
+                                              stage_kpts_.data(), stage_oct_.data(), stage_score_.data(), d.ptr<float>(0), levels);
+        extractor_timer += std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - t0).count();
+        if (rc != RFE_OK) { std::cerr << "[ERROR] Extractor inference failed : " << rfe_last_error(ExtractorSession) << std::endl; return EXIT_FAILURE; }
+        vKeyPoints.reserve(vKeyPoints.size() + (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            cv::KeyPoint kp;
+            kp.pt = cv::Point2f(stage_kpts_[2 * i], stage_kpts_[2 * i + 1]);
+            kp.response = stage_score_[i];
+            kp.size = 10;
+            kp.octave = stage_oct_[i];
+            vKeyPoints.emplace_back(kp);
+        }
+        Descriptors = (size_t)n == rows ? d : d.rowRange(0, n);
+        return EXIT_SUCCESS;
+    }
+
     // reference superpoint_onnx.cc:88-162: image is a CV_32F single-channel image, normally NormalizeImage's output; like the graph,
     // the kernels take the values as they are (no assumption that they are multiples of 1/255 or inside [0, 1])
     int Extractor_Inference(Configuration, const cv::Mat& image) {
@@ -191,6 +225,8 @@ private:
     }
     std::vector<int32_t> stage_kxy_;
     std::vector<float> stage_score_;
+    std::vector<float> stage_kpts_;
+    std::vector<int32_t> stage_oct_;
 
     // blocks of one size, handed out as shared_ptr whose deleter puts them back; the pool outlives the runner while tensors are in flight
     struct PinnedPool : std::enable_shared_from_this<PinnedPool> {

@@ -197,6 +197,33 @@ int rfe_extract_u8_bin(rfe_ctx* ctx, const uint8_t* img, int H, int W, int strid
 int rfe_extract_u8_bin_dev(rfe_ctx* ctx, const uint8_t* img_dev, int H, int W, int stride, int B, int Kmax, float thr,
                            int32_t* n_dev, int32_t* kxy_dev, float* score_dev, float* desc_dev, uint8_t* desc_bin_dev);
 
+/* ---- SuperPoint on a scale pyramid (SPextractor with nlevels > 1) ----
+ * The reference's ExtractMultiLayers (src/Extractors/SPextractor.cc:619-653) over the levels of ComputePyramid (:686-712): level l is
+ * W_l x H_l = lrintf(W / s_l) x lrintf(H / s_l), s_0 = 1, s_l = (float)((double)s_{l-1} * scale_factor), made from level l-1 by 11-bit
+ * fixed-point bilinear resampling with half-pixel centres (modelled on cv::resize INTER_LINEAR; bit parity with OpenCV is NOT claimed).
+ * Every level runs the rfe_extract_u8 pipeline with Kmax = kmax[l] (a level below 8 px or with kmax[l] == 0 yields no keypoints), and
+ * the rows are merged per frame in level order: row i of level l lands at sum_{j<l} n_j + i with kpts = (x * s_l, y * s_l) (one fp32
+ * multiply, keypoint.pt *= mvScaleFactor[level]), octave = l, score / desc unchanged.
+ * rfe_pyramid_geometry: pure function, no device (like rfe_pool_shard): the level sizes and scale factors; RFE_ERR_INVALID for arguments
+ * rfe_extract_pyramid_u8 refuses (the arrays are still filled when only a level rounds to zero pixels). */
+#define RFE_MAX_LEVELS 16
+int rfe_pyramid_geometry(int H, int W, int nlevels, float scale_factor, int32_t* level_h, int32_t* level_w, float* level_scale);
+/* B frames of H x W (row pitch stride, frame pitch stride*H); kmax [nlevels] is a HOST array; Ktot = sum of kmax.
+ * n [B], level_n [B,nlevels] (may be NULL), kpts [B,Ktot,2] f32 level-0 pixels, octave [B,Ktot] i32, score [B,Ktot],
+ * desc [B,Ktot,256]; levels [B, sum_l H_l*W_l] u8, level 0 first, tight pitch (may be NULL).  Rows >= n[b] are zero.
+ * Refused (RFE_ERR_INVALID): nlevels outside 1..16; scale_factor <= 1 or > 4 when nlevels > 1; a kmax[l] outside 0..4096, or all 0;
+ * H or W below 8, B below 1, stride below W; a NULL required pointer; a level that rounds to zero pixels.
+ * RFE_OPT_HOST_GRAPH does not apply to these entries (their kernel sequence is submitted the ordinary way).  The first call of an
+ * (H, W, nlevels, scale_factor) uploads its resampling tables and synchronises the ctx stream, as a workspace growth does. */
+int rfe_extract_pyramid_u8(rfe_ctx* ctx, const uint8_t* img, int H, int W, int stride, int B, int nlevels, float scale_factor,
+                           const int32_t* kmax, float thr, int32_t* n, int32_t* level_n, float* kpts, int32_t* octave,
+                           float* score, float* desc, uint8_t* levels);
+/* The same with device pointers (except kmax), asynchronous on the ctx stream: no host synchronisation and no host read of device
+ * data after the first call of a shape.  With `levels`, the pyramid is built there and SuperPoint reads levels >= 1 from it. */
+int rfe_extract_pyramid_u8_dev(rfe_ctx* ctx, const uint8_t* img_dev, int H, int W, int stride, int B, int nlevels, float scale_factor,
+                               const int32_t* kmax, float thr, int32_t* n_dev, int32_t* level_n_dev, float* kpts_dev,
+                               int32_t* octave_dev, float* score_dev, float* desc_dev, uint8_t* levels_dev);
+
 /* ---- LightGlue ----
  * P pairs.  k0n/k1n: normalised keypoints [P,Mmax,2] / [P,Nmax,2]; d0/d1: [P,Mmax,256] /
  * [P,Nmax,256]; m/n: [P] valid counts.  filter_thr: in-graph match filter (0.1).

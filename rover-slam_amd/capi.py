@@ -18,7 +18,8 @@ OPT_HOST_GRAPH = 3   # host entries replay a captured hipGraph per repeated call
 EXPORTS = [
     "rfe_init", "rfe_destroy", "rfe_last_error", "rfe_version", "rfe_load_weights", "rfe_load_onnx", "rfe_set_weights",
     "rfe_weight_count", "rfe_weights_id", "rfe_get_hparams", "rfe_set_hparams", "rfe_set_option", "rfe_get_option", "rfe_set_stream", "rfe_synchronize", "rfe_malloc", "rfe_free", "rfe_host_malloc", "rfe_host_free", "rfe_workspace_bytes", "rfe_memcpy_h2d",
-    "rfe_memcpy_d2h", "rfe_extract_u8", "rfe_extract_u8_dev", "rfe_extract_f32", "rfe_extract_f32_dev", "rfe_extract_u8_bin", "rfe_extract_u8_bin_dev", "rfe_match", "rfe_match_dev", "rfe_match_fused",
+    "rfe_memcpy_d2h", "rfe_extract_u8", "rfe_extract_u8_dev", "rfe_extract_f32", "rfe_extract_f32_dev", "rfe_extract_u8_bin", "rfe_extract_u8_bin_dev",
+    "rfe_pyramid_geometry", "rfe_extract_pyramid_u8", "rfe_extract_pyramid_u8_dev", "rfe_match", "rfe_match_dev", "rfe_match_fused",
     "rfe_extract_match_stream_dev", "rfe_stereo_match", "rfe_stereo_match_dev", "rfe_stereo_frame_dev", "rfe_l2_distance_matrix", "rfe_binarize_descriptors",
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
@@ -76,6 +77,10 @@ lib.rfe_extract_f32_dev.argtypes = _ext
 lib.rfe_extract_u8_dev.argtypes = _ext
 lib.rfe_extract_u8_bin.argtypes = _ext + [_u8p]
 lib.rfe_extract_u8_bin_dev.argtypes = _ext + [_u8p]
+lib.rfe_pyramid_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _ip, _ip, _fp]
+_pyr = [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _ip, C.c_float, _ip, _ip, _fp, _ip, _fp, _fp, _u8p]
+lib.rfe_extract_pyramid_u8.argtypes = _pyr
+lib.rfe_extract_pyramid_u8_dev.argtypes = _pyr
 _mt = [C.c_void_p, _fp, _fp, _fp, _fp, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_float, _ip, _ip, _fp]
 lib.rfe_match.argtypes = _mt
 lib.rfe_match_dev.argtypes = _mt
@@ -183,6 +188,15 @@ class DevBuf:
             self.ptr = None
 
 
+def split_levels(flat, level_h, level_w):
+    """[B, sum_l H_l*W_l] level buffer of rfe_extract_pyramid_u8 -> list of [B,H_l,W_l] views, level 0 first."""
+    out, off = [], 0
+    for h, w in zip(level_h, level_w):
+        out.append(flat[:, off:off + int(h) * int(w)].reshape(flat.shape[0], int(h), int(w)))
+        off += int(h) * int(w)
+    return out
+
+
 class StereoStream:
     """Device-resident stereo stream (rfe_stereo_frame_dev): owns the output buffers, push() enqueues one stereo frame
     (device image pointers) without any host synchronisation, results() downloads the last frame's outputs."""
@@ -215,6 +229,20 @@ class StereoStream:
         for b in self.bufs.values():
             b.free()
         self.bufs = {}
+
+
+MAX_LEVELS = 16
+
+
+def pyramid_geometry(H, W, nlevels, scale_factor):
+    """rfe_pyramid_geometry: (level_h, level_w, level_scale) of the scale pyramid (pure function, no device).  Raises RfeError for
+    arguments rfe_extract_pyramid_u8 refuses, a level that rounds to zero pixels included."""
+    L = max(int(nlevels), 1)
+    h, w, s = np.zeros((L,), np.int32), np.zeros((L,), np.int32), np.zeros((L,), np.float32)
+    rc = lib.rfe_pyramid_geometry(H, W, nlevels, scale_factor, h.ctypes.data, w.ctypes.data, s.ctypes.data)
+    if rc < 0:
+        raise RfeError(f"rfe_pyramid_geometry({H}, {W}, {nlevels}, {scale_factor}) failed ({rc})")
+    return h, w, s
 
 
 def pool_shard(F, n, member):
@@ -393,6 +421,36 @@ class Context:
         self._chk(lib.rfe_extract_u8(self.h, img.ctypes.data, H, W, stride, B, kmax, thr, n.ctypes.data, kxy.ctypes.data,
                                      score.ctypes.data, desc.ctypes.data))
         return n, kxy, score, desc
+
+    def extract_pyramid(self, frames_u8, nlevels=8, scale_factor=1.2, kmax=1024, thr=0.0005, with_levels=False, pad_cols=0):
+        """SuperPoint on a scale pyramid (rfe_extract_pyramid_u8).  frames_u8: [B,H,W] or [H,W] uint8 (host); kmax: an int (every level)
+        or one budget per level.  Returns a dict: n [B], level_n [B,L], kpts [B,Ktot,2] f32 level-0 pixels, octave [B,Ktot], score [B,Ktot],
+        desc [B,Ktot,256] (Ktot = sum of the budgets) and, with_levels, levels: a list of L arrays [B,H_l,W_l] u8."""
+        img = np.ascontiguousarray(frames_u8, np.uint8)
+        if img.ndim == 2:
+            img = img[None]
+        B, H, W = img.shape
+        stride = W + pad_cols
+        if pad_cols:
+            wide = np.full((B, H, stride), 255, np.uint8)
+            wide[:, :, :W] = img
+            img = wide
+        L = int(nlevels)
+        km = np.full((max(L, 1),), int(kmax), np.int32) if np.isscalar(kmax) else np.ascontiguousarray(kmax, np.int32)
+        K = int(km.sum())
+        out = {"n": np.zeros((B,), np.int32), "level_n": np.zeros((B, max(L, 1)), np.int32), "kpts": np.zeros((B, K, 2), np.float32),
+               "octave": np.zeros((B, K), np.int32), "score": np.zeros((B, K), np.float32), "desc": np.zeros((B, K, 256), np.float32)}
+        lv = None
+        if with_levels:
+            lh, lw, _ = pyramid_geometry(H, W, L, scale_factor)
+            lv = np.zeros((B, int((lh.astype(np.int64) * lw).sum())), np.uint8)
+        self._chk(lib.rfe_extract_pyramid_u8(self.h, img.ctypes.data, H, W, stride, B, L, scale_factor, km.ctypes.data, thr,
+                                             out["n"].ctypes.data, out["level_n"].ctypes.data, out["kpts"].ctypes.data,
+                                             out["octave"].ctypes.data, out["score"].ctypes.data, out["desc"].ctypes.data,
+                                             None if lv is None else lv.ctypes.data))
+        if with_levels:
+            out["levels"] = split_levels(lv, lh, lw)
+        return out
 
     def extract_f32(self, img_f32, kmax=1024, thr=0.0005):
         """The float entry: img_f32 [B,H,W] or [H,W] float32, already normalised (what the reference's Extractor_Inference is handed).

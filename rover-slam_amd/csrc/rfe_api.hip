@@ -186,7 +186,8 @@ extern "C" int rfe_init(int device, rfe_ctx** out) {
     c->stream = c->own_stream;
     if ((e = hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess) {
+        (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&c->ev_pyr, hipEventDisableTiming)) != hipSuccess) {
         rfe_destroy(c);
         return fail(nullptr, RFE_ERR_HIP, std::string("hipStreamCreate/hipEventCreate: ") + hipGetErrorString(e));
     }
@@ -204,11 +205,12 @@ extern "C" void rfe_destroy(rfe_ctx* c) {
     host_graph_release(c->g_match);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     c->sp_hold.reset(); c->lg_hold.reset();   // the last ctx holding a device copy frees it
-    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->sp_cnt);
+    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->sp_cnt); fr(c->ws_pyr); fr(c->ws_ptab);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    if (c->ev_pyr) (void)hipEventDestroy(c->ev_pyr);
     (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -515,7 +517,7 @@ extern "C" void rfe_host_free(void* p) {
 }
 
 extern "C" int64_t rfe_workspace_bytes(rfe_ctx* c) {
-    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes) : 0;
+    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes + c->ws_pyr_bytes + c->ws_ptab_bytes) : 0;
 }
 
 extern "C" uint64_t rfe_weights_id(rfe_ctx* c, int kind) {
@@ -917,6 +919,183 @@ extern "C" int rfe_extract_f32(rfe_ctx* c, const float* img, int H, int W, int s
     memcpy(kxy, hp + ib + nb, (size_t)B * Kmax * 8);
     memcpy(score, hp + ib + nb + kb, (size_t)B * Kmax * 4);
     if (!direct) memcpy(desc, hp + ib + nb + kb + sb, (size_t)B * Kmax * 1024);
+    prof_collect(c);
+    return RFE_OK;
+}
+
+// =====================================================================================
+// SuperPoint on a scale pyramid: the level chain on the side stream behind level 0's SuperPoint, every level through
+// sp_forward into per-level staging (ws_pyr: sp_forward carves ws_sp from offset 0 on every call), one merge launch
+// =====================================================================================
+extern "C" int rfe_pyramid_geometry(int H, int W, int nlevels, float scale_factor, int32_t* level_h, int32_t* level_w, float* level_scale) {
+    return pyramid_geometry(H, W, nlevels, scale_factor, level_h, level_w, level_scale);
+}
+
+namespace {
+
+struct PyrPlan {
+    int L = 0, Ktot = 0;
+    int32_t h[RFE_MAX_LEVELS], w[RFE_MAX_LEVELS]; float s[RFE_MAX_LEVELS];
+    int kmax[RFE_MAX_LEVELS]; bool run[RFE_MAX_LEVELS];
+    size_t off[RFE_MAX_LEVELS];   // level l's plane inside one frame of the level buffer
+    size_t frame = 0;             // sum_l H_l * W_l
+};
+
+int pyr_check(rfe_ctx* c, int H, int W, int stride, int B, int L, float sf, const int32_t* kmax, PyrPlan& P) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!c->has_sp) return fail(c, RFE_ERR_NO_WEIGHTS, "SuperPoint weights not loaded (rfe_load_weights / rfe_set_weights)");
+    if (L < 1 || L > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, "extract_pyramid: nlevels must be in 1..16");
+    if (L > 1 && !(sf > 1.0f && sf <= 4.0f)) return fail(c, RFE_ERR_INVALID, "extract_pyramid: scale_factor must be in (1, 4] when nlevels > 1");
+    if (H < 8 || W < 8 || B < 1 || stride < W) return fail(c, RFE_ERR_INVALID, "extract_pyramid: H and W must be at least 8, B > 0, stride >= W");
+    if (!kmax) return fail(c, RFE_ERR_INVALID, "extract_pyramid: null pointer");
+    P.L = L; P.Ktot = 0;
+    for (int l = 0; l < L; ++l) {
+        if (kmax[l] < 0 || kmax[l] > 4096) return fail(c, RFE_ERR_INVALID, "extract_pyramid: every kmax[l] must be in 0..4096");
+        P.kmax[l] = kmax[l]; P.Ktot += kmax[l];
+    }
+    if (P.Ktot == 0) return fail(c, RFE_ERR_INVALID, "extract_pyramid: every kmax[l] is 0");
+    if (pyramid_geometry(H, W, L, sf, P.h, P.w, P.s) != RFE_OK) return fail(c, RFE_ERR_INVALID, "extract_pyramid: a level rounds to zero pixels");
+    P.frame = 0;
+    for (int l = 0; l < L; ++l) {
+        P.off[l] = P.frame; P.frame += (size_t)P.h[l] * P.w[l];
+        P.run[l] = P.kmax[l] > 0 && P.h[l] >= 8 && P.w[l] >= 8;
+    }
+    return RFE_OK;
+}
+
+size_t pyr_stage_bytes(const PyrPlan& P, int B) {
+    size_t t = 0;
+    for (int l = 0; l < P.L; ++l)
+        if (P.run[l]) t += al((size_t)B * 4) + al((size_t)B * P.kmax[l] * 8) + al((size_t)B * P.kmax[l] * 4) + al((size_t)B * P.kmax[l] * 1024);
+    return t;
+}
+
+// Every allocation of the call happens here, before the first kernel is enqueued (ensure_ws synchronises and frees when it grows):
+// ws_sp for the largest level, ws_pyr for the internal level images (own_levels) + staging, the tables of this geometry, sp_cnt.
+int pyr_prepare(rfe_ctx* c, int H, int W, int B, float sf, const PyrPlan& P, bool own_levels) {
+    int rc;
+    if ((rc = ensure_ws(c, &c->ws_sp, &c->ws_sp_bytes, sp_ws_bytes(B, H, W)))) return rc;
+    if ((rc = ensure_ws(c, &c->ws_pyr, &c->ws_pyr_bytes, (own_levels ? al((size_t)B * P.frame) : 0) + pyr_stage_bytes(P, B)))) return rc;
+    if (!c->sp_cnt) { RFE_HIP(c, hipMalloc((void**)&c->sp_cnt, 8 * sizeof(int32_t))); c->sp_cnt_dirty = true; }
+    int sf_bits; memcpy(&sf_bits, &sf, 4);
+    const std::string key = std::to_string(H) + "x" + std::to_string(W) + "|" + std::to_string(P.L) + "|" + std::to_string(P.L > 1 ? sf_bits : 0);
+    if (P.L > 1 && key != c->ptab_key) {
+        std::vector<int2> tab;
+        pyramid_tables(P.L, P.h, P.w, tab, c->ptab_off);
+        c->ptab_key.clear();
+        const void* before = c->ws_ptab;
+        if ((rc = ensure_ws(c, &c->ws_ptab, &c->ws_ptab_bytes, tab.size() * sizeof(int2)))) return rc;
+        if (before == c->ws_ptab) RFE_HIP(c, hipStreamSynchronize(c->stream));   // earlier calls may still read the old tables
+        RFE_HIP(c, hipMemcpy(c->ws_ptab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice));
+        c->ptab_key = key;
+    }
+    return RFE_OK;
+}
+
+// img: level 0 (caller's pitch); lv: the level buffer [B, P.frame] (caller's or ws_pyr's); outputs device pointers
+int pyr_forward(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, const PyrPlan& P, float thr, uint8_t* lv, bool copy_level0,
+                int32_t* n, int32_t* level_n, float* kpts, int32_t* octave, float* score, float* desc) {
+    hipStream_t s = c->stream;
+    // the level chain runs on the side stream, concurrently with level 0's backbone; with events around every stage (full profiling
+    // pass) it runs at the front of the main stream, so that the stage times stay clean
+    const bool side = !(c->prof && c->prof_filter.empty());
+    hipStream_t sc = side ? c->side_stream : s;
+    if (side) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(sc, c->ev_fork, 0)); }
+    { ProfScope p(c, "sp_pyramid", sc);
+      if (copy_level0) launch_pyr_resample(sc, img, (long long)stride * H, stride, H, W, lv, (long long)P.frame, H, W, B, nullptr, nullptr);
+      const int2* tab = (const int2*)c->ws_ptab;
+      for (int l = 1; l < P.L; ++l) {
+          const uint8_t* src = l == 1 ? img : lv + P.off[l - 1];
+          const long long src_frame = l == 1 ? (long long)stride * H : (long long)P.frame;
+          const int src_stride = l == 1 ? stride : P.w[l - 1];
+          launch_pyr_resample(sc, src, src_frame, src_stride, P.h[l - 1], P.w[l - 1], lv + P.off[l], (long long)P.frame, P.h[l], P.w[l], B,
+                              tab + c->ptab_off[l], tab + c->ptab_off[l] + P.w[l]);
+      } }
+    if (side) RFE_HIP(c, hipEventRecord(c->ev_pyr, sc));
+    PyrMergeArgs m;
+    memset(&m, 0, sizeof(m));
+    m.L = P.L; m.Ktot = P.Ktot;
+    Bump a(c->ws_pyr);
+    if (lv == (uint8_t*)c->ws_pyr) a.take<uint8_t>((size_t)B * P.frame);
+    int rc;
+    bool joined = !side;
+    for (int l = 0; l < P.L; ++l) {
+        m.kmax[l] = P.kmax[l]; m.scale[l] = P.s[l];
+        if (!P.run[l]) continue;
+        int32_t* ln = a.take<int32_t>((size_t)B); int32_t* lk = a.take<int32_t>((size_t)B * P.kmax[l] * 2);
+        float* ls = a.take<float>((size_t)B * P.kmax[l]); float* ld = a.take<float>((size_t)B * P.kmax[l] * 256);
+        if (l >= 1 && !joined) { RFE_HIP(c, hipStreamWaitEvent(s, c->ev_pyr, 0)); joined = true; }   // levels >= 1 read the chain's output
+        if (l == 0) rc = sp_forward(c, img, H, W, stride, B, P.kmax[0], thr, ln, lk, ls, ld);
+        else rc = sp_forward(c, lv + P.off[l], P.h[l], P.w[l], P.w[l], B, P.kmax[l], thr, ln, lk, ls, ld, nullptr, false, (long long)P.frame);
+        if (rc) return rc;
+        m.n[l] = ln; m.kxy[l] = lk; m.sc[l] = ls; m.desc_l[l] = ld;
+    }
+    // a pyramid whose levels >= 1 all yield nothing still joins the chain before returning (the caller may read `levels`)
+    if (!joined) RFE_HIP(c, hipStreamWaitEvent(s, c->ev_pyr, 0));
+    m.n_out = n; m.level_n = level_n; m.kpts = kpts; m.octave = octave; m.score = score; m.desc = desc;
+    { ProfScope p(c, "sp_merge"); launch_pyr_merge(s, m, B); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+}  // namespace
+
+extern "C" int rfe_extract_pyramid_u8_dev(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, int nlevels, float scale_factor,
+                                          const int32_t* kmax, float thr, int32_t* n, int32_t* level_n, float* kpts, int32_t* octave,
+                                          float* score, float* desc, uint8_t* levels) {
+    PyrPlan P;
+    int rc = pyr_check(c, H, W, stride, B, nlevels, scale_factor, kmax, P);
+    if (rc) return rc;
+    if (!img || !n || !kpts || !octave || !score || !desc) return fail(c, RFE_ERR_INVALID, "extract_pyramid: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    if ((rc = pyr_prepare(c, H, W, B, scale_factor, P, levels == nullptr))) return rc;
+    return pyr_forward(c, img, H, W, stride, B, P, thr, levels ? levels : (uint8_t*)c->ws_pyr, levels != nullptr, n, level_n, kpts, octave,
+                       score, desc);
+}
+
+extern "C" int rfe_extract_pyramid_u8(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, int nlevels, float scale_factor,
+                                      const int32_t* kmax, float thr, int32_t* n, int32_t* level_n, float* kpts, int32_t* octave,
+                                      float* score, float* desc, uint8_t* levels) {
+    PyrPlan P;
+    int rc = pyr_check(c, H, W, stride, B, nlevels, scale_factor, kmax, P);
+    if (rc) return rc;
+    if (!img || !n || !kpts || !octave || !score || !desc) return fail(c, RFE_ERR_INVALID, "extract_pyramid: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    // one pinned block each way: [img] in; [n | level_n | kpts | octave | score | desc | levels] out (desc DMA'd straight into an
+    // rfe_host_malloc block, as rfe_extract_u8 does)
+    const size_t K = (size_t)B * P.Ktot;
+    const size_t ib = al((size_t)B * H * W), nb = al((size_t)B * 4), lb = al((size_t)B * nlevels * 4), kb = al(K * 8), ob = al(K * 4),
+                 sb = al(K * 4), db = al(K * 1024), vb = levels ? al((size_t)B * P.frame) : 0;
+    const size_t out_bytes = nb + lb + kb + ob + sb + db + vb;
+    if ((rc = ensure_ws(c, &c->ws_io, &c->ws_io_bytes, ib + out_bytes))) return rc;
+    if ((rc = ensure_pin(c, ib + out_bytes))) return rc;
+    if ((rc = pyr_prepare(c, H, W, B, scale_factor, P, levels == nullptr))) return rc;
+    char* p = (char*)c->ws_io;
+    char* hp = (char*)c->h_pin;
+    uint8_t* d_img = (uint8_t*)p; char* o = p + ib;
+    int32_t* d_n = (int32_t*)o; int32_t* d_ln = (int32_t*)(o + nb); float* d_k = (float*)(o + nb + lb); int32_t* d_o = (int32_t*)(o + nb + lb + kb);
+    float* d_s = (float*)(o + nb + lb + kb + ob); float* d_d = (float*)(o + nb + lb + kb + ob + sb);
+    uint8_t* d_v = levels ? (uint8_t*)(o + nb + lb + kb + ob + sb + db) : nullptr;
+    for (size_t r = 0; r < (size_t)B * H; ++r) memcpy(hp + r * W, img + r * stride, (size_t)W);
+    RFE_HIP(c, hipMemcpyAsync(d_img, hp, (size_t)B * H * W, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pyr_forward(c, d_img, H, W, W, B, P, thr, d_v ? d_v : (uint8_t*)c->ws_pyr, d_v != nullptr, d_n, d_ln, d_k, d_o, d_s, d_d))) return rc;
+    const bool direct = is_lib_pinned(desc, K * 1024);
+    char* ho = hp + ib;
+    if (direct) {
+        RFE_HIP(c, hipMemcpyAsync(ho, o, nb + lb + kb + ob + sb, hipMemcpyDeviceToHost, c->stream));
+        RFE_HIP(c, hipMemcpyAsync(desc, d_d, K * 1024, hipMemcpyDeviceToHost, c->stream));
+        if (levels) RFE_HIP(c, hipMemcpyAsync(ho + nb + lb + kb + ob + sb + db, d_v, (size_t)B * P.frame, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        RFE_HIP(c, hipMemcpyAsync(ho, o, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    memcpy(n, ho, (size_t)B * 4);
+    if (level_n) memcpy(level_n, ho + nb, (size_t)B * nlevels * 4);
+    memcpy(kpts, ho + nb + lb, K * 8);
+    memcpy(octave, ho + nb + lb + kb, K * 4);
+    memcpy(score, ho + nb + lb + kb + ob, K * 4);
+    if (!direct) memcpy(desc, ho + nb + lb + kb + ob + sb, K * 1024);
+    if (levels) memcpy(levels, ho + nb + lb + kb + ob + sb + db, (size_t)B * P.frame);
     prof_collect(c);
     return RFE_OK;
 }

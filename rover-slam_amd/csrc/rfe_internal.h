@@ -116,6 +116,7 @@ struct rfe_ctx {
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;   // descriptor head of SuperPoint runs here, concurrently with the detector head
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_pyr = nullptr;         // rfe_extract_pyramid_u8*: the level chain (side stream) is done
     std::string err;
     bool has_sp = false, has_lg = false;
     bool opt_lg_fold = true;             // RFE_OPT_LG_FOLD_WO
@@ -142,6 +143,10 @@ struct rfe_ctx {
     void* ws_io = nullptr; size_t ws_io_bytes = 0;   // staging for host-pointer entry points
     void* h_pin = nullptr; size_t h_pin_bytes = 0;   // pinned host mirror of ws_io for the per-frame host entries (extract / match): one DMA each way
     void* ws_tmp = nullptr; size_t ws_tmp_bytes = 0; // test hooks
+    // rfe_extract_pyramid_u8*: level images (when the caller passes none) + per-level SuperPoint staging -- apart from ws_sp, which every
+    // SuperPoint pass carves from offset 0 -- and the resampling tables of the last (H, W, nlevels, scale_factor) in ws_ptab
+    void* ws_pyr = nullptr; size_t ws_pyr_bytes = 0;
+    void* ws_ptab = nullptr; size_t ws_ptab_bytes = 0; std::string ptab_key; std::vector<size_t> ptab_off;
     int32_t* sp_cnt = nullptr;           // [4][2] (count, tickets) of the fused detector tail (sp_post.hip: sp_tail_lat_kernel); zero between calls
     bool sp_cnt_dirty = false;           // the tail ran and its ranking kernel was not enqueued behind it (an error in between): zeroed before the next use
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
@@ -279,6 +284,26 @@ void launch_stereo_match(hipStream_t s, const uint8_t* imgL, const uint8_t* imgR
 void launch_stereo_match_counts(hipStream_t s, const uint8_t* imgL, const uint8_t* imgR, int H, int W, int stride,
                                 const int32_t* kL, const int32_t* kR, int Kmax, const int32_t* counts, const float* dL,
                                 const float* dR, float mb, float mbf, float* uRight, float* depth, int32_t* sadv);
+
+// pyramid.hip: the scale pyramid of rfe_extract_pyramid_u8
+int pyramid_geometry(int H, int W, int nlevels, float scale_factor, int32_t* level_h, int32_t* level_w, float* level_scale);
+// coefficient tables of levels 1..nlevels-1, each level's [W_l] column entries then [H_l] row entries (source index, 11-bit weight of index + 1),
+// starting at off[l]
+void pyramid_tables(int nlevels, const int32_t* level_h, const int32_t* level_w, std::vector<int2>& tab, std::vector<size_t>& off);
+// one level of B frames from the level above (cx / cy: that level's table entries); cx == null: copy the Hd x Wd source as it is
+void launch_pyr_resample(hipStream_t s, const uint8_t* src, long long src_frame, int src_stride, int Hs, int Ws, uint8_t* dst, long long dst_frame,
+                         int Hd, int Wd, int B, const int2* cx, const int2* cy);
+struct PyrMergeArgs {
+    int L, Ktot;
+    const int32_t* n[RFE_MAX_LEVELS];        // per-level staging of the SuperPoint passes ([B] counts, null = level not run: n_l = 0)
+    const int32_t* kxy[RFE_MAX_LEVELS];      // [B, kmax_l, 2]
+    const float* sc[RFE_MAX_LEVELS];         // [B, kmax_l]
+    const float* desc_l[RFE_MAX_LEVELS];     // [B, kmax_l, 256]
+    int kmax[RFE_MAX_LEVELS];
+    float scale[RFE_MAX_LEVELS];
+    int32_t* n_out; int32_t* level_n /*optional [B, L]*/; float* kpts; int32_t* octave; float* score; float* desc;
+};
+void launch_pyr_merge(hipStream_t s, const PyrMergeArgs& a, int B);
 
 void launch_l2_matrix(hipStream_t s, const float* a, int M, const float* b, int N, float* out);
 void launch_binarize(hipStream_t s, const float* d, int64_t rows, uint8_t* out);
