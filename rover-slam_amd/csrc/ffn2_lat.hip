@@ -162,8 +162,7 @@ __global__ __launch_bounds__(64 * F2_NW, 1) void ffn2_ln_lat_kernel(const float*
 // ffn.0 (bias included, not normalised).  false = shape not served, nothing launched.
 bool launch_ffn2_ln_lat(hipStream_t s, const float* h, const float* w2, const float* b2, const float* ln_g, const float* ln_b, const float* R, int ldr,
                         float* C, int ldc, int M) {
-    static const bool on = tune_int("RFE_FFN2_LAT_FUSE", 1) != 0;   // tuning build: 0 = stand-alone lg_ln_gelu + gemm_lat (round 4)
-    if (!on || M < 1 || M > 8192 || !h || !w2 || !b2 || !ln_g || !ln_b || !R || (ldr % 4) || (ldc % 4)) return false;
+    if (M < 1 || M > 8192 || !h || !w2 || !b2 || !ln_g || !ln_b || !R || (ldr % 4) || (ldc % 4)) return false;
     const int MT = (M + F2_BM - 1) / F2_BM;
     static bool ls_[64];
     ensure_dynamic_lds((const void*)ffn2_ln_lat_kernel, F2_LDS_BYTES, ls_);

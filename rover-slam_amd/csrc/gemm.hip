@@ -37,19 +37,14 @@ __device__ __forceinline__ float gelu_short(float t) {
 // RES: the residual variant reads R in the D layout (four rows of 128-B segments in flight per step) and adds it after bias /
 // alpha like the oracle.  (Round 1's LDS-transposed whole-row epilogue, which also applied the LightGlue rotary to q | k, is gone:
 // the rotary moved into the attention kernel's loads -- same arithmetic, same time overall, one epilogue fewer here.)
-// PFT: register prefetch of the next K tile under the MFMAs (always on for the 64-row latency tiles).
+// Every tile prefetches the next K tile into registers under the MFMAs (+1 % on ffn1 / ffn2 for the 128-row tiles, profiles/r02_ab_notes.md).
 // KP (k-permuted, opt-in through GemmArgs::kperm): LDS tiles [rows][32] WITHOUT padding, the eight 16-byte slots of a row XOR-swizzled
 // by (row & 7): staging writes one ds_write_b128 per loaded float4 (the padded layout needs four scalar writes), a fragment read is
 // one ds_read_b128 per four k-steps (lane half h reads k = 16 h + 4 g .. + 3 of its row; eight consecutive lanes = eight rows hit the
 // eight different slots -> all 32 banks).  MFMA step (g, c) therefore multiplies k = 4 g + c and k = 16 + 4 g + c: every product
 // of the K tile is summed, in a different order than k ascending -- LightGlue only (SuperPoint's 1x1 heads stay bit-exact on the
 // padded path).  LDS instructions per K tile and wave: 36 instead of 144.
-// DMAB (KP throughput tile only; not batched): the B tile (weights) never touches a register -- it is copied by global_load_lds_dwordx4
-// into a DOUBLE-buffered LDS tile (2 x 32 KB; with the 16 KB A tile = 80 KB per workgroup: still two workgroups per CU,
-// tools/kbench/lds_occupancy.hip), tile t + 1 requested right after tile t is published; the 16-byte-slot swizzle is applied on the SOURCE
-// address (the LDS side of the copy is lane-linear: lane l of a wave instruction fills bytes 16 l .. of 1 KB = 8 rows).  Eight of the
-// twelve ds_write_b128 per thread and K tile and 32 staging VGPRs go away; the barriers are raw (s_waitcnt + s_barrier) so that the
-// copies stay in flight across the one that publishes the A tile.
+// (The B tile by LDS-DMA on this tile measured within 1.3 % -- ffn.0 269.5 -> 266.1 us, qkv 218.6 -> 216.3 -- and was not adopted: profiles/r03_ab_notes.md.)
 typedef __attribute__((address_space(3))) void* gemm_lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gemm_gptr_t;
 // ROPE (the qkv projection on the k-permuted throughput tile): LightGlue's rotary encoding of the q | k column tiles in the epilogue, so that the attention
@@ -59,29 +54,22 @@ typedef const __attribute__((address_space(1))) void* gemm_gptr_t;
 // workgroups per CU (tools/kbench/lds_occupancy.hip).  Forms that read the table from global memory in the epilogue measured 216 -> 288 us (row by row
 // between the stores: every load waits for the stores in front of it on the in-order vector-memory counter) and 216 -> 239 us (16 loads at a time in
 // front of all stores; the same whether the q | k or only the k tiles rotate: exposed round trips, not work) -- profiles/r05_ab_notes.md.
-template <int MB, int NB, bool RES, bool PFT = false, bool LNA = false, bool KP = false, bool DMAB = false, bool ROPE = false>
+template <int MB, int NB, bool RES, bool LNA = false, bool KP = false, bool ROPE = false>
 __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
     constexpr int BM = MB * 64, BN = NB * 64;
     constexpr int LDR = KP ? BK : LDT;          // LDS row stride in words
-    static_assert(!DMAB || (KP && PFT && !LNA && MB == 2), "DMAB: k-permuted throughput tile only");
-    static_assert(!ROPE || (KP && PFT && !LNA && !RES && !DMAB && MB == 2 && NB == 4), "ROPE: plain k-permuted 128 x 256 tile only");
-    __shared__ __attribute__((aligned(16))) float lds_static[DMAB ? 4 : (BM + BN) * LDR];   // A tile | B tile
-    extern __shared__ __attribute__((aligned(16))) float lds_dynamic[];                      // DMAB: A tile | B tile x 2 = (BM + 2 BN) * LDR words
-    float* const lds_ab = DMAB ? lds_dynamic : lds_static;
-    float* const As = lds_ab;
-    float* const Bs = lds_ab + BM * LDR;
+    static_assert(!KP || (!LNA && MB == 2), "KP: 128-row tiles without the fused LayerNorm only");
+    static_assert(!ROPE || (KP && !RES && NB == 4), "ROPE: plain k-permuted 128 x 256 tile only");
+    __shared__ __attribute__((aligned(16))) float lds_static[(BM + BN) * LDR];   // A tile | B tile
+    extern __shared__ __attribute__((aligned(16))) float lds_dynamic[];          // ROPE: the rotary table rows of the tile
+    float* const As = lds_static;
+    float* const Bs = lds_static + BM * LDR;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, h = lane >> 5;
     const int z = blockIdx.z;
-    int bxt = blockIdx.x, byt = blockIdx.y;      // column tile, row panel
-    if (g.xcd) {   // launch order is x fastest: linear id L -> XCD L & 7; the nct column tiles of row panel ((slot / nct) * 8 + xcd) sit in consecutive slots of that XCD
-        const int L = blockIdx.y * gridDim.x + blockIdx.x, nct = gridDim.x;
-        const int slot = L >> 3;
-        byt = (slot / nct) * 8 + (L & 7);
-        bxt = slot % nct;
-    }
+    const int bxt = blockIdx.x, byt = blockIdx.y;      // column tile, row panel
     const int m0 = byt * BM, n0 = bxt * BN;
     int M = g.M;
     if (g.m_valid) { M = g.m_valid[z]; if (M > g.M) M = g.M; }
@@ -152,11 +140,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
     const float* const bp = KP ? Bs + (wn * NB * 32 + i) * LDR : Bs + (wn * NB * 32 + i) * LDR + h;
 
     // Small (64-row) tiles serve latency-bound problems (one pair: M = 2048, one workgroup per CU), where every K step
-    // would otherwise expose a full global-memory round trip: there the next tile's loads are issued before the MFMA
-    // loop of the current one (16 VGPRs).  The throughput tiles rely on the other resident workgroups instead
-    // (register prefetch measured slower there).
-    constexpr bool PF = (MB == 1) || PFT;
-    constexpr bool LNI = LNA && PF && MB == 2;   // LN + GELU of the PREFETCHED tile interleaved with the second half of the MFMA loop
+    // would otherwise expose a full global-memory round trip: the next tile's loads are issued before the MFMA
+    // loop of the current one (16 VGPRs).  The 128-row throughput tiles do the same (+1 %, profiles/r02_ab_notes.md).
+    constexpr bool LNI = LNA && MB == 2;   // LN + GELU of the PREFETCHED tile interleaved with the second half of the MFMA loop
     float4 ra[A_IT], rb[B_IT], rg, rbeta;
     auto load_tile = [&](int k0) {
         if (LNA) { rg = *reinterpret_cast<const float4*>(g.ln_g + k0 + lkq * 4); rbeta = *reinterpret_cast<const float4*>(g.ln_b + k0 + lkq * 4); }
@@ -169,22 +155,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
             for (int it = 0; it < A_IT; ++it) ra[it] = *reinterpret_cast<const float4*>(base + aoff[it]);
         }
-        if (DMAB) return;   // the B tile goes through dma_b
         const float* base = Bt + k0;
 #pragma unroll
         for (int it = 0; it < B_IT; ++it) rb[it] = *reinterpret_cast<const float4*>(base + boff[it]);
-    };
-    // one wave instruction copies 64 x 16 B = 1 KB = 8 rows of 128 B; wave w issues the row groups (BN / 32) w .. of the tile.  Lane l fills
-    // row 8 grp + l / 8, physical slot l & 7, which holds logical slot (l & 7) ^ (row & 7) = (l & 7) ^ (l >> 3)
-    auto dma_b = [&](int k0, int buf) {
-        constexpr int GPW = BN / 32;   // row groups per wave
-#pragma unroll
-        for (int u = 0; u < GPW; ++u) {
-            const int grp = wave * GPW + u;
-            int row = grp * 8 + (lane >> 3); row = row < nlast ? row : nlast;
-            const float* src = Bt + (size_t)row * g.ldb + k0 + 4 * ((lane & 7) ^ (lane >> 3));
-            __builtin_amdgcn_global_load_lds((gemm_gptr_t)src, (gemm_lds_ptr_t)(Bs + buf * (BN * LDR) + grp * 256), 16, 0, 0);
-        }
     };
     // LN + GELU of one staged element, same operation order as the stand-alone kernel: ((a - mean) * rstd) * g + b, then GELU
     auto ln_elem = [&](float a, int it, float gq, float bq) { return gelu_short((a - ln_mean[it]) * ln_rstd[it] * gq + bq); };
@@ -194,13 +167,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
             ra[it] = make_float4(ln_elem(ra[it].x, it, rg.x, rbeta.x), ln_elem(ra[it].y, it, rg.y, rbeta.y),
                                  ln_elem(ra[it].z, it, rg.z, rbeta.z), ln_elem(ra[it].w, it, rg.w, rbeta.w));
     };
-#ifdef RFE_TUNING
-    const int abl = g.abl;
-#else
-    constexpr int abl = 0;
-#endif
-    if (DMAB) dma_b(0, 0);
-    if (PF) load_tile(0);
+    load_tile(0);
     if (rope) {   // behind the first tile's loads on the in-order counter: the wait for that tile does not cover these copies
         // one wave instruction = 64 x 16 B = 4 table rows; wave w copies rows 32 w .. 32 w + 31 of the tile (rows past M: the last row, never stored)
 #pragma unroll
@@ -211,23 +178,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
         }
     }
     if (LNI) ln_tile();   // first tile: nothing to hide it under
-    int bbuf = 0;
     for (int k0 = 0; k0 < g.K; k0 += BK) {
-        if (!PF) load_tile(k0);
-        if (DMAB) {
-            // #1: this tile's B copy and A rows have landed (requested one tile ago); every wave has finished the previous tile
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-            for (int it = 0; it < A_IT; ++it)
-                *reinterpret_cast<f32x4*>(da + it * 32 * LDR) = f32x4{ra[it].x, ra[it].y, ra[it].z, ra[it].w};
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // #2: the A tile is visible
-            // next tile, in flight under this tile's MFMAs.  Unconditional (the last tile re-requests itself into the idle buffer) and fenced:
-            // behind a branch the compiler merges the loaded registers with copies and waits for the loads on the spot, without the fence
-            // the scheduler sinks them below the MFMAs (profiles/r03_ab_notes.md)
-            { const int kn = k0 + BK < g.K ? k0 + BK : k0; dma_b(kn, bbuf ^ 1); load_tile(kn); }
-            __builtin_amdgcn_sched_barrier(0);
-        } else
-        if (!(abl & 2) || k0 == 0) {
         __syncthreads();   // previous tile fully consumed
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
@@ -253,8 +204,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
             else { d[0] = rb[it].x; d[1] = rb[it].y; d[2] = rb[it].z; d[3] = rb[it].w; }
         }
         __syncthreads();
-        }
-        if (!DMAB && PF && k0 + BK < g.K && !(abl & 1)) load_tile(k0 + BK);
+        if (k0 + BK < g.K) load_tile(k0 + BK);
         // LNI: the tile prefetched before this loop has landed by now (>= 64 MFMAs = 4096 cycles after its loads were issued):
         // its LayerNorm + GELU -- VALU work, 2 of the 16 elements of this thread per k-step -- runs in the shadow of the
         // MFMAs of the remaining k-steps instead of on the staging path in front of the barrier
@@ -274,14 +224,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
             // fragment back into its own registers as soon as its last MFMA of this group has been issued (+8 VGPRs, no LDS
             // round trip exposed at the group boundaries)
             const int iswz = i & 7;
-            const float* const bpt = DMAB ? bp + bbuf * (BN * LDR) : bp;   // this tile's B buffer
             f32x4 a4[MB], b4[NB];
             {
                 const int slot = ((h << 2) ^ iswz) << 2;
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) a4[mb] = *reinterpret_cast<const f32x4*>(ap + mb * 32 * LDR + slot);
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) b4[nb] = *reinterpret_cast<const f32x4*>(bpt + nb * 32 * LDR + slot);
+                for (int nb = 0; nb < NB; ++nb) b4[nb] = *reinterpret_cast<const f32x4*>(bp + nb * 32 * LDR + slot);
             }
 #pragma unroll
             for (int gq4 = 0; gq4 < 4; ++gq4) {
@@ -299,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
                         for (int mb = 0; mb < MB; ++mb)
                             acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[mb][cq], b4[nb][cq], acc[mb][nb], 0, 0, 0);
-                    if (gq4 < 3) { b4[nb] = *reinterpret_cast<const f32x4*>(bpt + nb * 32 * LDR + nslot); __builtin_amdgcn_sched_barrier(0); }
+                    if (gq4 < 3) { b4[nb] = *reinterpret_cast<const f32x4*>(bp + nb * 32 * LDR + nslot); __builtin_amdgcn_sched_barrier(0); }
                     RFE_LN_SHADOW(gq4 * 4 + nb)
                 }
                 if (gq4 < 3) {
@@ -323,7 +272,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
             }
         }
 #undef RFE_LN_SHADOW
-        if (DMAB) bbuf ^= 1;
     }
 
     {   // bias (+alpha, +ReLU, +residual) epilogue: 128-B coalesced accesses straight from the D layout
@@ -374,7 +322,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
                 for (int rr = 0; rr < 4; ++rr) {
                     const int r = rq * 4 + rr;
                     const int m = m0 + (wm * MB + mb) * 32 + rr + 8 * rq + 4 * h;
-                    if (m >= M || ((abl & 4) && m != 0)) continue;
+                    if (m >= M) continue;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
                         const int n = n0 + (wn * NB + nb) * 32 + i;
@@ -448,18 +396,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 
 // the shapes whose projection can carry the rotary epilogue: what takes the plain k-permuted 128 x 256 tile below
 bool gemm_nt_rope_ok(const GemmArgs& g) {
-    static const bool kp_on = tune_int("RFE_GEMM_KP", 1) != 0, pft = tune_int("RFE_GEMM_PF", 1) != 0, dmab = tune_int("RFE_GEMM_DMA", 0) != 0;
     const int batch = g.batch > 0 ? g.batch : 1;
-    return kp_on && pft && !dmab && g.kperm && batch == 1 && !g.m_valid && !g.R && !g.stats_in && !g.stats_out && !g.Bh && !g.relu && g.alpha == 1.0f && g.N % 256 == 0 &&
+    return g.kperm && batch == 1 && !g.m_valid && !g.R && !g.stats_in && !g.stats_out && !g.Bh && !g.relu && g.alpha == 1.0f && g.N % 256 == 0 &&
            g.rope_c0 % 256 == 0 && g.rope_c1 % 256 == 0 && (long long)((g.M + 127) / 128) * (g.N / 256) >= 256 && !gemm_latency_regime(g);
 }
 
 int launch_gemm_nt(hipStream_t s, const GemmArgs& g_in) {
     GemmArgs g = g_in;
-    g.xcd = 0;
-#ifdef RFE_TUNING
-    g.abl = tune_int("RFE_DBG_GEMM_ABL", 0);
-#endif
     const int batch = g.batch > 0 ? g.batch : 1;
     auto tiles = [&](int bm, int bn) { return (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * batch; };
     // RFE_OPT_LG_FP16X2: a LightGlue Linear whose weights come with fp16 (hi, lo) planes and whose shape takes the throughput tile
@@ -470,40 +413,21 @@ int launch_gemm_nt(hipStream_t s, const GemmArgs& g_in) {
         if (launch_gemm_lat(s, g, nullptr, 0)) return 0;
     }
     const bool res = g.R != nullptr, lna = g.stats_in != nullptr;
-#ifdef RFE_TUNING
-    static const bool ws_on = tune_int("RFE_GEMM_WS", 0) != 0;   // round 6, measured and not adopted: LayerNorm + GELU of the consumer on producer waves (gemm_ws.hip)
-    if (lna && ws_on && res && launch_gemm_ln_ws(s, g)) return 0;
-#endif
-    static const bool lni = tune_int("RFE_LN_INTERLEAVE", 1) != 0;   // tuning switch
-
-    static const bool kp_on = tune_int("RFE_GEMM_KP", 1) != 0;   // tuning switch: 0 = padded layout / k-ascending order everywhere
-    const bool kp = kp_on && g.kperm != 0;
-    static const bool pft = tune_int("RFE_GEMM_PF", 1) != 0;   // register prefetch of the next K tile also on the 128-row tiles (+1 % on ffn1 / ffn2, profiles/r02_ab_notes.md); RFE_GEMM_PF=0 (tuning build) disables
-    static const bool dmab = tune_int("RFE_GEMM_DMA", 0) != 0;   // tuning switch, OFF in the product: B tile by LDS-DMA on the k-permuted throughput tile (ffn.0 269.5 -> 266.1 us, qkv 218.6 -> 216.3, cross-qkv unchanged: within 1.3 %, not worth a second code path under the headline -- profiles/r03_ab_notes.md)
-    constexpr int kDmaLds = (128 + 2 * 256) * 32 * 4;            // 80 KB
+    const bool kp = g.kperm != 0 && !lna;   // the k-permuted layout serves the 128-row tiles without the fused LayerNorm
+    // 128-row tiles: rotary epilogue (qkv) > k-permuted (LightGlue) > LN + GELU on A under the MFMAs (ffn.3) > padded, k ascending (SuperPoint's 1x1 heads);
+    // 64-row tiles: LN + GELU on A at staging, or plain.  (The macro is expanded for both tile heights: in the k-permuted branch the KP argument is
+    // written `MB_ == 2` so that the 64-row expansions, which never take that branch, name the padded kernel they launch anyway instead of a KP one.)
 #define RFE_GEMM_GO(MB_, NB_, GRID)                                                                  \
     do {                                                                                             \
-        if (kp && MB_ == 2 && NB_ == 4 && pft && !lna && dmab && batch == 1 && !g.m_valid) {         \
-            if (res) {                                                                               \
-                static bool ls_[64]; ensure_dynamic_lds((const void*)gemm_nt_kernel<2, 4, true, true, false, true, true>, kDmaLds, ls_); \
-                hipLaunchKernelGGL((gemm_nt_kernel<2, 4, true, true, false, true, true>), GRID, dim3(256), kDmaLds, s, g); \
-            } else {                                                                                 \
-                static bool ls_[64]; ensure_dynamic_lds((const void*)gemm_nt_kernel<2, 4, false, true, false, true, true>, kDmaLds, ls_); \
-                hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, true, false, true, true>), GRID, dim3(256), kDmaLds, s, g); \
-            }                                                                                        \
-        } else                                                                                       \
         if (g.rope_csn && MB_ == 2 && NB_ == 4) {                                                    \
-            static bool lr_[64]; ensure_dynamic_lds((const void*)gemm_nt_kernel<2, 4, false, true, false, true, false, true>, 128 * 64 * 4, lr_); \
-            hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, true, false, true, false, true>), GRID, dim3(256), 128 * 64 * 4, s, g); \
+            static bool lr_[64]; ensure_dynamic_lds((const void*)gemm_nt_kernel<2, 4, false, false, true, true>, 128 * 64 * 4, lr_); \
+            hipLaunchKernelGGL((gemm_nt_kernel<2, 4, false, false, true, true>), GRID, dim3(256), 128 * 64 * 4, s, g); \
         } else                                                                                       \
-        if (kp && MB_ == 2 && pft && !lna) {                                                         \
-            if (res) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, MB_ == 2, false, MB_ == 2>), GRID, dim3(256), 0, s, g); \
-            else hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, false, MB_ == 2, false, MB_ == 2>), GRID, dim3(256), 0, s, g);         \
+        if (kp && MB_ == 2) {                                                                        \
+            if (res) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, false, MB_ == 2>), GRID, dim3(256), 0, s, g); \
+            else hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, false, false, MB_ == 2>), GRID, dim3(256), 0, s, g);    \
         } else                                                                                       \
-        if (lna && lni && MB_ == 2) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, MB_ == 2, true>), GRID, dim3(256), 0, s, g);   /* LN + GELU on A under the MFMAs */ \
-        else if (lna) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, false, true>), GRID, dim3(256), 0, s, g);   /* LN + GELU on A at staging */ \
-        else if (pft && MB_ == 2 && res) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, MB_ == 2>), GRID, dim3(256), 0, s, g);    \
-        else if (pft && MB_ == 2) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, false, MB_ == 2>), GRID, dim3(256), 0, s, g);     \
+        if (lna) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true, true>), GRID, dim3(256), 0, s, g);   \
         else if (res) hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, true>), GRID, dim3(256), 0, s, g);    \
         else hipLaunchKernelGGL((gemm_nt_kernel<MB_, NB_, false>), GRID, dim3(256), 0, s, g);        \
     } while (0)
@@ -514,13 +438,9 @@ int launch_gemm_nt(hipStream_t s, const GemmArgs& g_in) {
     const bool big = (g.N % 256 == 0 && tiles(128, 256) >= 256) || tiles(128, 128) >= 256 || g.M > 8192;
     if (!big || g.N % 256) g.stats_out = nullptr;   // partials cover whole column tiles only
     int ntiles;
-    // XCD-aware tile decode (round 6; tuning build only, OFF in the product): only where it is a bijection and there is something to share -- several column tiles, a
-    // whole number of 8 row panels, one batch.  Measured (tools/tune_sweep.py, three alternating runs, profiles/r06_ab_notes.md): qkv 1.991 -> 1.963 ms per step,
-    // cross-qkv 1.333 -> 1.329, ffn.0 4.902 -> 4.918, and ffn.3 -- whose own decode does not change -- 3.113 -> 3.191: the step does not move (34.15 - 34.21 against
-    // 34.11 - 34.18 ms).  The panels are not HBM-bound (440 MB in 224 us), so saving the A re-reads buys nothing.
-    static const bool xcd_on = tune_int("RFE_GEMM_XCD", 0) != 0;
-    auto xcd_ok = [&](int bm, int bn) { const int nct = (g.N + bn - 1) / bn, gy = (g.M + bm - 1) / bm; return xcd_on && batch == 1 && nct > 1 && gy % 8 == 0 && !g.m_valid; };
-    if (g.N % 256 == 0 && tiles(128, 256) >= 256) { ntiles = g.N / 256; g.xcd = xcd_ok(128, 256) ? 1 : 0; RFE_GEMM_GO(2, 4, dim3(g.N / 256, (g.M + 127) / 128, batch)); }
+    // (An XCD-aware tile decode -- the column tiles of one row panel on one XCD -- measured no change of the step, 34.15 - 34.21 against 34.11 - 34.18 ms: the
+    // panels are not HBM-bound, so saving the A re-reads buys nothing.  profiles/r06_ab_notes.md.)
+    if (g.N % 256 == 0 && tiles(128, 256) >= 256) { ntiles = g.N / 256; RFE_GEMM_GO(2, 4, dim3(g.N / 256, (g.M + 127) / 128, batch)); }
     else if (tiles(128, 128) >= 256 || g.M > 8192) { ntiles = (g.N + 127) / 128; RFE_GEMM_GO(2, 2, dim3((g.N + 127) / 128, (g.M + 127) / 128, batch)); }
     else if (tiles(64, 128) >= 256) { ntiles = (g.N + 127) / 128; RFE_GEMM_GO(1, 2, dim3((g.N + 127) / 128, (g.M + 63) / 64, batch)); }
     else { ntiles = (g.N + 63) / 64; RFE_GEMM_GO(1, 1, dim3((g.N + 63) / 64, (g.M + 63) / 64, batch)); }

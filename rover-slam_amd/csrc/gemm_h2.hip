@@ -46,22 +46,20 @@ __device__ __forceinline__ float gelu_short_h2(float t) {   // = gemm.hip:gelu_s
     return 0.5f * t * (1.0f + copysignf(er, x));
 }
 
-// DMA: the weight planes never touch a register -- they are copied by global_load_lds_dwordx4 into a DOUBLE-buffered LDS tile (2 x 32 KB;
+// The weight planes never touch a register -- they are copied by global_load_lds_dwordx4 into a DOUBLE-buffered LDS tile (2 x 32 KB;
 // with the 16 KB A tile = 80 KB per workgroup: exactly two workgroups per CU, tools/kbench/lds_occupancy.hip), tile t + 1 requested
 // right after tile t is published, together with the A rows of tile t + 1 (16 registers); the 16-byte-slot swizzle is applied on the
 // SOURCE address (the LDS side of the copy is lane-linear: lane l of a wave instruction fills bytes 16 l .. of 1 KB = 16 rows).
-// Without it (register staging of all twelve loads of a tile at its top) both workgroups of a CU end up waiting for L2 / HBM together.
+// Without it (register staging of all twelve loads of a tile at its top; measured and removed) both workgroups of a CU end up waiting for L2 / HBM together.
 typedef __attribute__((address_space(3))) void* h2_lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* h2_gptr_t;
-template <bool RES, bool LNA, bool DMA, int ABL = 0>   // ABL: timing ablations of the DMA variant (tuning build only, wrong results): 1 A staged once, 2 no barriers, 4 weights copied once, 8 no epilogue stores
+template <bool RES, bool LNA>
 __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
     constexpr int BM = 128, BN = 256, BK = 32, MB = 2, NB = 4;
     constexpr int BPL = BN * 64;                      // bytes of one B plane of one K tile
-    __shared__ __attribute__((aligned(16))) unsigned char lds_static[DMA ? 16 : 2 * (BM + BN) * 64];
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];   // DMA: 2 * BM * 64 + 2 * 2 * BPL = 80 KB
-    unsigned char* const lds = DMA ? lds_dyn : lds_static;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // 2 * BM * 64 + 2 * 2 * BPL = 80 KB
     unsigned char* const As = lds;                    // [2 planes][BM][64 B]
-    unsigned char* const Bs = lds + 2 * BM * 64;      // [2 planes][BN][64 B] (DMA: x 2 buffers)
+    unsigned char* const Bs = lds + 2 * BM * 64;      // [2 planes][BN][64 B] x 2 buffers
     const int tid = threadIdx.x, lane = tid & 63;
     // Activations are split while they are staged (h2_split2): with the default mode one |a| >= 65520 becomes inf and lo = inf - inf = NaN for
     // its whole output row.  MODE.FP16_OVFL saturates instead (h2_split.h) -- set for the variants without the fused LayerNorm + GELU, where it
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
     }
 
     // A staging: thread -> (row = tid / 8 + 32 it, 4 consecutive k); rows past the M edge are clamped (their products land in
-    // accumulators that are never stored).  B staging: thread -> (row = tid / 4 + 64 p, one 16-byte slot = 8 k) of each plane.
+    // accumulators that are never stored).
     const int lrow = tid >> 3, lkq = tid & 7;
     int mlast = M - 1 - m0; mlast = mlast < BM - 1 ? mlast : BM - 1;
     const float* const At = g.A + (size_t)m0 * g.lda;
@@ -104,10 +102,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
         a2off[it] = rc * g.lda2 + lkq * 4;
         adst[it] = row * 64 + (((lkq >> 1) ^ ((row >> 2) & 3)) << 4) + ((lkq & 1) << 3);   // 4 k = half a 16-byte slot
     }
-    const int srow = tid >> 2, sslot = tid & 3;
-    const int sw_off = srow * 64 + ((sslot ^ ((srow >> 2) & 3)) << 4);   // rows srow + 64 p: same (row >> 2) & 3
-    const uint16_t* const Bh = g.Bh + (size_t)(n0 + srow) * g.ldb + sslot * 8;
-    const uint16_t* const Bl = g.Bl + (size_t)(n0 + srow) * g.ldb + sslot * 8;
     const int frag_sw = (i >> 2) & 3;
 
     float ln_mean[4], ln_rstd[4];
@@ -126,10 +120,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
         }
     }
 
-    // LNA (ffn.3): the A rows of K tile t + 1 are requested right after tile t is published and land under its MFMAs -- the LayerNorm /
-    // GELU / split pass then starts on data that is already there (89.5 -> 74.5 us).  The plain variants keep all twelve loads at the top
-    // of the tile they belong to: with the prefetch they measured 3 % slower (ffn.0, cross-qkv), and with the weight planes prefetched as
-    // well (48 more live registers) everything spills -- profiles/r03_ab_notes.md.
+    // The A rows of K tile t + 1 are requested right after tile t is published and land under its MFMAs (the register-staged forms this replaced:
+    // profiles/r03_ab_notes.md).
     float4 fa[4];
     auto fetchA = [&](int k0) {
         if (A2t && k0 >= g.K1) {
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
             for (int it = 0; it < 4; ++it) fa[it] = *reinterpret_cast<const float4*>(base + aoff[it]);
         }
     };
-    // DMA: one wave instruction copies 64 x 16 B = 1 KB = 16 rows of one plane; wave w issues the row groups 4 w .. 4 w + 3 of both planes.
+    // One wave instruction copies 64 x 16 B = 1 KB = 16 rows of one plane; wave w issues the row groups 4 w .. 4 w + 3 of both planes.
     // Lane l fills row 16 grp + l / 4, physical slot l & 3, which holds logical slot (l & 3) ^ ((row >> 2) & 3) = (l & 3) ^ (l >> 4).
     auto dmaB = [&](int k0, int b) {
 #pragma unroll
@@ -173,42 +165,19 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
             *reinterpret_cast<u32x2*>(As + BM * 64 + adst[it]) = u32x2{l0, l1};
         }
     };
-    if (DMA) { dmaB(0, 0); fetchA(0); }
-    else if (LNA) fetchA(0);
+    dmaB(0, 0); fetchA(0);
     int bbuf = 0;
     for (int k0 = 0; k0 < g.K; k0 += BK) {
-        const unsigned char* Bt = Bs;                 // this tile's B planes
-        if (DMA) {
-            // #1: this tile's weight planes and A rows have landed (requested one tile ago); every wave has finished the previous tile
-            if (ABL & 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); else
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            if (!(ABL & 1) || k0 == 0) stageA(k0);
-            if (ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // #2: the A planes are visible
-            // in flight under this tile's MFMAs.  UNCONDITIONAL (the last tile re-requests itself into the idle buffer): behind a branch
-            // the compiler merges the loaded registers with copies and waits for the loads right here
-            { const int kn = k0 + BK < g.K ? k0 + BK : k0; if (!(ABL & 4)) dmaB(kn, bbuf ^ 1); if (!(ABL & 1)) fetchA(kn); }
-            __builtin_amdgcn_sched_barrier(0);   // ... and without this fence the scheduler sinks the A loads below the MFMAs, next to the barrier that waits for them
-            Bt = Bs + bbuf * (2 * BPL);
-            bbuf ^= 1;
-        } else {
-            if (!LNA) fetchA(k0);
-            u32x4 rh[4], rl[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                rh[p] = *reinterpret_cast<const u32x4*>(Bh + (size_t)64 * p * g.ldb + k0);
-                rl[p] = *reinterpret_cast<const u32x4*>(Bl + (size_t)64 * p * g.ldb + k0);
-            }
-            __syncthreads();   // previous tile consumed
-            stageA(k0);
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                *reinterpret_cast<u32x4*>(Bs + p * 64 * 64 + sw_off) = rh[p];
-                *reinterpret_cast<u32x4*>(Bs + BN * 64 + p * 64 * 64 + sw_off) = rl[p];
-            }
-            __syncthreads();
-            if (LNA) { fetchA(k0 + BK < g.K ? k0 + BK : k0); __builtin_amdgcn_sched_barrier(0); }   // unconditional, fenced: see the DMA branch
-        }
+        // #1: this tile's weight planes and A rows have landed (requested one tile ago); every wave has finished the previous tile
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        stageA(k0);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // #2: the A planes are visible
+        // in flight under this tile's MFMAs.  UNCONDITIONAL (the last tile re-requests itself into the idle buffer): behind a branch
+        // the compiler merges the loaded registers with copies and waits for the loads right here
+        { const int kn = k0 + BK < g.K ? k0 + BK : k0; dmaB(kn, bbuf ^ 1); fetchA(kn); }
+        __builtin_amdgcn_sched_barrier(0);   // ... and without this fence the scheduler sinks the A loads below the MFMAs, next to the barrier that waits for them
+        const unsigned char* const Bt = Bs + bbuf * (2 * BPL);   // this tile's B planes
+        bbuf ^= 1;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int slot = ((2 * c + h) ^ frag_sw) << 4;
@@ -232,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
         }
     }
 
-    if (!(ABL & 8)) {   // alpha (+residual) epilogue: 128-B coalesced accesses straight from the D layout (gemm.hip)
+    {   // alpha (+residual) epilogue: 128-B coalesced accesses straight from the D layout (gemm.hip)
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -310,27 +279,13 @@ int launch_gemm_h2(hipStream_t s, const GemmArgs& g) {
     const int panels8 = (((g.M + 127) / 128) + 7) / 8 * 8;   // row panels padded to a multiple of 8: the block -> (panel, column tile) decode stays bijective
     const dim3 grid((unsigned)(panels8 * (g.N / 256)));
     const bool res = g.R != nullptr, lna = g.stats_in != nullptr;
-    static const bool dma = tune_int("RFE_H2_DMA", 1) != 0;   // tuning switch: 0 = weight planes staged through registers
     constexpr int kDmaLds = 2 * 128 * 64 + 2 * 2 * 256 * 64;   // 80 KB
 #define RFE_H2_LAUNCH(RES_, LNA_)                                                                                                     \
     do {                                                                                                                              \
-        if (dma) {                                                                                                                    \
-            static bool lds_set[64];                                                                                                  \
-            ensure_dynamic_lds((const void*)gemm_h2_kernel<RES_, LNA_, true>, kDmaLds, lds_set);                                      \
-            hipLaunchKernelGGL((gemm_h2_kernel<RES_, LNA_, true>), grid, dim3(256), kDmaLds, s, g);                                   \
-        } else {                                                                                                                      \
-            hipLaunchKernelGGL((gemm_h2_kernel<RES_, LNA_, false>), grid, dim3(256), 0, s, g);                                        \
-        }                                                                                                                             \
+        static bool lds_set[64];                                                                                                      \
+        ensure_dynamic_lds((const void*)gemm_h2_kernel<RES_, LNA_>, kDmaLds, lds_set);                                                \
+        hipLaunchKernelGGL((gemm_h2_kernel<RES_, LNA_>), grid, dim3(256), kDmaLds, s, g);                                             \
     } while (0)
-#ifdef RFE_TUNING
-    if (!lna && !res) switch (tune_int("RFE_DBG_H2_ABL", 0)) {
-#define RFE_H2_ABL(n) case n: { static bool ls_[64]; ensure_dynamic_lds((const void*)gemm_h2_kernel<false, false, true, n>, kDmaLds, ls_); \
-                                hipLaunchKernelGGL((gemm_h2_kernel<false, false, true, n>), grid, dim3(256), kDmaLds, s, g); return 0; }
-        RFE_H2_ABL(1) RFE_H2_ABL(2) RFE_H2_ABL(3) RFE_H2_ABL(4) RFE_H2_ABL(7) RFE_H2_ABL(8) RFE_H2_ABL(15)
-#undef RFE_H2_ABL
-        default: break;
-    }
-#endif
     if (lna && res) RFE_H2_LAUNCH(true, true);
     else if (lna) RFE_H2_LAUNCH(false, true);
     else if (res) RFE_H2_LAUNCH(true, false);

@@ -40,15 +40,6 @@ typedef const __attribute__((address_space(1))) void* glat_gptr_t;
 
 constexpr int LBK = 64;       // k per stage: LDS rows of 256 B
 
-#ifdef RFE_TUNING
-// in-kernel timeline (tuning build, abl & 4): per workgroup, wave 0 lane 0 records (shader clock, 100 MHz wall clock) at entry, after the
-// first stage has landed, after the K loop and at exit; read back with rfe_k_dbg_timeline
-__device__ unsigned long long rfe_dbg_ts[2048 * 8];
-#define RFE_TS(slot) do { if ((abl & 4) && tid == 0 && blockIdx.x < 2048) { rfe_dbg_ts[blockIdx.x * 8 + (slot)] = clock64(); rfe_dbg_ts[blockIdx.x * 8 + 4 + (slot)] = wall_clock64(); } } while (0)
-#else
-#define RFE_TS(slot) do { } while (0)
-#endif
-
 // WI x WJ: 16-column (n) x 16-row (m) blocks per wave; WGN x WGM: waves per workgroup along n and m (WGN * WGM == 4).
 // LSTAGES: depth of the LDS ring (LSTAGES - 1 stages in flight under the matrix instructions of one).
 // H2 (RFE_OPT_LG_FP16X2, default off): the same tile, ring, block decode and epilogue with every product as a SPLIT product on the f16 matrix
@@ -57,7 +48,7 @@ __device__ unsigned long long rfe_dbg_ts[2048 * 8];
 // stay fp32 and are split as they are read from LDS; one v_mfma_f32_16x16x32_f16 consumes 32 k (lane group q holds k = 8 q .. 8 q + 7 of
 // both operands), three of them replace eight v_mfma_f32_16x16x4_f32.
 template <int WI, int WJ, int WGN, int WGM, int LSTAGES, bool RES, bool ROPE, bool H2 = false>
-__global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g, const float* __restrict__ rope_csn, int rope_cols, int MT, int abl) {
+__global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g, const float* __restrict__ rope_csn, int rope_cols, int MT) {
     constexpr int NW = WGN * WGM;                         // waves per workgroup: 4 (one per SIMD) or 8 (two per SIMD)
     static_assert(NW == 4 || NW == 8, "four or eight waves per workgroup");
     constexpr int BN = 16 * WI * WGN, BM = 16 * WJ * WGM, ROWS = BN + BM, STAGE_F = ROWS * LBK;
@@ -67,7 +58,6 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
     extern __shared__ __attribute__((aligned(16))) float lds[];   // LSTAGES stages of (BN + BM) x 64 floats
 
     const int tid = threadIdx.x, lane = tid & 63;
-    RFE_TS(0);
     if (H2) h2_saturate_mode();                           // an activation past fp16's range saturates instead of turning its row into NaN (h2_split.h)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
@@ -139,20 +129,15 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
         const int st = t % LSTAGES;
         // stage t has landed (this wave's copies: counted wait -- the stages t + 1 .. still in flight are younger; everybody's: barrier),
         // and every wave has left stage t - 1, whose buffer the next request reuses
-#if defined(RFE_EXP) && (RFE_EXP & 2)   // compile-time ablations of the floor measurement (tools/kbench/build_exp.sh, wrong results): 2 = no waits / barriers after the first stage
-        if (t == 0)
-#endif
         {
             int younger = T - 1 - t; younger = younger < LSTAGES - 2 ? younger : LSTAGES - 2;
-            if (abl & 1) younger = 0;
             if (younger >= 4) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(4 * NDMA) : "memory");
             else if (younger == 3) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(3 * NDMA) : "memory");
             else if (younger == 2) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * NDMA) : "memory");
             else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NDMA) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         }
-        if (t == 0) RFE_TS(1);
-        if (t + LSTAGES - 1 < T && !(abl & 1)) issue(t + LSTAGES - 1, (t + LSTAGES - 1) % LSTAGES);
+        if (t + LSTAGES - 1 < T) issue(t + LSTAGES - 1, (t + LSTAGES - 1) % LSTAGES);
         const float* const ws = wfrag + st * STAGE_F;
         const float* const as = afrag + st * STAGE_F;
         if constexpr (H2) {
@@ -196,9 +181,6 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
 #pragma unroll
             for (int j = 0; j < WJ; ++j) b[j] = *reinterpret_cast<const f32x4*>(as + j * 16 * LBK + sl);
         };
-#if defined(RFE_EXP) && (RFE_EXP & 1)   // 1 = no LDS fragment reads after the first (operands stay in registers): with 2, the pure-MFMA K loop (38.6 cycles per instruction)
-        if (t == 0)
-#endif
         frags(0, a4, b4);
         // Order inside a k group (pinned with sched_barriers; one wave per SIMD: nobody else covers an exposed LDS round trip):
         //   first matrix instruction of group kg  -- the s_waitcnt for kg's fragments sits in front of it, and they were requested a whole
@@ -210,16 +192,7 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
             f32x4 an[WI], bn[WJ];
             acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[0][0], b4[0][0], acc[0][0], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#if defined(RFE_EXP) && (RFE_EXP & 1)
-            if (kg + 1 < LBK / 16) {
-#pragma unroll
-                for (int i = 0; i < WI; ++i) an[i] = a4[i] + 1e-9f;
-#pragma unroll
-                for (int j = 0; j < WJ; ++j) bn[j] = b4[j] + 1e-9f;
-            }
-#else
             if (kg + 1 < LBK / 16) { frags(kg + 1, an, bn); __builtin_amdgcn_sched_barrier(0); }
-#endif
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -243,7 +216,6 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
             }
     }
 
-    RFE_TS(2);
     // ---- epilogue: one 16-byte access per (block, lane) for rotary table / residual / store
 #pragma unroll
     for (int j = 0; j < WJ; ++j) {
@@ -268,14 +240,7 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
             if (live) *reinterpret_cast<f32x4*>(g.C + (size_t)m * g.ldc + n) = v[i];
         }
     }
-    RFE_TS(3);
 }
-
-#ifdef RFE_TUNING
-extern "C" int rfe_k_dbg_timeline(unsigned long long* host, int n) {   // tuning build only: copy out the first n entries of the timeline
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(rfe_dbg_ts), (size_t)n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 // Shapes served: k-permuted LightGlue Linears (GemmArgs::kperm) without batch / m_valid / fused LayerNorm, K % 64 == 0 (K1 % 64 == 0), at most
 // 8192 rows, N a multiple of 32 -- i.e. the Linears of a one- or few-pair forward.  Returns false when the shape is not one of them (nothing
@@ -287,29 +252,21 @@ bool launch_gemm_lat(hipStream_t s, const GemmArgs& g, const float* rope_csn, in
     const bool h2 = g.Bh && g.Bl && !g.relu && (g.ldb % 8) == 0;   // RFE_OPT_LG_FP16X2: the split form of the same tiles (weight planes from load time)
     if ((g.lda % 4) || (g.ldb % 4) || (g.ldc % 4) || (g.A2 && (g.lda2 % 4)) || (g.R && (g.ldr % 4))) return false;
     const bool res = g.R != nullptr, rope = rope_csn != nullptr;
-#ifdef RFE_TUNING
-    const int abl = tune_int("RFE_GLAT_ABL", 0);         // 1 = only the first LSTAGES - 1 stages are copied (timing ablation, wrong results); 4 = record the timeline
-    const int stages_env = tune_int("RFE_GLAT_STAGES", 0);
-    const int w8 = tune_int("RFE_GLAT_W8", 3);           // bit 0: qkv, bit 1: residual form with EIGHT waves per workgroup (two per SIMD); 0 = four (A/B)
-#else
-    constexpr int abl = 0, stages_env = 0;
-#endif
 #define RFE_GLAT_LAUNCH(WI_, WJ_, WGN_, WGM_, LS_, RES_, ROPE_)                                                                  \
     do {                                                                                                                         \
         constexpr int BN_ = 16 * WI_ * WGN_, BM_ = 16 * WJ_ * WGM_, BYTES_ = LS_ * (BN_ + BM_) * LBK * 4;                        \
         const int MT = (g.M + BM_ - 1) / BM_;                                                                                    \
         auto kern = h2 ? gemm_lat_kernel<WI_, WJ_, WGN_, WGM_, LS_, RES_, ROPE_, true> : gemm_lat_kernel<WI_, WJ_, WGN_, WGM_, LS_, RES_, ROPE_, false>; \
         static bool ls_[2][64]; ensure_dynamic_lds((const void*)kern, BYTES_, ls_[h2 ? 1 : 0]);                                  \
-        hipLaunchKernelGGL(kern, dim3((g.N / BN_) * ((MT + 7) / 8 * 8), batch), dim3(64 * WGN_ * WGM_), BYTES_, s, g, rope_csn, rope_cols, MT, abl); \
+        hipLaunchKernelGGL(kern, dim3((g.N / BN_) * ((MT + 7) / 8 * 8), batch), dim3(64 * WGN_ * WGM_), BYTES_, s, g, rope_csn, rope_cols, MT);  \
         return true;                                                                                                             \
     } while (0)
     // ring depth: as many 64-k stages as the 160 KB of LDS hold, at most 6 (measured: 3 is as fast -- the kernel is bound by the matrix
-    // pipe -- the deeper ring only buys tolerance against a slow first touch of the weights); RFE_GLAT_STAGES=3 in the tuning build
+    // pipe -- the deeper ring only buys tolerance against a slow first touch of the weights)
 #define RFE_GLAT_GO(WI_, WJ_, WGN_, WGM_, RES_, ROPE_)                                                                           \
     do {                                                                                                                         \
         constexpr int ROWS_ = 16 * WI_ * WGN_ + 16 * WJ_ * WGM_;                                                                 \
         constexpr int LSMAX_ = 160 * 1024 / (ROWS_ * LBK * 4) > 6 ? 6 : 160 * 1024 / (ROWS_ * LBK * 4);                          \
-        if (stages_env == 3) RFE_GLAT_LAUNCH(WI_, WJ_, WGN_, WGM_, 3, RES_, ROPE_);                                              \
         RFE_GLAT_LAUNCH(WI_, WJ_, WGN_, WGM_, LSMAX_, RES_, ROPE_);                                                              \
     } while (0)
     // tile: the widest column tile (96 / 64 / 32 columns x 64 rows) that still gives the chip about one workgroup per CU.  The qkv and the
@@ -319,16 +276,10 @@ bool launch_gemm_lat(hipStream_t s, const GemmArgs& g, const float* rope_csn, in
     const long long panels = (long long)batch * ((g.M + 63) / 64);
     if (rope) {   // qkv
         if (g.N % 96 || res || (rope_cols % 64)) return false;
-#ifdef RFE_TUNING
-        if (!(w8 & 1)) RFE_GLAT_GO(3, 2, 2, 2, false, true);
-#endif
         RFE_GLAT_GO(3, 1, 2, 4, false, true);
     }
     if (res) {
         if (g.N % 32) return false;
-#ifdef RFE_TUNING
-        if (!(w8 & 2)) RFE_GLAT_GO(2, 1, 1, 4, true, false);
-#endif
         RFE_GLAT_GO(1, 1, 2, 4, true, false);
     }
     if (g.N % 96 == 0 && panels * (g.N / 96) >= 224) RFE_GLAT_GO(3, 2, 2, 2, false, false);

@@ -6,8 +6,8 @@
 // 32 x 32 x 16 block: 24 matrix instructions of 32 cycles per 32 keys x 32 queries where the fp32 kernel issues 64 of 64 cycles.
 // The reference runs this inside Session::Run(lightglue_sim.onnx), src/Matchers/lightglue_onnx.cpp:210-214.
 //
-// Workgroup = 4 waves = 256 queries of one head, wave = 64 queries (NQB = 2: two 32-query blocks b share every K / V^T fragment read and
-// every staged tile serves twice the queries; the 128-query / 32-query-wave shape of the fp32 kernel -- NQB = 1, one tile buffer, three
+// Workgroup = 4 waves = 256 queries of one head, wave = 64 queries (AH_NQB = 2: two 32-query blocks b share every K / V^T fragment read and
+// every staged tile serves twice the queries; the 128-query / 32-query-wave shape of the fp32 kernel -- AH_NQB = 1, one tile buffer, three
 // workgroups per CU -- measured 7 % slower, profiles/r03_ab_notes.md).  64-key tiles, double-buffered in LDS (64 KB, two
 // workgroups per CU), ONE barrier per tile: tile t+1 is fetched into registers before the products of tile t and written (split into
 // planes) after them.  Per tile and 32-key sub-block:
@@ -73,16 +73,16 @@ __device__ __forceinline__ void ah_softmax_step(f32x16& st, bool first, float& m
     l_run += ps;
 }
 
-// NQB: 32-query blocks per wave (workgroup = 128 NQB queries); DBUF: double-buffered tiles (one barrier per tile) or one buffer (two)
-template <bool ROPE, int ABL = 0, int NQB = 2, bool DBUF = true>   // ABL: timing ablations (tuning build only, wrong results): 1 no softmax VALU, 2 stage only tile 0, 4 no MFMA
-__global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
+constexpr int AH_NQB = 2;   // 32-query blocks per wave (workgroup = 128 AH_NQB queries)
+template <bool ROPE>
+__global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld, float* __restrict__ out,
     int Lq, int Lk, int nqb, const int* __restrict__ qlen, const int* __restrict__ klen, const int* __restrict__ kv_map,
     int nseq_total, const float* __restrict__ rope_csn) {
     // [buffer][K hi, K lo, V^T hi, V^T lo][64 rows x 128 B]
-    constexpr int AH_Q = 128 * NQB;
+    constexpr int AH_Q = 128 * AH_NQB;
     h2_saturate_mode();
-    __shared__ __attribute__((aligned(16))) unsigned char lds[(DBUF ? 2 : 1) * 4 * AH_K * 128];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 4 * AH_K * 128];
     // XCD-aware decode as lg_attention_kernel: the query blocks of one (sequence, head) run on one XCD
     const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
     const int qb = t_ % nqb, unit = (t_ / nqb) * 8 + xcd;
@@ -101,14 +101,14 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
     }
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const bool wactive = qb * AH_Q + wave * (32 * NQB) < nq;   // wave-uniform: a wave whose 64 queries are all padding only stages tiles
+    const bool wactive = qb * AH_Q + wave * (32 * AH_NQB) < nq;   // wave-uniform: a wave whose 64 queries are all padding only stages tiles
     constexpr float kScale = 0.125f * 1.44269504088896341f;  // 1/sqrt(64) * log2(e): softmax in base 2, folded into Q
 
     // ---- Q fragments: lane (j, h) of block b holds Q[query][16 s + 8 h .. + 7], s = 0..3, as (hi, lo) planes
-    f16x8 qh[NQB][4], ql[NQB][4];
+    f16x8 qh[AH_NQB][4], ql[AH_NQB][4];
 #pragma unroll
-    for (int b = 0; b < NQB; ++b) {
-        const int qrow = qb * AH_Q + wave * (32 * NQB) + b * 32 + j;
+    for (int b = 0; b < AH_NQB; ++b) {
+        const int qrow = qb * AH_Q + wave * (32 * AH_NQB) + b * 32 + j;
         const size_t qrow_c = (size_t)seq * Lq + (qrow < Lq ? qrow : Lq - 1);
         const float* qp = q + qrow_c * ld + head * 64 + 8 * h;
 #pragma unroll
@@ -133,16 +133,16 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
         }
     }
 
-    f32x16 o[NQB][2];
+    f32x16 o[AH_NQB][2];
 #pragma unroll
-    for (int b = 0; b < NQB; ++b)
+    for (int b = 0; b < AH_NQB; ++b)
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[b][db][r] = 0.f;
-    float m_run[NQB], l_run[NQB];
+    float m_run[AH_NQB], l_run[AH_NQB];
 #pragma unroll
-    for (int b = 0; b < NQB; ++b) { m_run[b] = -INFINITY; l_run[b] = 0.f; }
+    for (int b = 0; b < AH_NQB; ++b) { m_run[b] = -INFINITY; l_run[b] = 0.f; }
 
     const float* kbase = k + (size_t)kvseq * Lk * ld + head * 64;
     const float* vbase = v + (size_t)kvseq * Lk * ld + head * 64;
@@ -220,11 +220,8 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
     fetch(0);
     int buf = 0;
     for (int k0 = 0; k0 < nk; k0 += AH_K) {
-        if (!DBUF) __syncthreads();             // one buffer: the previous tile has been consumed by every wave
-        if (!(ABL & 2) || k0 == 0) {
-        stash(buf);                             // DBUF: buffer `buf` was last read for tile k0 - 128: every wave has passed the barrier of tile k0 - 64 since
+        stash(buf);                             // buffer `buf` was last read for tile k0 - 128: every wave has passed the barrier of tile k0 - 64 since
         if (k0 + AH_K < nk) fetch(k0 + AH_K);   // in flight under this tile's products
-        }
         __syncthreads();
         if (wactive) {
             const unsigned char* const Kh = lds + buf * (4 * AH_K * 128);
@@ -236,9 +233,9 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
                 if (k0 + sub * 32 >= nk) break;
                 const bool first = k0 == 0 && sub == 0;
                 // ---- S^T[key][query] relative to the running reference maximum, both query blocks
-                f32x16 st[NQB];
+                f32x16 st[AH_NQB];
 #pragma unroll
-                for (int b = 0; b < NQB; ++b) {
+                for (int b = 0; b < AH_NQB; ++b) {
                     const float init = first ? 0.f : -m_run[b];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) st[b][r] = init;
@@ -251,34 +248,24 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
                     const f16x8 kh = *reinterpret_cast<const f16x8*>(Kh + off);
                     const f16x8 kl = *reinterpret_cast<const f16x8*>(Kl + off);
                     // small terms first; the two query blocks alternate so that no instruction waits for its predecessor's accumulator
-                    if (ABL & 4) { st[0][s] += (float)kh[0] + (float)kl[1]; continue; }
 #pragma unroll
-                    for (int b = 0; b < NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[b][s], st[b], 0, 0, 0);
+                    for (int b = 0; b < AH_NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[b][s], st[b], 0, 0, 0);
 #pragma unroll
-                    for (int b = 0; b < NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[b][s], st[b], 0, 0, 0);
+                    for (int b = 0; b < AH_NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[b][s], st[b], 0, 0, 0);
 #pragma unroll
-                    for (int b = 0; b < NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[b][s], st[b], 0, 0, 0);
+                    for (int b = 0; b < AH_NQB; ++b) st[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[b][s], st[b], 0, 0, 0);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 // ---- online softmax, then P as (hi, lo) planes: registers 8 s .. 8 s + 7 are the B operand of PV's k-step s
-                f16x8 ph[NQB][2], pl[NQB][2];
+                f16x8 ph[AH_NQB][2], pl[AH_NQB][2];
 #pragma unroll
-                for (int b = 0; b < NQB; ++b) {
+                for (int b = 0; b < AH_NQB; ++b) {
                     if (k0 + sub * 32 + 32 > nk) {   // only the last key block can contain keys >= nk
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int key = k0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                             if (key >= nk) st[b][r] = -INFINITY;
                         }
-                    }
-                    if (ABL & 1) {
-#pragma unroll
-                        for (int s = 0; s < 2; ++s) {
-                            ph[b][s] = __builtin_bit_cast(f16x8, f32x4{st[b][8 * s], st[b][8 * s + 1], st[b][8 * s + 2], st[b][8 * s + 3]});
-                            pl[b][s] = __builtin_bit_cast(f16x8, f32x4{st[b][8 * s + 4], st[b][8 * s + 5], st[b][8 * s + 6], st[b][8 * s + 7]});
-                        }
-                        l_run[b] = 1.f; m_run[b] = 0.f;
-                        continue;
                     }
                     ah_softmax_step(st[b], first, m_run[b], l_run[b], o[b][0], o[b][1]);
 #pragma unroll
@@ -298,29 +285,28 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
                         const int off = vrow_off[db] + (((2 * (2 * sub + s) + h) ^ vfrag_sw[db]) << 4);
                         const f16x8 vh = *reinterpret_cast<const f16x8*>(Vh + off);
                         const f16x8 vl = *reinterpret_cast<const f16x8*>(Vl + off);
-                        if (ABL & 4) { o[0][db][s] += (float)vh[0] + (float)vl[1] + (float)ph[0][s][1] + (float)pl[NQB - 1][s][2] + (float)ph[NQB - 1][s][3] + (float)pl[0][s][0]; continue; }
 #pragma unroll
-                        for (int b = 0; b < NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[b][s], o[b][db], 0, 0, 0);
+                        for (int b = 0; b < AH_NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[b][s], o[b][db], 0, 0, 0);
 #pragma unroll
-                        for (int b = 0; b < NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[b][s], o[b][db], 0, 0, 0);
+                        for (int b = 0; b < AH_NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[b][s], o[b][db], 0, 0, 0);
 #pragma unroll
-                        for (int b = 0; b < NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[b][s], o[b][db], 0, 0, 0);
+                        for (int b = 0; b < AH_NQB; ++b) o[b][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[b][s], o[b][db], 0, 0, 0);
                     }
                 __builtin_amdgcn_s_setprio(0);
             }
         }
-        if (DBUF) buf ^= 1;
+        buf ^= 1;
     }
     if (!wactive) {   // all 64 queries of this wave are padding: zero context rows
-        for (int e = lane; e < 32 * NQB * 64; e += 64) {
-            const int row = qb * AH_Q + wave * (32 * NQB) + (e >> 6);
+        for (int e = lane; e < 32 * AH_NQB * 64; e += 64) {
+            const int row = qb * AH_Q + wave * (32 * AH_NQB) + (e >> 6);
             if (row < Lq) out[((size_t)seq * Lq + row) * 256 + head * 64 + (e & 63)] = 0.f;
         }
         return;
     }
 #pragma unroll
-    for (int b = 0; b < NQB; ++b) {
-        const int qrow = qb * AH_Q + wave * (32 * NQB) + b * 32 + j;
+    for (int b = 0; b < AH_NQB; ++b) {
+        const int qrow = qb * AH_Q + wave * (32 * AH_NQB) + b * 32 + j;
         const float l = l_run[b] + __shfl_xor(l_run[b], 32);
         if (qrow < Lq) {
             const float inv = (qrow < nq && l > 0.f) ? 1.0f / l : 0.f;  // padded rows -> 0
@@ -338,23 +324,9 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void lg_attention_h2_kernel(
 // Same contract as launch_lg_attention's throughput path (lg_kernels.hip); called by it when the option is on and the problem is large.
 void launch_lg_attention_h2(hipStream_t s, const float* q, const float* k, const float* v, int ld, float* out, int nseq, int Lq, int Lk,
                             const int* qlen, const int* klen, const int* kv_map, const float* rope_csn) {
-    static const int nqb_sel = tune_int("RFE_AH_NQB", 2);   // tuning switch: 1 = 128-query workgroups of 32-query waves, one tile buffer, three workgroups per CU
-    const int AH_Q = 128 * (nqb_sel == 1 ? 1 : 2);
+    constexpr int AH_Q = 128 * AH_NQB;
     const int nqb = (Lq + AH_Q - 1) / AH_Q;
     const int units8 = (4 * nseq + 7) / 8 * 8;
-#ifdef RFE_TUNING
-    switch (tune_int("RFE_DBG_AH_ABL", 0)) {   // timing ablations (cross variant), tuning build only: profiles/r03_ab_notes.md
-#define RFE_AH_ABL(n) case n: hipLaunchKernelGGL((lg_attention_h2_kernel<false, n>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, nseq, rope_csn); return;
-        RFE_AH_ABL(1) RFE_AH_ABL(2) RFE_AH_ABL(3) RFE_AH_ABL(4) RFE_AH_ABL(6)
-#undef RFE_AH_ABL
-        default: break;
-    }
-#endif
-    if (nqb_sel == 1) {
-        if (rope_csn) hipLaunchKernelGGL((lg_attention_h2_kernel<true, 0, 1, false>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, nseq, rope_csn);
-        else hipLaunchKernelGGL((lg_attention_h2_kernel<false, 0, 1, false>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, nseq, rope_csn);
-        return;
-    }
     if (rope_csn)
         hipLaunchKernelGGL((lg_attention_h2_kernel<true>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, nseq, rope_csn);
     else

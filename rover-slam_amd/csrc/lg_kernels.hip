@@ -69,7 +69,6 @@ __device__ __forceinline__ void at_softmax_step(f32x16& st, bool first, float& m
 }
 __device__ __forceinline__ float at_softmax_finish(float l_run) { return l_run + __shfl_xor(l_run, 32); }
 
-// ABL: timing ablations only (wrong results): 1 = no softmax VALU, 2 = stage only the first K/V tile, 3 = both
 // SPLIT: split-key variant for latency-bound problems (one pair = 64 (sequence, head, query block) units for 256 CUs and
 // a 2048-MFMA serial chain per wave): blockIdx.y selects one of gridDim.y key ranges, the workgroup writes its
 // unnormalised accumulators and (reference max, sum) to `part`, and lg_attention_combine_kernel merges the ranges.
@@ -83,11 +82,11 @@ __device__ __forceinline__ float at_softmax_finish(float l_run) { return l_run +
 // row and L2 resident).  Net effect on the step: none within noise (profiles/r02_ab_notes.md) -- kept because it removes the
 // LDS-transposed epilogue from the GEMM.  Variants that did not pay (double-buffered LDS, register prefetch of the next tile,
 // 64 queries per wave, 256-query workgroups, k rotated by the projection and q here) are recorded in profiles/r01_pmc.md / r02_ab_notes.md.
-// PFK (split variant only): the next K/V tile is fetched into registers right after the current one is published, i.e. under the
+// The split variant prefetches: the next K/V tile is fetched into registers right after the current one is published, i.e. under the
 // MFMAs.  The split variant runs one workgroup per CU, so nothing else hides the global round trip of every tile (the throughput
 // variant has 4 co-resident workgroups and measured slower with the prefetch: 146 VGPRs -> 3 workgroups, profiles/r02_ab_notes.md).
-template <int ABL = 0, bool SPLIT = false, bool ROPE = false, bool PFK = false>
-__global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 workgroups per CU: at most 128 VGPRs
+template <bool SPLIT = false, bool ROPE = false>
+__global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 4 workgroups per CU: at most 128 VGPRs
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld, float* __restrict__ out,
     int Lq, int Lk, int nqb, const int* __restrict__ qlen, const int* __restrict__ klen, const int* __restrict__ kv_map,
     int prio, float* __restrict__ part, int nseq_total, const float* __restrict__ rope_csn) {
@@ -182,17 +181,17 @@ __global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 
         kbeg = (int)blockIdx.y * per;
         kend = kbeg + per < nk ? kbeg + per : nk;
     }
-    if (PFK && kbeg < kend) fetch(kbeg);
+    if (SPLIT && kbeg < kend) fetch(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += AT_K) {
         const bool more = DBUF && (k0 + AT_K < kend);
         if (DBUF) {
             if (more) fetch(k0 + AT_K);
-        } else if (PFK) {
+        } else if (SPLIT) {
             __syncthreads();
             stash(0);
             __syncthreads();
             if (k0 + AT_K < kend) fetch(k0 + AT_K);
-        } else if (!(ABL & 2) || k0 == 0) {
+        } else {
             __syncthreads();
             fetch(k0);
             stash(0);
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 
             f32x16 st;
             const bool first = k0 == kbeg && sub == 0;
             {
-                const float init = (ABL & 1) ? 0.f : at_softmax_init(first, m_run);
+                const float init = at_softmax_init(first, m_run);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) st[r] = init;
             }
@@ -215,7 +214,6 @@ __global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 
             for (int s = 0; s < 32; ++s) st = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * s], qreg[s], st, 0, 0, 0);
             if (prio) __builtin_amdgcn_s_setprio(0);
             // ---- online softmax over this lane's 16 keys (+ the other half-wave's 16)
-            if (!(ABL & 1)) {
             // only the last key tile can contain keys >= nk
             if (k0 + sub * 32 + 32 > nk) {
 #pragma unroll
@@ -225,7 +223,6 @@ __global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 
                 }
             }
             at_softmax_step(st, first, m_run, l_run, o0, o1);
-            } else { l_run = 1.f; }
             // ---- O^T[d][query] += sum_key V[key][d] * P[key][query]; k-step r uses key(r,h)
             const float* va = Vs[buf] + (sub * 32 + 4 * h) * 64 + j;
             if (prio) __builtin_amdgcn_s_setprio(1);
@@ -243,7 +240,7 @@ __global__ __launch_bounds__(256, PFK ? 2 : 4) void lg_attention_kernel(   // 4 
             buf ^= 1;
         }
     }
-    if (!(ABL & 1)) l_run = at_softmax_finish(l_run);
+    l_run = at_softmax_finish(l_run);
     if (SPLIT) {
         if (qrow < Lq) {
             const size_t prow = ((size_t)blockIdx.y * nseq_total + seq) * Lq + qrow;
@@ -291,7 +288,7 @@ constexpr int AD_K = 32;
 __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld, float* __restrict__ out,
     int Lq, int Lk, int nqb, const int* __restrict__ qlen, const int* __restrict__ klen, const int* __restrict__ kv_map,
-    int prio, int nseq_total, const float* __restrict__ rope_q) {
+    int prio, int nseq_total) {
     // Dynamic LDS on purpose: with static `__shared__ float Kd[2][..]` tiles the compiler's wait-count pass cannot tell buffer buf from
     // buf ^ 1 and puts an s_waitcnt vmcnt(0) in front of the first ds_read of tile t -- i.e. AFTER tile t + 1 has just been requested, so
     // every wave sat out that round trip and nothing overlapped (round-3 advisor finding, visible in the ISA).  With one dynamic array and
@@ -322,16 +319,9 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     float qreg[32];   // qreg[4 g + e] = Q[query][8 g + 4 h + e] * scale
     {
         const float4* qp4 = reinterpret_cast<const float4*>(q + qrow_c * ld + head * 64) + h;
-        // rope_q (self blocks at throughput shapes: the projection's epilogue has rotated K, gemm.hip): Q is rotated here, as it is loaded -- a lane's
-        // float4 is two whole pairs (dims 8 g + 4 h .. + 3), (c, s) from the table row of this query; the three operations of every other rotary form
-        const float4* cp4 = rope_q ? reinterpret_cast<const float4*>(rope_q + qrow_c * 64) + h : nullptr;
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-            float4 t = qp4[2 * g];
-            if (rope_q) {
-                const float4 cs = cp4[2 * g];
-                t = make_float4(t.x * cs.x - t.y * cs.y, t.y * cs.x + t.x * cs.y, t.z * cs.z - t.w * cs.w, t.w * cs.z + t.z * cs.w);
-            }
+            const float4 t = qp4[2 * g];
             qreg[4 * g] = t.x * kScale; qreg[4 * g + 1] = t.y * kScale; qreg[4 * g + 2] = t.z * kScale; qreg[4 * g + 3] = t.w * kScale;
         }
     }
@@ -446,68 +436,49 @@ size_t lg_attention_part_bytes(int nseq, int Lq) {   // scratch of the split-key
     return rows <= AT_SPLIT_MAX_ROWS ? rows * AT_SPLIT_MAX * (256 + 8) * sizeof(float) : 0;
 }
 
+// `prio`: s_setprio(1) around the MFMA clusters (+0.8 %).  Always 1, and still a kernel ARGUMENT on purpose: with the s_setprio unconditional the compiler
+// allocates lg_attention_kernel<SPLIT> 150 instead of 142 VGPRs and lg_attention_dma_kernel 121 instead of 120 (profiles/single_path.md) -- do not fold it in
+// without re-checking the register counts and the step time
+constexpr int AT_PRIO = 1;
 void launch_lg_attention(hipStream_t s, const float* q, const float* k, const float* v, int ld, float* out, int nseq, int Lq,
-                         int Lk, const int* qlen, const int* klen, const int* kv_map, float* part, const float* rope_csn, bool fp16x2, bool k_roped) {
-    if (rope_csn && k_roped) {   // K already rotated by the projection's epilogue, Q not (tuning form RFE_QKV_ROPE=2): K / V tiles by LDS-DMA, Q rotated on load
-        const int nqb = (Lq + AT_Q - 1) / AT_Q, units8 = (4 * nseq + 7) / 8 * 8;
-        static const int prio = tune_int("RFE_ATT_PRIO", 1);
-        hipLaunchKernelGGL(lg_attention_dma_kernel, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, prio, nseq, rope_csn);
-        return;
-    }
+                         int Lk, const int* qlen, const int* klen, const int* kv_map, float* part, const float* rope_csn, bool fp16x2) {
     if (fp16x2 && (size_t)nseq * Lq >= 32768 && (ld % 4) == 0) {   // RFE_OPT_LG_FP16X2, throughput shapes (one / few pairs: the split form of the latency kernel below)
         launch_lg_attention_h2(s, q, k, v, ld, out, nseq, Lq, Lk, qlen, klen, kv_map, rope_csn);
         return;
     }
     // latency regime (one / few pairs, the shapes the reference itself runs), keys and queries already rotated by the projection: the
     // in-workgroup key split (lg_attention_lat.hip) -- no partial sums in HBM, no combine launch
-    static const bool lat_on = tune_int("RFE_LAT", 1) != 0;
-    if (lat_on && !rope_csn && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS && launch_lg_attention_lat(s, q, k, v, ld, out, nseq, Lq, Lk, qlen, klen, kv_map, fp16x2)) return;
+    if (!rope_csn && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS && launch_lg_attention_lat(s, q, k, v, ld, out, nseq, Lq, Lk, qlen, klen, kv_map, fp16x2)) return;
     const int nqb = (Lq + AT_Q - 1) / AT_Q;
     // (sequence, head) units, padded to a multiple of 8: the kernels deal their blocks round-robin over the 8 XCDs and map
     // block -> (unit, query block) by unit = (t / nqb) * 8 + xcd, which is a bijection only for a multiple of 8 units
     // (2P sequences always are; the per-frame self block of the stream mode runs on B sequences, e.g. 33)
     const int units8 = (4 * nseq + 7) / 8 * 8;
     const bool rope = rope_csn != nullptr;
-    // latency regime: fewer (sequence, head, query block) units than CUs -> split the keys until the chip is covered
-    static const int split_env = tune_int("RFE_ATT_SPLIT", -1);   // 0/1 = off, n = force n ranges
-    if (part && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS && split_env != 0 && split_env != 1) {
+    // latency shapes the kernel above does not serve: fewer (sequence, head, query block) units than CUs -> split the keys until the chip is covered
+    if (part && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS) {
         const int units = nqb * 4 * nseq;
         int ns = 1;
         while (ns < AT_SPLIT_MAX && units * ns * 2 <= 256 && Lk / (ns * 2) >= 2 * AT_K) ns *= 2;
-        if (split_env > 1) ns = split_env < AT_SPLIT_MAX ? split_env : AT_SPLIT_MAX;
         if (ns > 1) {
-            static const bool pfk = tune_int("RFE_ATT_SPLIT_PF", 1) != 0;
-            if (rope && pfk)
-                hipLaunchKernelGGL((lg_attention_kernel<0, true, true, true>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
-                                   nqb, qlen, klen, kv_map, 1, part, nseq, rope_csn);
-            else if (pfk)
-                hipLaunchKernelGGL((lg_attention_kernel<0, true, false, true>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
-                                   nqb, qlen, klen, kv_map, 1, part, nseq, rope_csn);
-            else if (rope)
-                hipLaunchKernelGGL((lg_attention_kernel<0, true, true>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
-                                   nqb, qlen, klen, kv_map, 1, part, nseq, rope_csn);
+            if (rope)
+                hipLaunchKernelGGL((lg_attention_kernel<true, true>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
+                                   nqb, qlen, klen, kv_map, AT_PRIO, part, nseq, rope_csn);
             else
-                hipLaunchKernelGGL((lg_attention_kernel<0, true, false>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
-                                   nqb, qlen, klen, kv_map, 1, part, nseq, rope_csn);
+                hipLaunchKernelGGL((lg_attention_kernel<true, false>), dim3(nqb * units8, ns), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk,
+                                   nqb, qlen, klen, kv_map, AT_PRIO, part, nseq, rope_csn);
             hipLaunchKernelGGL(lg_attention_combine_kernel, dim3((unsigned)(((size_t)nseq * Lq * 64 + 255) / 256)), dim3(256), 0, s, part,
                                ns, nseq, Lq, qlen, out);
             return;
         }
     }
-#ifdef RFE_TUNING
-    const int abl = tune_int("RFE_DBG_ATT_ABL", 0);   // timing ablations (wrong results), tuning build only
-    if (abl == 1) { hipLaunchKernelGGL((lg_attention_kernel<1>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, 0, nullptr, nseq, rope_csn); return; }
-    if (abl == 2) { hipLaunchKernelGGL((lg_attention_kernel<2>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, 0, nullptr, nseq, rope_csn); return; }
-    if (abl == 3) { hipLaunchKernelGGL((lg_attention_kernel<3>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, 0, nullptr, nseq, rope_csn); return; }
-#endif
-    static const int prio = tune_int("RFE_ATT_PRIO", 1);   // s_setprio(1) around the MFMA clusters (+0.8 %); RFE_ATT_PRIO=0 disables
-    static const bool dma = tune_int("RFE_ATT_DMA", 1) != 0;   // tuning switch: 0 = register-staged tiles for the cross blocks too
-    if (!rope && dma && (ld % 4) == 0)
-        hipLaunchKernelGGL(lg_attention_dma_kernel, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, prio, nseq, (const float*)nullptr);
+    // throughput shapes: K / V tiles by LDS-DMA when q | k arrive rotated (self blocks behind the rotary epilogue, cross blocks); rotary on load otherwise
+    if (!rope && (ld % 4) == 0)
+        hipLaunchKernelGGL(lg_attention_dma_kernel, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nseq);
     else if (rope)
-        hipLaunchKernelGGL((lg_attention_kernel<0, false, true>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, prio, nullptr, nseq, rope_csn);
+        hipLaunchKernelGGL((lg_attention_kernel<false, true>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nullptr, nseq, rope_csn);
     else
-        hipLaunchKernelGGL((lg_attention_kernel<0, false, false>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, prio, nullptr, nseq, rope_csn);
+        hipLaunchKernelGGL((lg_attention_kernel<false, false>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nullptr, nseq, rope_csn);
 }
 
 // ---------------------------------------------------------------- LayerNorm(512) + GELU(erf), in place
@@ -873,10 +844,7 @@ __global__ __launch_bounds__(256) void lg_mutual_kernel(const int32_t* __restric
 // one launch, the workgroup that draws the last ticket of a pair (release fence + atomic per workgroup) running the mutual step -- 29.3 us against
 // 8.4 + 5.1 us for the two kernels: the device-scope fences write the L2s back in every one of the 256 workgroups and the mutual step becomes a
 // serial tail behind the slowest of them; a kernel boundary (2.4-4.3 us) is cheaper.
-bool lg_assign_few_pairs(int P, int L) {
-    static const bool on = tune_int("RFE_LG_ASSIGN_MERGE", 1) != 0;   // tuning build: 0 = the five separate launches
-    return on && (long long)P * ((L + 31) / 32) < 128;
-}
+bool lg_assign_few_pairs(int P, int L) { return (long long)P * ((L + 31) / 32) < 128; }
 void launch_lg_assign(hipStream_t s, const float* sim, const float* z0, const float* z1, int P, int L, int cap,
                       const int* m, const int* n, float thr, float* scores_opt, float* rowlse, float* collse,
                       int32_t* a0, float* mx0, int32_t* a1, int32_t* S, int32_t* pairs, float* ms, int scores_pair,
@@ -890,8 +858,7 @@ void launch_lg_assign(hipStream_t s, const float* sim, const float* z0, const fl
         return;
     }
     hipLaunchKernelGGL(lg_rowlse_kernel, dim3((L + 3) / 4, P), dim3(256), 0, s, sim, L, m, n, rowlse);
-    static const bool col_lds = tune_int("RFE_LG_COL_LDS", 1) != 0;   // tuning switch: 0 = the three-walk kernel for every shape
-    if (col_lds && L <= 1024 && L % 32 == 0 && (long long)P * (L / 32) >= 256)   // throughput shape: stripe resident in LDS, read from HBM once
+    if (L <= 1024 && L % 32 == 0 && (long long)P * (L / 32) >= 256)   // throughput shape: stripe resident in LDS, read from HBM once
         hipLaunchKernelGGL(lg_col_lds_kernel, dim3(L / 32, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);
     else if ((long long)P * ((L + 31) / 32) < 128)   // a few pairs: narrower stripes, 4x the threads per workgroup
         hipLaunchKernelGGL((lg_col_kernel<16, 64>), dim3((L + 15) / 16, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);

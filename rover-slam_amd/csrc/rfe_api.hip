@@ -321,7 +321,7 @@ static int set_sp_upload(rfe_ctx* c, const float* blob);
 static int set_lg_upload(rfe_ctx* c, const float* blob);
 
 static int set_sp(rfe_ctx* c, const float* blob) {
-    const uint64_t hash = fnv1a64(blob, (size_t)SP_COUNT) ^ (uint64_t)conv_ck();
+    const uint64_t hash = fnv1a64(blob, (size_t)SP_COUNT);
     std::lock_guard<std::mutex> lk(g_weights_mu);
     auto key = std::make_tuple(c->device, (int)RFE_KIND_SUPERPOINT, hash, 0);
     for (;; ++std::get<3>(key)) {   // same hash, different contents -> next collision index
@@ -381,7 +381,7 @@ static int set_sp_upload(rfe_ctx* c, const float* blob) {
             if ((rc = upload(c, &c->sp.conv1a_w, t.data(), t.size()))) return rc;
         } else if (L.k == 3) {
             std::vector<float> t;
-            pack_conv3x3_weights(w, L.cin, L.cout, t);
+            pack_conv3x3_weights(w, L.cin, L.cout, L.pool, t);
             if ((rc = upload(c, &c->sp.packed[l], t.data(), t.size()))) return rc;
         } else {
             if ((rc = upload(c, &c->sp.packed[l], w, wn))) return rc;  // [N][K] as-is
@@ -654,20 +654,16 @@ extern "C" int rfe_load_onnx(rfe_ctx* c, const char* sp_path, const char* lg_pat
 namespace {
 
 struct SpBuffers {
-    float *a1, *p1, *a2, *p2, *a3, *p3, *a4, *f4, *pa, *logits, *da, *dmap, *smap, *nmap, *ss;
+    float *p1, *a2, *p2, *a3, *p3, *a4, *f4, *pa, *logits, *da, *dmap, *smap, *nmap, *ss;
     uint8_t *mask, *supp;
     float* cand_score; int32_t* cand_idx;
     unsigned long long* sel_keys; int32_t* sel_n;     // selected (score, pixel) keys between select_kernel and select_rank_kernel
     bool tail_fused = false;                          // sp_tail_lat_kernel ran: candidates are 64-bit keys at cand_score (cand_score | cand_idx = 8 B per pixel)
 };
 
-// conv1a as its own launch (78.6 MB/frame activation in HBM) instead of recomputed inside conv1b: A/B and test switch
-bool sp_unfused_conv1() { static const bool u = tune_env("RFE_UNFUSED_CONV1") != nullptr; return u; }
-
 size_t sp_ws_bytes(int B, int H, int W) {
     const size_t hw = (size_t)B * H * W, cells = hw / 64;
     size_t t = 0;
-    if (sp_unfused_conv1()) t += al(hw * 64 * 4);   // a1: never materialised on the default (fused) path
     t += al(hw / 4 * 64 * 4) * 2;  // p1, a2
     t += al(hw / 16 * 64 * 4);     // p2
     t += al(hw / 16 * 128 * 4);    // a3
@@ -684,7 +680,7 @@ size_t sp_ws_bytes(int B, int H, int W) {
 void sp_carve(void* ws, int B, int H, int W, SpBuffers& b) {
     const size_t hw = (size_t)B * H * W, cells = hw / 64;
     Bump a(ws);
-    b.a1 = sp_unfused_conv1() ? a.take<float>(hw * 64) : nullptr; b.p1 = a.take<float>(hw / 4 * 64); b.a2 = a.take<float>(hw / 4 * 64);
+    b.p1 = a.take<float>(hw / 4 * 64); b.a2 = a.take<float>(hw / 4 * 64);
     b.p2 = a.take<float>(hw / 16 * 64); b.a3 = a.take<float>(hw / 16 * 128);
     b.p3 = a.take<float>(cells * 128); b.a4 = a.take<float>(cells * 128); b.f4 = a.take<float>(cells * 128);
     b.pa = a.take<float>(cells * 256); b.da = a.take<float>(cells * 256); b.dmap = a.take<float>(cells * 256);
@@ -745,34 +741,26 @@ int sp_forward_maps(rfe_ctx* c, const void* img, int H, int W, int stride, int B
     // Hc = H2/2 and the score map / NMS / selection live on the 8Hc x 8Wc frame (= the image when H, W are multiples of 8;
     // KITTI 1241 x 376 -> 155 x 47 cells, score map 1240 x 376).  The workspace carve (sized from B*H*W) is an upper bound.
     const int H1 = H / 2, W1 = W / 2, H2 = H1 / 2, W2 = W1 / 2, Hc = H2 / 2, Wc = W2 / 2, cells = B * Hc * Wc;
-    if (sp_unfused_conv1()) {
-        { ProfScope p(c, "conv1a"); launch_conv1a_u8(s, img, img_f32, stride, B, H, W, w.conv1a_w, w.bias[L_1A], b.a1); }
-        { ProfScope p(c, "conv1b"); launch_conv3x3(s, b.a1, B, H, W, 64, w.packed[L_1B], w.bias[L_1B], 64, true, true, b.p1, L_1B); }
-    } else {   // conv1a recomputed inside conv1b's LDS staging: the [B,H,W,64] activation never touches HBM
-        ProfScope p(c, "conv1ab");
-        launch_conv1ab_fused(s, img, img_f32, stride, B, H, W, w.conv1a_w, w.bias[L_1A], w.packed[L_1B], w.bias[L_1B], b.p1, frame_step);
-    }
-    { ProfScope p(c, "conv2a"); launch_conv3x3(s, b.p1, B, H1, W1, 64, w.packed[L_2A], w.bias[L_2A], 64, true, false, b.a2, L_2A); }
-    { ProfScope p(c, "conv2b"); launch_conv3x3(s, b.a2, B, H1, W1, 64, w.packed[L_2B], w.bias[L_2B], 64, true, true, b.p2, L_2B); }
-    { ProfScope p(c, "conv3a"); launch_conv3x3(s, b.p2, B, H2, W2, 64, w.packed[L_3A], w.bias[L_3A], 128, true, false, b.a3, L_3A); }
-    { ProfScope p(c, "conv3b"); launch_conv3x3(s, b.a3, B, H2, W2, 128, w.packed[L_3B], w.bias[L_3B], 128, true, true, b.p3, L_3B); }
-    { ProfScope p(c, "conv4a"); launch_conv3x3(s, b.p3, B, Hc, Wc, 128, w.packed[L_4A], w.bias[L_4A], 128, true, false, b.a4, L_4A); }
-    { ProfScope p(c, "conv4b"); launch_conv3x3(s, b.a4, B, Hc, Wc, 128, w.packed[L_4B], w.bias[L_4B], 128, true, false, b.f4, L_4B); }
+    { ProfScope p(c, "conv1ab");   // conv1a recomputed inside conv1b's LDS staging: the [B,H,W,64] activation never touches HBM
+      launch_conv1ab_fused(s, img, img_f32, stride, B, H, W, w.conv1a_w, w.bias[L_1A], w.packed[L_1B], w.bias[L_1B], b.p1, frame_step); }
+    { ProfScope p(c, "conv2a"); launch_conv3x3(s, b.p1, B, H1, W1, 64, w.packed[L_2A], w.bias[L_2A], 64, true, kSpLayers[L_2A].pool, b.a2, L_2A); }
+    { ProfScope p(c, "conv2b"); launch_conv3x3(s, b.a2, B, H1, W1, 64, w.packed[L_2B], w.bias[L_2B], 64, true, kSpLayers[L_2B].pool, b.p2, L_2B); }
+    { ProfScope p(c, "conv3a"); launch_conv3x3(s, b.p2, B, H2, W2, 64, w.packed[L_3A], w.bias[L_3A], 128, true, kSpLayers[L_3A].pool, b.a3, L_3A); }
+    { ProfScope p(c, "conv3b"); launch_conv3x3(s, b.a3, B, H2, W2, 128, w.packed[L_3B], w.bias[L_3B], 128, true, kSpLayers[L_3B].pool, b.p3, L_3B); }
+    { ProfScope p(c, "conv4a"); launch_conv3x3(s, b.p3, B, Hc, Wc, 128, w.packed[L_4A], w.bias[L_4A], 128, true, kSpLayers[L_4A].pool, b.a4, L_4A); }
+    { ProfScope p(c, "conv4b"); launch_conv3x3(s, b.a4, B, Hc, Wc, 128, w.packed[L_4B], w.bias[L_4B], 128, true, kSpLayers[L_4B].pool, b.f4, L_4B); }
     // The two heads only share their input f4.  The descriptor head (convDa, convDb, L2 norm: MFMA work) runs on the
     // side stream while the detector head continues on the main one with its tail of small bandwidth / latency-bound
     // kernels (convPb, softmax, 5 NMS passes, selection), which would otherwise leave most of the chip idle.
     // With events around every stage (full profiling pass) the heads stay serial so that the stage times are clean.
-    static const bool fork_env = tune_env("RFE_SP_NO_FORK") == nullptr;
-    const bool fork = fork_env && !(c->prof && c->prof_filter.empty());
+    const bool fork = !(c->prof && c->prof_filter.empty());
     hipStream_t sd = fork ? c->side_stream : s;
     if (fork) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(sd, c->ev_fork, 0)); }
-    { ProfScope p(c, "convDa", sd); launch_conv3x3(sd, b.f4, B, Hc, Wc, 128, w.packed[L_DA], w.bias[L_DA], 256, true, false, b.da, L_DA); }
+    { ProfScope p(c, "convDa", sd); launch_conv3x3(sd, b.f4, B, Hc, Wc, 128, w.packed[L_DA], w.bias[L_DA], 256, true, kSpLayers[L_DA].pool, b.da, L_DA); }
     { ProfScope p(c, "convDb", sd); launch_gemm_nt(sd, gemm_plain(b.da, 256, w.packed[L_DB], 256, w.bias[L_DB], b.dmap, 256, cells, 256, 256)); }
     { ProfScope p(c, "sp_post", sd); launch_descmap_norm(sd, b.dmap, cells); }
     if (fork) RFE_HIP(c, hipEventRecord(c->ev_join, sd));
-    static const bool join_early = tune_env("RFE_SP_JOIN_EARLY") != nullptr;   // tuning build: two streams, but the heads one after the other (diagnostic)
-    if (fork && join_early) RFE_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-    { ProfScope p(c, "convPa"); launch_conv3x3(s, b.f4, B, Hc, Wc, 128, w.packed[L_PA], w.bias[L_PA], 256, true, false, b.pa, L_PA); }
+    { ProfScope p(c, "convPa"); launch_conv3x3(s, b.f4, B, Hc, Wc, 128, w.packed[L_PA], w.bias[L_PA], 256, true, kSpLayers[L_PA].pool, b.pa, L_PA); }
     { ProfScope p(c, "convPb"); launch_gemm_nt(s, gemm_plain(b.pa, 256, w.packed[L_PB], 256, w.bias[L_PB], b.logits, 65, cells, 65, 256)); }
     { ProfScope p(c, "sp_post");
       // one to four frames, published radius: softmax + NMS + candidate compaction in ONE launch (sp_post.hip: sp_tail_lat_kernel); otherwise the separate launches
@@ -1149,13 +1137,12 @@ void lg_ffn(rfe_ctx* c, LgBuffers& b, float* x, const float* second, int rows, c
     // LayerNorm(512) + GELU between the two Linears is fused across them: ffn.0's epilogue leaves per-row partial sums next to the
     // raw h, ffn.3 normalises while it stages its A tiles -- h crosses HBM once in each direction instead of twice (268 MB per block
     // saved, one launch fewer).  Throughput tiles only: launch_gemm_nt returns 0 partials for small problems, which keep the
-    // stand-alone lg_ln_gelu pass (as does RFE_LN_FUSE=0 in the tuning build).
-    static const bool ln_fuse = tune_int("RFE_LN_FUSE", 1) != 0;
+    // stand-alone lg_ln_gelu pass.
     int P = 0;
     { ProfScope p(c, "lg_ffn1");   // A = [x | second]: second is the message, or the attention context when Wo is folded into W1
       GemmArgs a = gemm_lgw(c, x, 256, w1, 512, b1, b.h, 512, rows, 512, 512);
       a.A2 = second; a.lda2 = 256; a.K1 = 256;
-      if (ln_fuse && !gemm_latency_regime(a)) a.stats_out = b.lnstat;   // latency regime: the stand-alone pass below (see lg_kernels.hip)
+      if (!gemm_latency_regime(a)) a.stats_out = b.lnstat;   // latency regime: the stand-alone pass below (see lg_kernels.hip)
       P = launch_gemm_nt(s, a); }
     if (P == 0 && !c->opt_lg_fp16x2) {
         // one / few pairs per call: LayerNorm + GELU inside ffn.3 (ffn2_lat.hip: the 16 x 512 panel normalised once per workgroup) -- no stand-alone
@@ -1163,7 +1150,7 @@ void lg_ffn(rfe_ctx* c, LgBuffers& b, float* x, const float* second, int rows, c
         ProfScope p(c, "lg_ffn2");
         if (launch_ffn2_ln_lat(s, b.h, w2, b2, g, be, x, 256, x, 256, rows)) return;
     }
-    if (P == 0) { ProfScope p(c, "lg_ln_gelu"); launch_lg_ln_gelu(s, b.h, g, be, rows); }   // small problems (and RFE_LN_FUSE=0): stand-alone pass
+    if (P == 0) { ProfScope p(c, "lg_ln_gelu"); launch_lg_ln_gelu(s, b.h, g, be, rows); }   // small problems: stand-alone pass
     { ProfScope p(c, "lg_ffn2");
       GemmArgs a = gemm_lgw(c, b.h, 512, w2, 512, b2, x, 256, rows, 256, 512);
       a.R = x; a.ldr = 256;
@@ -1179,22 +1166,21 @@ bool lg_self_qkv_attention(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, const
     // q,k,v = Wqkv x + b, q and k rotated by the projection's epilogue -- gemm_lat.hip at one / few pairs, gemm.hip's ROPE tile at throughput shapes (table
     // rows staged into LDS by DMA under the K loop) -- so that every attention kernel runs without a table and takes its K tiles straight into LDS
     // (self blocks: lg_attention_dma_kernel 523 us against 565 us for the form that rotates every staged K tile; +9 us on the projection).
-    // Rotating only K there and q as the attention loads it measured worse on both sides (RFE_QKV_ROPE=2, profiles/r05_ab_notes.md).
+    // Rotating only K there and q as the attention loads it measured worse on both sides (profiles/r05_ab_notes.md).
     // RFE_OPT_LG_FP16X2: gemm_h2.hip has no rotary epilogue, lg_attention_h2_kernel rotates both on load.
-    bool roped = false, k_roped = false;
+    bool roped = false;
     { ProfScope p(c, "lg_qkv");
       GemmArgs a = gemm_lgw(c, x, 256, Lw.wqkv, 256, Lw.bqkv, b.qkv, 768, rows, 768, 256);
-      static const int nt_rope = tune_int("RFE_QKV_ROPE", 1);   // tuning switch: 0 = plain epilogue, rotary on load in lg_attention_kernel<.., ROPE>; 2 = only k in the epilogue, q on load
       if (gemm_latency_regime(a) && launch_gemm_lat(s, a, csn, 512)) roped = true;
       else {
-          if (nt_rope && csn) {
-              a.rope_c0 = nt_rope == 2 ? 256 : 0; a.rope_c1 = 512;
-              if (gemm_nt_rope_ok(a)) { a.rope_csn = csn; k_roped = true; roped = nt_rope != 2; }
+          if (csn) {
+              a.rope_c0 = 0; a.rope_c1 = 512;
+              if (gemm_nt_rope_ok(a)) { a.rope_csn = csn; roped = true; }
           }
           launch_gemm_nt(s, a);
       } }
     { ProfScope p(c, "lg_attention");
-      launch_lg_attention(s, b.qkv, b.qkv + 256, b.qkv + 512, 768, b.ctx, nseq, L, L, lens, lens, nullptr, lg_part(b, nseq, L), roped ? nullptr : csn, c->opt_lg_fp16x2, k_roped); }
+      launch_lg_attention(s, b.qkv, b.qkv + 256, b.qkv + 512, 768, b.ctx, nseq, L, L, lens, lens, nullptr, lg_part(b, nseq, L), roped ? nullptr : csn, c->opt_lg_fp16x2); }
     return roped;
 }
 
@@ -1423,8 +1409,7 @@ extern "C" int rfe_extract_match_stream_dev(rfe_ctx* c, const uint8_t* img, int 
     lg_carve(c->ws_lg, P, L, b, extra_bytes);
     float* kn_all = (float*)b.extra;
     hipStream_t s = c->stream;
-    static const bool dedup = tune_env("RFE_NO_SELF_DEDUP") == nullptr;   // tuning / test switch
-    if (!dedup || L != Kmax) {
+    if (L != Kmax) {   // Kmax not a multiple of 4: every pair runs its own layer-0 self block
         { ProfScope p(c, "lg_misc");
           launch_normalize_kpts(s, kxy, (int64_t)B * Kmax, H, W, kn_all);
           if ((rc = lg_stage(c, b, kn_all, kn_all + (size_t)Kmax * 2, desc, desc + (size_t)Kmax * 256, n, n + 1, P, Kmax, Kmax, L))) return rc; }
@@ -1559,14 +1544,13 @@ extern "C" int rfe_stereo_frame_dev(rfe_ctx* c, const uint8_t* imgL, const uint8
         return fail(c, RFE_ERR_INVALID, "stereo_frame: null pointer, stride < W or mb <= 0");
     RFE_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    // state: [2,H,W] staged views (unfused-conv1 tuning path only) | sadv [Kmax] | two slots of { kn [Kmax,2], desc [Kmax,256], n [1] }: the previous left
+    // state: sadv [Kmax] | two slots of { kn [Kmax,2], desc [Kmax,256], n [1] }: the previous left
     // view lives in slot st_flip, this frame's staging kernel fills the other one, then the slots swap -- nothing is copied behind the match
-    const size_t b_img = al((size_t)2 * H * W), b_sad = al((size_t)Kmax * 4), b_kn = al((size_t)Kmax * 8), b_desc = al((size_t)Kmax * 1024), b_n = al(4);
+    const size_t b_sad = al((size_t)Kmax * 4), b_kn = al((size_t)Kmax * 8), b_desc = al((size_t)Kmax * 1024), b_n = al(4);
     const bool fresh = c->st_H != H || c->st_W != W || c->st_K != Kmax;
-    if ((rc = ensure_ws(c, &c->ws_st, &c->ws_st_bytes, b_img + b_sad + 2 * (b_kn + b_desc + b_n) + 256))) return rc;
+    if ((rc = ensure_ws(c, &c->ws_st, &c->ws_st_bytes, b_sad + 2 * (b_kn + b_desc + b_n) + 256))) return rc;
     if (fresh || reset) { c->st_have_prev = false; c->st_H = H; c->st_W = W; c->st_K = Kmax; }
     char* p = (char*)c->ws_st;
-    uint8_t* d_img = (uint8_t*)p; p += b_img;
     int32_t* sadv = (int32_t*)p; p += b_sad;
     float* kn_slot[2]; float* desc_slot[2]; int32_t* n_slot[2];
     for (int q = 0; q < 2; ++q) { kn_slot[q] = (float*)p; p += b_kn; desc_slot[q] = (float*)p; p += b_desc; n_slot[q] = (int32_t*)p; p += b_n; }
@@ -1577,23 +1561,16 @@ extern "C" int rfe_stereo_frame_dev(rfe_ctx* c, const uint8_t* imgL, const uint8
     // kernels slow the latency-bound LightGlue chain (profiles/r02_ab_notes.md).  The two views are read where the caller has them (round 5: conv1's
     // tile loader takes the distance between frame 0 and frame 1 -- any distance, here imgR - imgL; the two staging copies are gone).  The caller keeps
     // them valid until the ctx stream has passed this call, like every input of a *_dev entry.
-    const uint8_t *vL = imgL, *vR = imgR;
-    int vstride = stride;
-    if (sp_unfused_conv1()) {     // tuning path (stand-alone conv1a has no frame step): stage as before
-        RFE_HIP(c, hipMemcpy2DAsync(d_img, (size_t)W, imgL, (size_t)stride, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, s));
-        RFE_HIP(c, hipMemcpy2DAsync(d_img + (size_t)H * W, (size_t)W, imgR, (size_t)stride, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, s));
-        vL = d_img; vR = d_img + (size_t)H * W; vstride = W;
-    }
-    if ((rc = sp_forward(c, vL, H, W, vstride, 2, Kmax, thr, n, kxy, score, desc, nullptr, false, (long long)(vR - vL)))) return rc;
+    if ((rc = sp_forward(c, imgL, H, W, stride, 2, Kmax, thr, n, kxy, score, desc, nullptr, false, (long long)(imgR - imgL)))) return rc;
     // Frame::ComputeStereoMatches (src/Frame.cc:1159-1446) on the device-resident features; counts stay on the device
     // ... on the SIDE stream: the stereo kernels (45 us of small launches) and the temporal LightGlue match below only share their inputs, and
     // the one-pair LightGlue is a chain of latency-bound kernels that leaves room next to it (with an event pair around every stage, full
     // profiling pass, everything stays serial so that the stage times are clean)
-    const bool st_fork = c->st_have_prev && !(c->prof && c->prof_filter.empty()) && tune_env("RFE_ST_NO_FORK") == nullptr;
+    const bool st_fork = c->st_have_prev && !(c->prof && c->prof_filter.empty());
     hipStream_t ss = st_fork ? c->side_stream : s;
     if (st_fork) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(ss, c->ev_fork, 0)); }
     { ProfScope ps(c, "stereo_match", ss);
-      launch_stereo_match_counts(ss, vL, vR, H, W, vstride, kxy, kxy + (size_t)Kmax * 2, Kmax, n, desc,
+      launch_stereo_match_counts(ss, imgL, imgR, H, W, stride, kxy, kxy + (size_t)Kmax * 2, Kmax, n, desc,
                                  desc + (size_t)Kmax * 256, mb, mbf, uRight, depth, sadv); }
     if (st_fork) RFE_HIP(c, hipEventRecord(c->ev_join, ss));
     // every exit below -- the error returns of ensure_ws / lg_forward included -- joins the side stream first: the caller's NEXT call
@@ -1834,7 +1811,7 @@ extern "C" int rfe_k_conv3x3(rfe_ctx* c, const float* in, int B, int H, int W, i
     if ((Cin != 16 && Cin != 32 && Cin != 64 && Cin != 128) || (Cout % 64)) return fail(c, RFE_ERR_INVALID, "k_conv3x3: Cin in {16,32,64,128}, Cout % 64 == 0");
     RFE_HIP(c, hipSetDevice(c->device));
     std::vector<float> packed;
-    pack_conv3x3_weights(w, Cin, Cout, packed);
+    pack_conv3x3_weights(w, Cin, Cout, pool != 0, packed);
     int rc = ensure_ws(c, &c->ws_tmp, &c->ws_tmp_bytes, al(packed.size() * 4) + al((size_t)Cout * 4));
     if (rc) return rc;
     float* dw = (float*)c->ws_tmp; float* db = (float*)((char*)c->ws_tmp + al(packed.size() * 4));

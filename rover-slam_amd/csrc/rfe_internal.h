@@ -13,22 +13,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace rfe {
 
-// Tuning / ablation switches read from the environment exist only in a -DRFE_TUNING build (`make tuning` ->
-// librover_fe_tuning.so, used by tools/ for A/B measurements).  The shipped library never consults the environment:
-// its numerics and kernel choices depend on its arguments and on rfe_set_option alone.
-#ifdef RFE_TUNING
-inline const char* tune_env(const char* name) { return getenv(name); }
-#else
-inline const char* tune_env(const char*) { return nullptr; }
-#endif
-inline int tune_int(const char* name, int dflt) { const char* e = tune_env(name); return e ? atoi(e) : dflt; }
+// The library never consults the environment: its numerics and kernel choices depend on its arguments and on rfe_set_option alone.
 
 // ---------------------------------------------------------------- SuperPoint layer table
 // names follow the reference's dead libtorch header include/SuperPoint.h:24-41
-struct SpLayer { int cin, cout, k; };
+struct SpLayer { int cin, cout, k; bool pool; };   // pool: the fused 2x2 max-pool behind the layer (decides its launch AND which weight images are packed)
 static const SpLayer kSpLayers[12] = {
-    {1, 64, 3}, {64, 64, 3}, {64, 64, 3}, {64, 64, 3}, {64, 128, 3}, {128, 128, 3},
-    {128, 128, 3}, {128, 128, 3}, {128, 256, 3}, {256, 65, 1}, {128, 256, 3}, {256, 256, 1}};
+    {1, 64, 3, false}, {64, 64, 3, true}, {64, 64, 3, false}, {64, 64, 3, true}, {64, 128, 3, false}, {128, 128, 3, true},
+    {128, 128, 3, false}, {128, 128, 3, false}, {128, 256, 3, false}, {256, 65, 1, false}, {128, 256, 3, false}, {256, 256, 1, false}};
 enum { L_1A, L_1B, L_2A, L_2B, L_3A, L_3B, L_4A, L_4B, L_PA, L_PB, L_DA, L_DB };
 
 constexpr int LG_LAYERS = 9;
@@ -36,7 +28,7 @@ constexpr int64_t SP_COUNT = 1300865;
 constexpr int64_t LG_COUNT = 11321153;
 
 // conv3x3 implicit-GEMM tiling (see sp_conv.hip)
-constexpr int CONV_CK = 8;    // input channels per LDS chunk (RFE_CONV_CK=16 selects the larger chunk)
+constexpr int CONV_CK = 8;    // input channels per LDS chunk
 constexpr int CONV_NT = 64;   // output channels per workgroup
 
 // device-side packed SuperPoint weights
@@ -96,13 +88,6 @@ struct GemmArgs {
     // rope_csn != null: LightGlue's rotary encoding applied by the epilogue to output columns rope_c0 <= n < rope_c1 (the k columns of the qkv projection;
     // multiples of 256): (t0, t1) -> (t0 c - t1 s, t1 c + t0 s) on adjacent column pairs, (c, s) = rope_csn[row][(column & 63) / 2].  Plain projections only.
     const float* rope_csn; int rope_c0, rope_c1;
-    // xcd != 0 (set by launch_gemm_nt when the grid allows it): workgroups are dealt round-robin over the 8 XCDs in launch order, so the column tiles of ONE row
-    // panel -- which read the same A rows -- are decoded onto one XCD (one L2 fetch of the panel instead of gridDim.x of them); the tiles are the same, only which
-    // workgroup computes which tile changes
-    int xcd;
-#ifdef RFE_TUNING
-    int abl;   // timing ablations (wrong results): 1 = global loads of the first K tile only, 2 = LDS stores / barriers of the first K tile only, 4 = no epilogue stores
-#endif
 };
 
 }  // namespace rfe
@@ -185,15 +170,14 @@ int ensure_ws(rfe_ctx* c, void** p, size_t* cur, size_t need);
 
 // ---------------------------------------------------------------- kernel launchers
 // sp_conv.hip
-void pack_conv3x3_weights(const float* w_oihw, int cin, int cout, std::vector<float>& out);
-size_t packed_conv3x3_count(int cin, int cout);
-int conv_ck();   // input channels per LDS chunk the 3x3 weights are packed for (8; RFE_CONV_CK=16 for A/B)
-// img: u8 pixels (NormalizeImage fused) or, img_f32, already normalised float pixels; stride in pixels
-void launch_conv1a_u8(hipStream_t s, const void* img, bool img_f32, int stride, int B, int H, int W,
-                      const float* w9x64, const float* bias, float* out);
+// pool: the layer is launched with the fused 2x2 max-pool (decides whether the 16 x 16 x 4 tiles' weight image is emitted: conv3x3_reads_t16)
+bool conv3x3_reads_t16(int cin, int cout, bool pool);
+void pack_conv3x3_weights(const float* w_oihw, int cin, int cout, bool pool, std::vector<float>& out);
+size_t packed_conv3x3_count(int cin, int cout, bool pool);
 void launch_conv3x3(hipStream_t s, const float* in, int B, int H, int W, int cin,
                     const float* wpacked, const float* bias, int cout, bool relu, bool pool, float* out,
                     int tag = 0);
+// img: u8 pixels (NormalizeImage fused) or, img_f32, already normalised float pixels; stride in pixels
 void launch_conv1ab_fused(hipStream_t s, const void* img, bool img_f32, int stride, int B, int H, int W, const float* w1a,
                           const float* b1a, const float* wp, const float* bias, float* out, long long frame_step = 0 /*pixels between frames; 0 = stride * H*/);
 // gemm.hip
@@ -207,7 +191,6 @@ inline void ensure_dynamic_lds(const void* kernel, int bytes, bool* done) {
         if (dev >= 0 && dev < 64) done[dev] = true;
     }
 }
-bool launch_gemm_ln_ws(hipStream_t s, const GemmArgs& g);   // gemm_ws.hip: the LayerNorm-fused consumer with producer / math waves; false = shape not served
 int launch_gemm_h2(hipStream_t s, const GemmArgs& g);   // gemm_h2.hip: split GEMM on the f16 matrix pipe (GemmArgs::Bh / Bl), called by launch_gemm_nt
 void launch_split_f16(hipStream_t s, const float* x, uint16_t* hi, uint16_t* lo, size_t n);
 bool gemm_nt_rope_ok(const GemmArgs& g);                  // may launch_gemm_nt carry GemmArgs::rope_csn for this shape? (set rope_c0 / rope_c1 first)
@@ -218,8 +201,7 @@ inline bool gemm_latency_regime(const GemmArgs& g) {
     const long long b = g.batch > 0 ? g.batch : 1;
     auto tiles = [&](int bm, int bn) { return (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * b; };
     const bool big = (g.N % 256 == 0 && tiles(128, 256) >= 256) || tiles(128, 128) >= 256 || g.M > 8192;
-    static const bool on = tune_int("RFE_LAT", 1) != 0;   // tuning build: RFE_LAT=0 = the round-3 latency path
-    return on && !big;
+    return !big;
 }
 // gemm_lat.hip: false = shape not served (nothing launched).  rope_csn != null: rotary epilogue on output columns < rope_cols (qkv).
 bool launch_gemm_lat(hipStream_t s, const GemmArgs& g, const float* rope_csn, int rope_cols);
@@ -258,8 +240,7 @@ void launch_lg_attention(hipStream_t s, const float* q, const float* k, const fl
                          const int* kv_map /*seq -> kv seq index, or null = identity*/,
                          float* part /*lg_attention_part_bytes(nseq, Lq) of scratch for the split-key variant, or null*/,
                          const float* rope_csn = nullptr /*self blocks: rotary table [nseq*Lq, 32] of (cos, sin) pairs, applied to q and k on load*/,
-                         bool fp16x2 = false /*RFE_OPT_LG_FP16X2: problems of >= 32 768 query rows take lg_attention_h2.hip's split products on the f16 matrix pipe*/,
-                         bool k_roped = false /*with rope_csn: k is already rotated (gemm.hip's rotary epilogue), only q is rotated on load*/);
+                         bool fp16x2 = false /*RFE_OPT_LG_FP16X2: problems of >= 32 768 query rows take lg_attention_h2.hip's split products on the f16 matrix pipe*/);
 void launch_lg_attention_h2(hipStream_t s, const float* q, const float* k, const float* v, int ld, float* out, int nseq, int Lq, int Lk,
                             const int* qlen, const int* klen, const int* kv_map, const float* rope_csn);   // lg_attention_h2.hip
 size_t lg_attention_part_bytes(int nseq, int Lq);

@@ -25,20 +25,16 @@ constexpr int TWS = IW;            // LDS row stride (words)
 constexpr int PLANE = IH * TWS;    // 340 words per input-channel plane
 constexpr int NT = CONV_NT;
 
-// input channels per LDS chunk: 16 (58.6 KB LDS, 2 workgroups/CU) or 8 (29.3 KB, 3-4 workgroups/CU)
-int conv_ck() {
-    static const int ck = [] { const char* e = tune_env("RFE_CONV_CK"); const int v = e ? atoi(e) : CONV_CK; return (v == 8 || v == 16) ? v : CONV_CK; }();
-    return ck;
-}
+constexpr int CK = CONV_CK;        // input channels per LDS chunk: 8 (29.3 KB LDS, 3-4 workgroups/CU)
 
-// two images of the same weights: the implicit-GEMM tiles' [Cout/64][Cin/CK][CK*9][64] and, behind it (Cin a multiple of 16, Cout of 16), the 16 x 16 x 4 tiles'
-// [Cout/16][Cin/16][9][4][16][4] (see conv3x3_t16d_kernel)
-size_t packed_conv3x3_count(int cin, int cout) { return (size_t)cout * cin * 9 * ((cin % 16 == 0 && cout % 16 == 0) ? 2 : 1); }
+// two images of the same weights: the implicit-GEMM tiles' [Cout/64][Cin/CK][CK*9][64] and, behind it for the layers a 16 x 16 x 4 launch can read
+// (conv3x3_reads_t16), those tiles' [Cout/16][Cin/16][9][4][16][4] (see conv3x3_t16d_kernel)
+size_t packed_conv3x3_count(int cin, int cout, bool pool) { return (size_t)cout * cin * 9 * (conv3x3_reads_t16(cin, cout, pool) ? 2 : 1); }
 
 // [Cout/64][Cin/CK][CK*9][64] : element (ct, ch, kl, j) = w[ct*64+j][ch*CK + kl/9][(kl%9)/3][kl%3]
-void pack_conv3x3_weights(const float* w, int cin, int cout, std::vector<float>& out) {
-    out.assign(packed_conv3x3_count(cin, cout), 0.f);
-    const int CK = conv_ck(), KCH = CK * 9;
+void pack_conv3x3_weights(const float* w, int cin, int cout, bool pool, std::vector<float>& out) {
+    out.assign(packed_conv3x3_count(cin, cout, pool), 0.f);
+    const int KCH = CK * 9;
     const int nch = cin / CK, nct = cout / NT;
     for (int ct = 0; ct < nct; ++ct)
         for (int ch = 0; ch < nch; ++ch)
@@ -47,7 +43,7 @@ void pack_conv3x3_weights(const float* w, int cin, int cout, std::vector<float>&
                     int co = ct * NT + j, ci = ch * CK + kl / 9, tap = kl % 9;
                     out[(((size_t)ct * nch + ch) * KCH + kl) * NT + j] = w[((size_t)co * cin + ci) * 9 + tap];
                 }
-    if (cin % 16 || cout % 16) return;
+    if (!conv3x3_reads_t16(cin, cout, pool)) return;
     // the 16 x 16 x 4 tiles (round 6): element (block of 16 output channels b, 16-channel stage st, group g of 16 kappa, lane group q, channel co, step s) =
     // w[16 b + co][16 st + kap / 9][tap = kap % 9] with kap = 16 g + 4 s + q -- the four weights ONE lane (co, q) feeds to the four consecutive k-steps 4 g .. 4 g + 3
     // are 16 contiguous bytes, and the 64 lanes of a group read 1 KB in lane order (one conflict-free ds_read_b128 instead of four ds_read_b32).  The order in which
@@ -77,7 +73,7 @@ __device__ __forceinline__ void conv_a_offsets(int (&aoff)[9], int h, int wave, 
 }
 
 // one staged chunk of CK input channels: CK*9/2 k-steps x 4 MFMA per wave
-template <int CK, int PLANE_ = PLANE, int BLK1_ = TWS>
+template <int PLANE_ = PLANE, int BLK1_ = TWS>
 __device__ __forceinline__ void conv_chunk_mma(const float* lds_in, const float* lds_w, const int (&aoff)[9], int boff,
                                                f32x16 (&acc)[2][2]) {
 #pragma unroll 1
@@ -96,9 +92,8 @@ __device__ __forceinline__ void conv_chunk_mma(const float* lds_in, const float*
     }
 }
 
-template <int CK, int NTHR = 256>
 __device__ __forceinline__ void conv_stage_weights(float* lds_w, const float* src_chunk, int tid) {
-    constexpr int KCH = CK * 9;
+    constexpr int KCH = CK * 9, NTHR = 256;
     const float4* src = reinterpret_cast<const float4*>(src_chunk);
     float4* dst = reinterpret_cast<float4*>(lds_w);
 #pragma unroll
@@ -162,7 +157,7 @@ __device__ __forceinline__ ConvBlock conv_decode(int nct, int gx, int gy, int nt
 static inline unsigned conv_grid(int gx, int gy, int B, int nct) { return (unsigned)(((gx * gy * B + 7) / 8) * 8 * nct); }
 
 // TAG only gives each SuperPoint layer its own kernel symbol (per-layer rows in rocprofv3 --stats)
-template <int CIN, bool POOL, bool RELU, int TAG, int CK>
+template <int CIN, bool POOL, bool RELU, int TAG>
 __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
     const float* __restrict__ in, const float* __restrict__ wp, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int COUT, int gx, int gy, int ntiles) {
@@ -235,9 +230,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
             float* d = lds_in + s_loff[it];
             d[0] = v.x; d[PLANE] = v.y; d[2 * PLANE] = v.z; d[3 * PLANE] = v.w;
         }
-        conv_stage_weights<CK>(lds_w, wp_ct + (size_t)ch * KCH * NT, tid);
+        conv_stage_weights(lds_w, wp_ct + (size_t)ch * KCH * NT, tid);
         __syncthreads();
-        conv_chunk_mma<CK>(lds_in, lds_w, aoff, boff, acc);
+        conv_chunk_mma(lds_in, lds_w, aoff, boff, acc);
     }
     conv_store<POOL, RELU>(acc, out, b, H, W, COUT, x0, y0, co0, wave, col, h);
 }
@@ -251,15 +246,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
 // exchanged through LDS (4 x 32 px x 32 channels, the staging buffers are free by then) and pooled from there.
 constexpr int STH = 4, SNT = 32;
 
-// ROWS (round 6): rows per tile = waves per workgroup, 4 or 5 (no pool).  240 x 320 x 64 channels of ONE frame are 1200 four-row workgroups for 1024 resident slots -- four
-// rounds' worth run together, 176 stragglers follow alone -- but 960 five-row workgroups, all resident at once (conv2a of one frame).
-template <int CIN, bool RELU, int CK, bool POOL = false, int ROWS = STH>
-__global__ __launch_bounds__(64 * ROWS, 4) void conv3x3_small_kernel(
+// (Five-row tiles -- 240 x 320 x 64 channels of ONE frame as 960 workgroups that are all resident at once instead of 1200 -- measured conv2a 60.5 -> 69.8 us:
+// not adopted, profiles/r06_ab_notes.md 2d.)
+template <int CIN, bool RELU, bool POOL = false>
+__global__ __launch_bounds__(64 * STH, 4) void conv3x3_small_kernel(
     const float* __restrict__ in, const float* __restrict__ wp, const float* __restrict__ bias,
     float* __restrict__ out, int H, int W, int COUT, int gx, int gy, int ntiles) {
     constexpr int KCH = CK * 9;
-    static_assert(ROWS == STH || !POOL, "the pooling exchange is written for four rows");
-    constexpr int NTH = 64 * ROWS, RIH = ROWS + 2, RPLANE = RIH * TWS;     // threads, haloed rows, words per input-channel plane
+    constexpr int NTH = 64 * STH, RIH = STH + 2, RPLANE = RIH * TWS;     // threads, haloed rows, words per input-channel plane
     constexpr int LDS_WORDS = (CK * RPLANE + KCH * SNT) > (POOL ? STH * TW * SNT : 0) ? (CK * RPLANE + KCH * SNT) : STH * TW * SNT;
     __shared__ __attribute__((aligned(16))) float lds[LDS_WORDS];
     float* lds_in = lds;
@@ -270,7 +264,7 @@ __global__ __launch_bounds__(64 * ROWS, 4) void conv3x3_small_kernel(
     const ConvBlock blk = conv_decode(COUT / SNT, gx, gy, ntiles);
     if (!blk.valid) return;
     const int b = blk.b, ct = blk.ct;
-    const int x0 = blk.bx * TW, y0 = blk.by * ROWS;
+    const int x0 = blk.bx * TW, y0 = blk.by * STH;
     const int co0 = ct * SNT;
 
     f32x16 acc;
@@ -542,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_t16d_kernel(
 // and a lane's A offsets just start two rows / columns further in when its pixel lies in the second piece.  160 x 1020 canvas for 33
 // frames: 640 tiles, 96.7 % of the MFMA rows are real pixels.  Same per-pixel reduction order as every other variant (bit-exact).
 constexpr int CIH = TH + 4, CIW = TW + 4, CPLANE = CIH * CIW;
-template <int CIN, bool RELU, int TAG, int CK>
+template <int CIN, bool RELU, int TAG>
 __global__ __launch_bounds__(256, 2) void conv3x3_comp_kernel(
     const float* __restrict__ in, const float* __restrict__ wp, const float* __restrict__ bias,
     float* __restrict__ out, int B, int H, int W, int COUT, int gx, int gy, int ntiles) {
@@ -620,9 +614,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_comp_kernel(
             float* d = lds_in + s_loff[it];
             d[0] = v.x; d[CPLANE] = v.y; d[2 * CPLANE] = v.z; d[3 * CPLANE] = v.w;
         }
-        conv_stage_weights<CK>(lds_w, wp_ct + (size_t)ch * KCH * NT, tid);
+        conv_stage_weights(lds_w, wp_ct + (size_t)ch * KCH * NT, tid);
         __syncthreads();
-        conv_chunk_mma<CK, CPLANE, CIW>(lds_in, lds_w, aoff, boff, acc);
+        conv_chunk_mma<CPLANE, CIW>(lds_in, lds_w, aoff, boff, acc);
     }
     // epilogue: D layout as in conv_store, every pixel mapped back to (frame, y, x)
 #pragma unroll
@@ -646,7 +640,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_comp_kernel(
 // ------------------------------------------------------------------------------------------
 // conv1a + conv1b fused: the 64-channel input tile of conv1b is never read from HBM; every staged
 // 8-channel chunk is recomputed in LDS from the u8 image tile (NormalizeImage * 1/255, conv1a 1->64,
-// bias, ReLU -- same fmaf chain as conv1a_u8_kernel / the oracle, so still bit-exact), then conv1b +
+// bias, ReLU -- same fmaf chain as the oracle, so still bit-exact), then conv1b +
 // ReLU + 2x2 max-pool as above.  Removes the 78.6 MB/frame round trip of the largest activation.
 // PX = uint8_t: the reference's NormalizeImage (x * 1/255) is applied here; PX = float: an already normalised CV_32F image as the reference's
 // Extractor_Inference takes it (src/Extractors/superpoint_onnx.cc:88-118) is used as it is.  stride in pixels.
@@ -656,7 +650,7 @@ __device__ __forceinline__ float px_value(PX v) {
     else return v;
 }
 
-template <int CK, typename PX>
+template <typename PX>
 __global__ __launch_bounds__(256, 2) void conv1ab_fused_kernel(
     const PX* __restrict__ img, int stride, const float* __restrict__ w1a /*[9][64]*/, const float* __restrict__ b1a,
     const float* __restrict__ wp, const float* __restrict__ bias, float* __restrict__ out, int H, int W, long long frame_step /*pixels from frame b to b + 1*/) {
@@ -724,9 +718,9 @@ __global__ __launch_bounds__(256, 2) void conv1ab_fused_kernel(
                 lds_in[e * PLANE + p_loff[it]] = p_inb[it] ? fmaxf(a, 0.f) : 0.f;
             }
         }
-        conv_stage_weights<CK>(lds_w, wp + (size_t)ch * KCH * NT, tid);
+        conv_stage_weights(lds_w, wp + (size_t)ch * KCH * NT, tid);
         __syncthreads();
-        conv_chunk_mma<CK>(lds_in, lds_w, aoff, boff, acc);
+        conv_chunk_mma(lds_in, lds_w, aoff, boff, acc);
     }
     conv_store<true, true>(acc, out, b, H, W, COUT, x0, y0, 0, wave, col, h);
 }
@@ -735,52 +729,45 @@ void launch_conv1ab_fused(hipStream_t s, const void* img, bool img_f32, int stri
                           const float* b1a, const float* wp, const float* bias, float* out, long long frame_step) {
     dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH, B);
     if (frame_step == 0) frame_step = (long long)stride * H;
-    if (img_f32) {
-        if (conv_ck() == 8)
-            hipLaunchKernelGGL((conv1ab_fused_kernel<8, float>), grid, dim3(256), 0, s, (const float*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
-        else
-            hipLaunchKernelGGL((conv1ab_fused_kernel<16, float>), grid, dim3(256), 0, s, (const float*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
-        return;
-    }
-    if (conv_ck() == 8)
-        hipLaunchKernelGGL((conv1ab_fused_kernel<8, uint8_t>), grid, dim3(256), 0, s, (const uint8_t*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
-    else
-        hipLaunchKernelGGL((conv1ab_fused_kernel<16, uint8_t>), grid, dim3(256), 0, s, (const uint8_t*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
+    if (img_f32) hipLaunchKernelGGL((conv1ab_fused_kernel<float>), grid, dim3(256), 0, s, (const float*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
+    else hipLaunchKernelGGL((conv1ab_fused_kernel<uint8_t>), grid, dim3(256), 0, s, (const uint8_t*)img, stride, w1a, b1a, wp, bias, out, H, W, frame_step);
 }
 
 #define RFE_CONV_LAUNCH(CIN, POOL, RELU, TAG)                                                                            \
-    do {                                                                                                                \
-        if (ck8) hipLaunchKernelGGL((conv3x3_mfma_kernel<CIN, POOL, RELU, TAG, 8>), dim3(conv_grid(gx, gy, B, cout / NT)), dim3(256), 0, s, in, wp, bias, out, H, W, cout, gx, gy, gx * gy * B); \
-        else hipLaunchKernelGGL((conv3x3_mfma_kernel<CIN, POOL, RELU, TAG, 16>), dim3(conv_grid(gx, gy, B, cout / NT)), dim3(256), 0, s, in, wp, bias, out, H, W, cout, gx, gy, gx * gy * B);   \
-    } while (0)
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<CIN, POOL, RELU, TAG>), dim3(conv_grid(gx, gy, B, cout / NT)), dim3(256), 0, s, in, wp, bias, out, H, W, cout, gx, gy, gx * gy * B)
 
-// tag: SuperPoint layer id (L_1B .. L_DA) for the production path, 0 for the generic test hook
+// pixel budgets (B * H * W) of the 16 x 16 x 4 tiles, see launch_conv3x3
+constexpr int CONV_T16_PX = 12000, CONV_T16_PX64 = 20000, CONV_T16P_PX128 = 20000;
+
+// may a conv3x3_t16d_kernel launch of launch_conv3x3 read this layer's second weight image?  (The pooling layers with 64 input channels never take those tiles.)
+bool conv3x3_reads_t16(int cin, int cout, bool pool) { return (cin == 128 || (cin == 64 && !pool)) && cout % T16_NC == 0; }
+
+// tag: SuperPoint layer id (L_2A .. L_DA) for the production path, 0 for the generic test hook
 void launch_conv3x3(hipStream_t s, const float* in, int B, int H, int W, int cin, const float* wp,
                     const float* bias, int cout, bool relu, bool pool, float* out, int tag) {
     const int gx = (W + TW - 1) / TW, gy = (H + TH - 1) / TH;
-    const bool ck8 = conv_ck() == 8;
+    const long long px = (long long)B * H * W;
     // latency regime: too few 8 x 32 x 64 tiles to occupy the chip -> 4 x 32 x 32 tiles (4x the workgroups)
-    static const int small_thr = tune_int("RFE_CONV_SMALL", 700);   // 0 disables; 700: conv2a / conv2b of two VGA frames (600 tiles) take the small tile (117 -> 111 us each), two 752 x 480 frames (720 tiles) do not (measured slower: 2.613 against 2.595 ms per stereo frame)
+    constexpr int CONV_SMALL = 700;   // conv2a / conv2b of two VGA frames (600 tiles) take the small tile (117 -> 111 us each), two 752 x 480 frames (720 tiles) do not (measured slower: 2.613 against 2.595 ms per stereo frame)
+    const bool small = (long long)gx * gy * B * (cout / NT) < CONV_SMALL && (cin == 64 || cin == 128);
     // ... and, among those, the layers WITHOUT a pool of up to 12 000 pixels (Cin = 128: conv4a / conv4b / convPa / convDa of one or two frames, 60 x 80 or
     // 60 x 94 each) or 20 000 pixels (Cin = 64: conv3a of one frame): 16 x 16 x 4 tiles with LDS-DMA rings.  Measured at 640 x 480, event-timed stages
     // (profiles/r04_ab_notes.md): one frame conv4a / 4b 39 -> 29 us, convPa / Da 49 -> 45, conv3a 41 -> 36; two frames conv4a / 4b 54 -> 45, convPa / Da
     // 74 -> 68; beyond those budgets the 32-channel tiles re-read the weights too often (conv3a at two frames 60 -> 66 us) and conv3x3_small_kernel stays.
-    static const int t16_px = tune_int("RFE_CONV_T16", 12000), t16_px64 = tune_int("RFE_CONV_T16_64", 20000);   // pixel budgets; 0 disables (tuning build)
-    if (ck8 && relu && !pool && (long long)gx * gy * B * (cout / NT) < small_thr && (cin == 64 || cin == 128) &&
-        (long long)B * H * W <= (cin == 64 ? t16_px64 : t16_px) && cout % T16_NC == 0) {
+    if (small && relu && !pool && px <= (cin == 64 ? CONV_T16_PX64 : CONV_T16_PX) && cout % T16_NC == 0) {
         const int sx = (W + T16_W - 1) / T16_W, sy = (H + T16_H - 1) / T16_H;
         // 16 output channels per workgroup (one accumulator chain per wave, twice the workgroups, 48 KB of LDS: three workgroups per CU) while the
-        // 32-channel grid is below nc16_thr workgroups: a 60 x 80 layer of ONE frame is 300 (conv4a / 4b) or 600 (convPa / Da) workgroups of 32 channels
+        // 32-channel grid is below CONV_T16_NC16 workgroups: a 60 x 80 layer of ONE frame is 300 (conv4a / 4b) or 600 (convPa / Da) workgroups of 32 channels
         // for 256 CUs x 2 -- 88 CUs run three, 168 run two, and a wave alone on its SIMD issues its chain at 40 instead of 32 cycles
-        // Measured on one box (tools/tune_sweep.py, 200 steps, off / 700 / 1300 / 2500): one 640 x 480 frame 0.630 -> 0.605 ms (conv4a / 4b 28.7 -> 22.3 us,
+        // Measured on one box (200 steps, off / 700 / 1300 / 2500): one 640 x 480 frame 0.630 -> 0.605 ms (conv4a / 4b 28.7 -> 22.3 us,
         // convPa / Da 45 -> 33.7), one pair 2.314 -> 2.276, one 752 x 480 stereo frame 2.517 -> 2.487 (2500: convPa / Da of two 60 x 94 maps too); the
         // 64-channel-input layer (conv3a of one frame, 1200 workgroups) does not gain (36.6 -> 37.2 us) and keeps 32.
-        static const int nc16_thr = tune_int("RFE_CONV_T16_NC16", 1000);   // round 6 (b128 weight fragments): convPa / Da of TWO frames (1200 - 1440 workgroups of 32 channels) are better off with 32 (60.2 -> 58.4, 71 -> 69 us), everything smaller with 16   // 0 disables (tuning build A/B)
-        if (cin == 128 && (long long)sx * sy * B * (cout / T16_NC) < nc16_thr && cout % 16 == 0) {
+        constexpr int CONV_T16_NC16 = 1000;   // round 6 (b128 weight fragments): convPa / Da of TWO frames (1200 - 1440 workgroups of 32 channels) are better off with 32 (60.2 -> 58.4, 71 -> 69 us), everything smaller with 16
+        if (cin == 128 && (long long)sx * sy * B * (cout / T16_NC) < CONV_T16_NC16) {
             const dim3 g16(conv_grid(sx, sy, B, cout / 16));
             constexpr int b16 = 3 * (T16D_PIX * T16_CK + T16D_WROWS * 16) * 4;        // 51 KB
-            static bool l16_[2][64];
-            ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<128, true, 16>, b16, l16_[0]);
+            static bool l16_[64];
+            ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<128, true, 16>, b16, l16_);
             hipLaunchKernelGGL((conv3x3_t16d_kernel<128, true, 16>), g16, dim3(256), b16, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
             return;
         }
@@ -798,69 +785,46 @@ void launch_conv3x3(hipStream_t s, const float* in, int B, int H, int W, int cin
     }
     // the pooling layer with 128 input channels (conv3b) of ONE frame on the 16 x 16 x 4 tiles with 16 output channels per workgroup (round 6,
     // conv3x3_t16d_kernel<128, true, 16, POOL>): 120 x 160 x 128 channels = 2400 workgroups of one accumulator chain per wave instead of 600 workgroups of
-    // 32 x 32 x 2 chains that leave 88 CUs with three and 168 with two.  Measured (tools/tune_sweep.py, c2, 200 steps, two alternating runs, profiles/r06_ab_notes.md):
+    // 32 x 32 x 2 chains that leave 88 CUs with three and 168 with two.  Measured (c2, 200 steps, two alternating runs, profiles/r06_ab_notes.md):
     // conv3b 73.4 -> 64.0 us (32 channels per workgroup: 69.3); two frames with 32 channels 110 -> 128 us, the 64-input-channel layer (conv2b, 240 x 320)
-    // 59.4 -> 68.3 us -- neither is taken.  Pixel budgets per Cin, 0 = off.
-    static const int t16p_px64 = tune_int("RFE_CONV_T16P_64", 0), t16p_px128 = tune_int("RFE_CONV_T16P_128", 20000), t16p_nc16 = tune_int("RFE_CONV_T16P_NC16", 1);
-    if (ck8 && relu && pool && (cin == 64 || cin == 128) && (long long)B * H * W <= (cin == 64 ? t16p_px64 : t16p_px128) && cout % T16_NC == 0 && H % 2 == 0 && W % 2 == 0) {
+    // 59.4 -> 68.3 us -- neither is taken.
+    if (relu && pool && cin == 128 && px <= CONV_T16P_PX128 && cout % T16_NC == 0 && H % 2 == 0 && W % 2 == 0) {
         const int sx = (W + T16_W - 1) / T16_W, sy = (H + T16_H - 1) / T16_H;
-        static bool lp_[4][64];
-        if (t16p_nc16) {
-            constexpr int b16 = 3 * (T16D_PIX * T16_CK + T16D_WROWS * 16) * 4;
-            const dim3 g16(conv_grid(sx, sy, B, cout / 16));
-            if (cin == 128) { ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<128, true, 16, true>, b16, lp_[0]);
-                              hipLaunchKernelGGL((conv3x3_t16d_kernel<128, true, 16, true>), g16, dim3(256), b16, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B); }
-            else { ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<64, true, 16, true>, b16, lp_[1]);
-                   hipLaunchKernelGGL((conv3x3_t16d_kernel<64, true, 16, true>), g16, dim3(256), b16, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B); }
-            return;
-        }
-        constexpr int bytes = 3 * (T16D_PIX * T16_CK + T16D_WROWS * T16_NC) * 4;
-        const dim3 gs(conv_grid(sx, sy, B, cout / T16_NC));
-        if (cin == 128) { ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<128, true, T16_NC, true>, bytes, lp_[2]);
-                          hipLaunchKernelGGL((conv3x3_t16d_kernel<128, true, T16_NC, true>), gs, dim3(256), bytes, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B); }
-        else { ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<64, true, T16_NC, true>, bytes, lp_[3]);
-               hipLaunchKernelGGL((conv3x3_t16d_kernel<64, true, T16_NC, true>), gs, dim3(256), bytes, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B); }
+        constexpr int b16 = 3 * (T16D_PIX * T16_CK + T16D_WROWS * 16) * 4;
+        static bool lp_[64];
+        ensure_dynamic_lds((const void*)conv3x3_t16d_kernel<128, true, 16, true>, b16, lp_);
+        hipLaunchKernelGGL((conv3x3_t16d_kernel<128, true, 16, true>), dim3(conv_grid(sx, sy, B, cout / 16)), dim3(256), b16, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
         return;
     }
-    if (ck8 && (!pool || relu) && (long long)gx * gy * B * (cout / NT) < small_thr && (cin == 64 || cin == 128)) {
+    if (small && (!pool || relu)) {
         const int sx = (W + TW - 1) / TW, sy = (H + STH - 1) / STH;
         const dim3 gs(conv_grid(sx, sy, B, cout / SNT));
         if (pool) {   // (every pooling layer of SuperPoint has a ReLU)
-            if (cin == 128) hipLaunchKernelGGL((conv3x3_small_kernel<128, true, 8, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
-            else hipLaunchKernelGGL((conv3x3_small_kernel<64, true, 8, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
-            return;
+            if (cin == 128) hipLaunchKernelGGL((conv3x3_small_kernel<128, true, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
+            else hipLaunchKernelGGL((conv3x3_small_kernel<64, true, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
         }
-        // five-row tiles (round 6, tuning switch): the 64-channel pool-less layer of ONE 240 x 320 map (conv2a of one frame) as 960 workgroups of five waves
-        static const int r5_px = tune_int("RFE_CONV_SMALL_R5", 0);   // pixel budget, 0 = off
-        if (cin == 64 && relu && (long long)B * H * W <= r5_px) {
-            const int sy5 = (H + 4) / 5;
-            hipLaunchKernelGGL((conv3x3_small_kernel<64, true, 8, false, 5>), dim3(conv_grid(sx, sy5, B, cout / SNT)), dim3(320), 0, s, in, wp, bias, out, H, W, cout, sx, sy5, sx * sy5 * B);
-            return;
-        }
-        if (cin == 128 && relu) hipLaunchKernelGGL((conv3x3_small_kernel<128, true, 8>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
-        else if (cin == 128) hipLaunchKernelGGL((conv3x3_small_kernel<128, false, 8>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
-        else if (relu) hipLaunchKernelGGL((conv3x3_small_kernel<64, true, 8>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
-        else hipLaunchKernelGGL((conv3x3_small_kernel<64, false, 8>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
+        else if (cin == 128 && relu) hipLaunchKernelGGL((conv3x3_small_kernel<128, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
+        else if (cin == 128) hipLaunchKernelGGL((conv3x3_small_kernel<128, false>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
+        else if (relu) hipLaunchKernelGGL((conv3x3_small_kernel<64, true>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
+        else hipLaunchKernelGGL((conv3x3_small_kernel<64, false>), gs, dim3(256), 0, s, in, wp, bias, out, H, W, cout, sx, sy, sx * sy * B);
         return;
     }
     // 60 x 80 grid (conv4a/4b, convPa/Da), TFLOP/s at batch 33: plain 8x32 tiles 94 / 103 (22 % of the MFMA rows are padding); round-2a
     // tilings that divide the grid exactly with M-blocks of 2 rows x 16 columns (4x80 tile of 5 waves, 12x16 tile of 3 waves) 99 / 110;
     // composite 8x32 tiles over the two-frames-wide canvas 125 / 127 -> adopted, the 2x16-block kernels are gone (profiles/r02_ab_notes.md)
-    static const int comp = tune_int("RFE_CONV_COMP", 1);   // composite tiles over the two-frames-wide canvas (0: round-2a tilings)
-    if (comp && ck8 && !pool && relu && cin == 128 && (tag == L_4A || tag == L_4B || tag == L_PA || tag == L_DA) && B >= 2 &&
+    if (!pool && relu && cin == 128 && (tag == L_4A || tag == L_4B || tag == L_PA || tag == L_DA) && B >= 2 &&
         H % 2 == 0 && W >= TW && H >= TH && (H % TH != 0 || W % TW != 0) &&
         (long long)B * H * W * cin < (1ll << 31)) {   // 32-bit element offsets over the whole batch inside the kernel
         const int cx = (2 * W + TW - 1) / TW, cy = (((B + 1) / 2) * H + TH - 1) / TH;
         const dim3 gc(conv_grid(cx, cy, 1, cout / NT));
         switch (tag) {
-            case L_4A: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_4A, 8>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
-            case L_4B: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_4B, 8>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
-            case L_PA: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_PA, 8>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
-            default: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_DA, 8>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
+            case L_4A: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_4A>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
+            case L_4B: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_4B>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
+            case L_PA: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_PA>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
+            default: hipLaunchKernelGGL((conv3x3_comp_kernel<128, true, L_DA>), gc, dim3(256), 0, s, in, wp, bias, out, B, H, W, cout, cx, cy, cx * cy); return;
         }
     }
     switch (tag) {
-        case L_1B: RFE_CONV_LAUNCH(64, true, true, L_1B); return;
         case L_2A: RFE_CONV_LAUNCH(64, false, true, L_2A); return;
         case L_2B: RFE_CONV_LAUNCH(64, true, true, L_2B); return;
         case L_3A: RFE_CONV_LAUNCH(64, false, true, L_3A); return;
@@ -883,53 +847,6 @@ void launch_conv3x3(hipStream_t s, const float* in, int B, int H, int W, int cin
     else if (cin == 128) RFE_CONV_GEN(128);
     else if (cin == 16) RFE_CONV_GEN(16);
     else if (cin == 32) RFE_CONV_GEN(32);
-}
-
-// ------------------------------------------------------------------------------------------
-// conv1a: u8 image -> (x * 1/255) -> conv3x3 1->64 + bias + ReLU, NHWC out.  HBM bound (writes
-// 256 B per pixel).  16 lanes per pixel, 4 output channels per lane: a wave stores 1 KB contiguous.
-// NormalizeImage (reference src/Matchers/transform.cpp:11) is fused here.
-template <typename PX>
-__global__ __launch_bounds__(256) void conv1a_u8_kernel(const PX* __restrict__ img, int stride,
-                                                        int H, int W, const float* __restrict__ w9x64,
-                                                        const float* __restrict__ bias,
-                                                        float* __restrict__ out) {
-    const int b = blockIdx.y;
-    const int cg = threadIdx.x & 15;  // channel group: channels 4cg..4cg+3
-    float wr[9][4], br[4];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wr[k][e] = w9x64[k * 64 + cg * 4 + e];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) br[e] = bias[cg * 4 + e];
-    const PX* im = img + (size_t)b * stride * H;
-    float* ob = out + (size_t)b * H * W * 64;
-    const int npix = H * W;
-    for (int p = blockIdx.x * 16 + (threadIdx.x >> 4); p < npix; p += gridDim.x * 16) {
-        const int y = p / W, x = p % W;
-        float a[4] = {br[0], br[1], br[2], br[3]};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int gy = y + ky - 1, gx = x + kx - 1;
-                float v = 0.f;
-                if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = px_value(im[(size_t)gy * stride + gx]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = fmaf(v, wr[ky * 3 + kx][e], a[e]);
-            }
-        float4 o = make_float4(fmaxf(a[0], 0.f), fmaxf(a[1], 0.f), fmaxf(a[2], 0.f), fmaxf(a[3], 0.f));
-        *reinterpret_cast<float4*>(ob + (size_t)p * 64 + cg * 4) = o;
-    }
-}
-
-void launch_conv1a_u8(hipStream_t s, const void* img, bool img_f32, int stride, int B, int H, int W,
-                      const float* w9x64, const float* bias, float* out) {
-    int blocks = (H * W + 15) / 16;
-    if (blocks > 4096) blocks = 4096;
-    if (img_f32) hipLaunchKernelGGL(conv1a_u8_kernel<float>, dim3(blocks, B), dim3(256), 0, s, (const float*)img, stride, H, W, w9x64, bias, out);
-    else hipLaunchKernelGGL(conv1a_u8_kernel<uint8_t>, dim3(blocks, B), dim3(256), 0, s, (const uint8_t*)img, stride, H, W, w9x64, bias, out);
 }
 
 }  // namespace rfe

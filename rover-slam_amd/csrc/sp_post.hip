@@ -285,12 +285,11 @@ void launch_nms(hipStream_t st, const float* score, int B, int H, int W, int rad
                 uint8_t* tmp_mask, uint8_t* tmp_supp, float* out) {
     // One or two frames per call only: the fused kernel needs 127 KB of LDS (one workgroup per CU, 150 tiles per VGA frame -- fine when
     // there are one or two frames), at 33 frames its 4950 workgroups run in 20 rounds and the five light launches win (0.57 vs 0.25 ms per step)
-    static const int fused_frames = tune_int("RFE_NMS_FUSED", 4);   // tuning build: 0 = the five-launch form at every batch size
-    if (radius == NF_R && B <= fused_frames) {
+    constexpr int NMS_FUSED_FRAMES = 4;
+    if (radius == NF_R && B <= NMS_FUSED_FRAMES) {
         const int gx = (W + NTW - 1) / NTW;
         auto wgs = [&](int th) { return (long long)gx * ((H + th - 1) / th) * B; };
-        static const int th_env = tune_int("RFE_NMS_TH", 0);   // tuning build: force the tile height
-        const int th = th_env ? th_env : (wgs(32) <= 256 ? 32 : wgs(40) <= 256 ? 40 : wgs(48) <= 256 ? 48 : 32);
+        const int th = wgs(32) <= 256 ? 32 : wgs(40) <= 256 ? 40 : wgs(48) <= 256 ? 48 : 32;
 #define RFE_NMS_FUSED_GO(TH_)                                                                                                        \
         do {                                                                                                                         \
             constexpr int bytes = (TH_ + 2 * NF_HALO) * NF_IW * 17;   /* four float planes + one byte plane */                         \
@@ -630,8 +629,8 @@ void launch_select(hipStream_t s, const float* nms, int B, int H, int W, int Kma
     hipLaunchKernelGGL(select_count_kernel, dim3(nch, B), dim3(256), 0, s, nms, HW, nch, thr, chunk_cnt);
     hipLaunchKernelGGL(select_compact_kernel, dim3(nch, B), dim3(256), 0, s, nms, HW, nch, thr, chunk_cnt, cand_score, cand_idx);
     // one or two frames: rank-all over the chip; more: one select workgroup per frame already runs the frames in parallel
-    static const int ra_frames = tune_int("RFE_SELECT_RANKALL", 4);   // tuning build: 0 = the radix-select form at every batch size
-    if (B <= ra_frames) {
+    constexpr int SELECT_RANKALL_FRAMES = 4;
+    if (B <= SELECT_RANKALL_FRAMES) {
         const int cap = HW < RA_MAX ? HW : RA_MAX, span = cap > Kmax ? cap : Kmax;
         static bool ls_[64];
         ensure_dynamic_lds((const void*)select_rankall_kernel, RA_MAX * 8, ls_);
@@ -877,13 +876,12 @@ __global__ __launch_bounds__(256) void select_rankall_keys_kernel(const unsigned
 // false = not served (more than four frames, another NMS radius): the caller runs the separate launches
 bool launch_sp_tail_lat(hipStream_t st, const float* logits, int B, int Hc, int Wc, int radius, int border, float thr, unsigned long long* cand_keys,
                         int32_t* cand_cnt, float* smap_out, float* nmap_out) {
-    static const int frames = tune_int("RFE_SP_TAIL_FUSED", 4);   // tuning build: 0 = the separate launches at every batch size
-    if (radius != NF_R || B > frames || B < 1) return false;
+    constexpr int SP_TAIL_FUSED_FRAMES = 4;
+    if (radius != NF_R || B > SP_TAIL_FUSED_FRAMES || B < 1) return false;
     const int H = 8 * Hc, W = 8 * Wc;
     const int gx = (W + NTW - 1) / NTW;
     auto wgs = [&](int th) { return (long long)gx * ((H + th - 1) / th) * B; };
-    static const int th_env = tune_int("RFE_NMS_TH", 0);
-    const int th = th_env ? th_env : (wgs(32) <= 256 ? 32 : wgs(40) <= 256 ? 40 : wgs(48) <= 256 ? 48 : 32);
+    const int th = wgs(32) <= 256 ? 32 : wgs(40) <= 256 ? 40 : wgs(48) <= 256 ? 48 : 32;
 #define RFE_SP_TAIL_GO(TH_)                                                                                                                  \
     do {                                                                                                                                     \
         constexpr int bytes = (TH_ + 2 * NF_HALO) * NF_IW * 17;                                                                               \
