@@ -252,7 +252,7 @@ int rfe_extract_match_stream_dev(rfe_ctx* ctx, const uint8_t* img_dev, int H, in
                                  int32_t* S_dev, int32_t* pairs_dev, float* ms_dev);
 
 /* ---- sparse stereo matching ----
- * Frame::ComputeStereoMatches (src/Frame.cc:1159-1446) for nLevels == 1: for every left keypoint, best right
+ * Frame::ComputeStereoMatches (src/Frame.cc:1159-1446) for nLevels == 1 (rfe_stereo_match_pyramid below for nLevels > 1): for every left keypoint, best right
  * keypoint within +-2 rows and the disparity range [0, mbf/mb) by 256-d L2 distance
  * (SPmatcher::DescriptorDistance_sp, src/Matchers/SPmatcher.cc:2184-2189; accepted below (TH_HIGH+TH_LOW)/2 = 1.3),
  * 11x11 SAD refinement over +-5 px on the raw images, parabola sub-pixel fit, median outlier cut.
@@ -282,6 +282,47 @@ int rfe_stereo_frame_dev(rfe_ctx* ctx, const uint8_t* imgL_dev, const uint8_t* i
                          float thr, float filter_thr, float mb, float mbf, int reset, int32_t* n_dev, int32_t* kxy_dev,
                          float* score_dev, float* desc_dev, float* uRight_dev, float* depth_dev, int32_t* S_dev,
                          int32_t* pairs_dev, float* ms_dev);
+
+/* ---- octave-aware sparse stereo matching: scale-pyramid keypoints (SPextractor with nlevels > 1) ----
+ * Frame::ComputeStereoMatches (src/Frame.cc:1159-1446) with its four uses of the scale pyramid: the row band of a RIGHT keypoint is
+ * r = 2 * mvScaleFactors[kpR.octave] (:1207-1218), a candidate's octave lies within +-1 of the left keypoint's (:1273), the SAD
+ * refinement runs at the left keypoint's level on coordinates round(pt * mvInvScaleFactors[octave]) (:1302-1307), and the result
+ * goes back to level 0 with mvScaleFactors[octave] (:1405).  Everything else is rfe_stereo_match, and with nlevels == 1 the outputs
+ * are rfe_stereo_match's bit for bit.
+ * levelsL / levelsR: ONE view's level images each, exactly the `levels` output of rfe_extract_pyramid_u8[_dev] ([sum_l H_l*W_l] u8,
+ * level 0 first, tight pitch; with B = 2 the second view starts sum_l H_l*W_l bytes after the first).  The library recomputes the
+ * geometry from (H, W, nlevels, scale_factor) as rfe_pyramid_geometry does; the caller passes no tables.
+ * kL/kR: [N,2]/[Nr,2] f32 level-0 pixels, octL/octR: [N]/[Nr] i32, dL/dR: [N,256]/[Nr,256]; uRight / depth: [N], -1 = no match.
+ * sad_source: which image the 11x11 patches come from.  ORB-SLAM3 reads mvImagePyramid[kpL.octave]; Rover-SLAM commented that out
+ * (src/Frame.cc:1315, :1341) and reads level 0 at the level-scaled coordinates, a different place for octave > 0 (DESIGN.md 6c has
+ * the comparison).  Both are offered; the bounds checks use the size of the image that is read.
+ * Refused (RFE_ERR_INVALID): geometry arguments rfe_pyramid_geometry refuses; a sad_source other than the two; N or Nr outside 0..4096
+ * (the outlier cut sorts in one workgroup); mb <= 0; a NULL required pointer; host entry only: an octave outside [0, nlevels).  The
+ * _dev entry cannot read the octaves without a synchronisation: there, a left keypoint with such an octave gets no match and a right
+ * one is never a candidate. */
+#define RFE_STEREO_SAD_LEVEL  0   /* patches from pyramid level kpL.octave (ORB-SLAM3; default) */
+#define RFE_STEREO_SAD_LEVEL0 1   /* patches from level 0 at level-scaled coordinates (Rover-SLAM src/Frame.cc:1318,1356 as written) */
+int rfe_stereo_match_pyramid(rfe_ctx* ctx, const uint8_t* levelsL, const uint8_t* levelsR, int H, int W, int nlevels, float scale_factor,
+                             const float* kL, const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr,
+                             const float* dL, const float* dR, float mb, float mbf, int sad_source, float* uRight, float* depth);
+/* the same with device pointers, asynchronous on the ctx stream */
+int rfe_stereo_match_pyramid_dev(rfe_ctx* ctx, const uint8_t* levelsL, const uint8_t* levelsR, int H, int W, int nlevels, float scale_factor,
+                                 const float* kL, const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr,
+                                 const float* dL, const float* dR, float mb, float mbf, int sad_source, float* uRight, float* depth);
+/* rfe_stereo_frame_dev for pyramids, ONE device-resident call per stereo frame: both views through the pyramid extraction as one
+ * batch of 2 (rfe_extract_pyramid_u8_dev's outputs: n [2], level_n [2,nlevels] or NULL, kpts [2,Ktot,2], octave [2,Ktot],
+ * score [2,Ktot], desc [2,Ktot,256]), the octave-aware stereo match on the device-resident merged features (uRight / depth [Ktot],
+ * entries >= n[0] are -1), and one LightGlue match of THIS left view (set 0) against the PREVIOUS left view (set 1) on
+ * NormalizeKeypoints of the float level-0 keypoints with the true image size (S [1], pairs [Ktot,2], ms [Ktot]).
+ * kmax: HOST array [nlevels], Ktot = sum <= 4096.  reset != 0, a change of H, W, nlevels, scale_factor or any kmax[l], or an
+ * rfe_stereo_frame_dev call on the same ctx in between, starts a new sequence (S = 0): the two entries never match against each
+ * other's stored view.  No host synchronisation and no host read of device data after the first call of a shape;
+ * RFE_OPT_HOST_GRAPH does not apply.  Refusals: those of rfe_extract_pyramid_u8_dev and rfe_stereo_match_pyramid, Ktot > 4096. */
+int rfe_stereo_frame_pyramid_dev(rfe_ctx* ctx, const uint8_t* imgL_dev, const uint8_t* imgR_dev, int H, int W, int stride,
+                                 int nlevels, float scale_factor, const int32_t* kmax, float thr, float filter_thr, float mb, float mbf,
+                                 int sad_source, int reset, int32_t* n_dev, int32_t* level_n_dev, float* kpts_dev, int32_t* octave_dev,
+                                 float* score_dev, float* desc_dev, float* uRight_dev, float* depth_dev, int32_t* S_dev,
+                                 int32_t* pairs_dev, float* ms_dev);
 
 /* ---- descriptor helpers for the callers' classic searches, host pointers (device forms below) ----
  * rfe_l2_distance_matrix: out[i*N + j] = SPmatcher::DescriptorDistance_sp(a_i, b_j)

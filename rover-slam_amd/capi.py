@@ -20,7 +20,8 @@ EXPORTS = [
     "rfe_weight_count", "rfe_weights_id", "rfe_get_hparams", "rfe_set_hparams", "rfe_set_option", "rfe_get_option", "rfe_set_stream", "rfe_synchronize", "rfe_malloc", "rfe_free", "rfe_host_malloc", "rfe_host_free", "rfe_workspace_bytes", "rfe_memcpy_h2d",
     "rfe_memcpy_d2h", "rfe_extract_u8", "rfe_extract_u8_dev", "rfe_extract_f32", "rfe_extract_f32_dev", "rfe_extract_u8_bin", "rfe_extract_u8_bin_dev",
     "rfe_pyramid_geometry", "rfe_extract_pyramid_u8", "rfe_extract_pyramid_u8_dev", "rfe_match", "rfe_match_dev", "rfe_match_fused",
-    "rfe_extract_match_stream_dev", "rfe_stereo_match", "rfe_stereo_match_dev", "rfe_stereo_frame_dev", "rfe_l2_distance_matrix", "rfe_binarize_descriptors",
+    "rfe_extract_match_stream_dev", "rfe_stereo_match", "rfe_stereo_match_dev", "rfe_stereo_frame_dev", "rfe_stereo_match_pyramid", "rfe_stereo_match_pyramid_dev", "rfe_stereo_frame_pyramid_dev",
+    "rfe_l2_distance_matrix", "rfe_binarize_descriptors",
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
@@ -93,6 +94,12 @@ lib.rfe_stereo_match.argtypes = _st
 lib.rfe_stereo_match_dev.argtypes = _st
 lib.rfe_stereo_frame_dev.argtypes = [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_int, _ip, _ip, _fp, _fp, _fp, _fp, _ip, _ip, _fp]
+_stp = [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _ip, C.c_int, _fp, _ip, C.c_int, _fp, _fp, C.c_float, C.c_float,
+        C.c_int, _fp, _fp]
+lib.rfe_stereo_match_pyramid.argtypes = _stp
+lib.rfe_stereo_match_pyramid_dev.argtypes = _stp
+lib.rfe_stereo_frame_pyramid_dev.argtypes = [C.c_void_p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _ip, C.c_float, C.c_float,
+                                             C.c_float, C.c_float, C.c_int, C.c_int, _ip, _ip, _fp, _ip, _fp, _fp, _fp, _fp, _ip, _ip, _fp]
 lib.rfe_l2_distance_matrix.argtypes = [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _fp]
 lib.rfe_binarize_descriptors.argtypes = [C.c_void_p, _fp, C.c_int, _u8p]
 lib.rfe_search_candidates.argtypes = [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _ip, _ip, _u8p, _ip, _fp, _fp]
@@ -217,6 +224,46 @@ class StereoStream:
                                                self.thr, self.filter_thr, self.mb, self.mbf, int(reset or self.first), b["n"].ptr,
                                                b["kxy"].ptr, b["score"].ptr, b["desc"].ptr, b["u_right"].ptr, b["depth"].ptr,
                                                b["S"].ptr, b["pairs"].ptr, b["ms"].ptr))
+        self.first = False
+
+    def results(self):
+        self.ctx.synchronize()
+        out = {name: self.bufs[name].download(shape, dt) for name, dt, shape in self._spec}
+        out["S"] = int(out["S"][0])
+        return out
+
+    def close(self):
+        for b in self.bufs.values():
+            b.free()
+        self.bufs = {}
+
+
+STEREO_SAD_LEVEL, STEREO_SAD_LEVEL0 = 0, 1   # include/rover_fe.h: RFE_STEREO_SAD_*
+
+
+class StereoPyramidStream:
+    """StereoStream for scale pyramids (rfe_stereo_frame_pyramid_dev): kmax is one budget per level (or an int for every level)."""
+
+    def __init__(self, ctx, H, W, nlevels=8, scale_factor=1.2, kmax=128, mb=0.11, mbf=0.11 * 435.0, thr=0.0005, filter_thr=0.1,
+                 sad_source=STEREO_SAD_LEVEL):
+        self.ctx, self.H, self.W, self.L, self.sf = ctx, H, W, int(nlevels), scale_factor
+        self.kmax = np.full((max(self.L, 1),), int(kmax), np.int32) if np.isscalar(kmax) else np.ascontiguousarray(kmax, np.int32)
+        self.mb, self.mbf, self.thr, self.filter_thr, self.sad_source = mb, mbf, thr, filter_thr, sad_source
+        K = self.K = int(self.kmax.sum())
+        self._spec = [("n", np.int32, (2,)), ("level_n", np.int32, (2, max(self.L, 1))), ("kpts", np.float32, (2, K, 2)),
+                      ("octave", np.int32, (2, K)), ("score", np.float32, (2, K)), ("desc", np.float32, (2, K, 256)),
+                      ("u_right", np.float32, (K,)), ("depth", np.float32, (K,)), ("S", np.int32, (1,)), ("pairs", np.int32, (K, 2)),
+                      ("ms", np.float32, (K,))]
+        self.bufs = {name: ctx.alloc(max(int(np.prod(shape)), 1) * np.dtype(dt).itemsize) for name, dt, shape in self._spec}
+        self.first = True
+
+    def push(self, img_l_dev, img_r_dev, stride=None, reset=False):
+        b = self.bufs
+        self.ctx._chk(lib.rfe_stereo_frame_pyramid_dev(self.ctx.h, _addr(img_l_dev), _addr(img_r_dev), self.H, self.W, stride or self.W, self.L,
+                                                       self.sf, self.kmax.ctypes.data, self.thr, self.filter_thr, self.mb, self.mbf,
+                                                       self.sad_source, int(reset or self.first), b["n"].ptr, b["level_n"].ptr, b["kpts"].ptr,
+                                                       b["octave"].ptr, b["score"].ptr, b["desc"].ptr, b["u_right"].ptr, b["depth"].ptr,
+                                                       b["S"].ptr, b["pairs"].ptr, b["ms"].ptr))
         self.first = False
 
     def results(self):
@@ -502,6 +549,29 @@ class Context:
         u = np.full((max(N, 1),), -1, np.float32); z = np.full((max(N, 1),), -1, np.float32)
         self._chk(lib.rfe_stereo_match(self.h, il.ctypes.data, ir.ctypes.data, H, W, W, kl.ctypes.data, N, kr.ctypes.data, Nr,
                                        dl.ctypes.data, dr.ctypes.data, mb, mbf, u.ctypes.data, z.ctypes.data))
+        return u[:N], z[:N]
+
+    def stereo_match_pyramid(self, levels_l, levels_r, H, W, nlevels, scale_factor, k_l, oct_l, k_r, oct_r, d_l, d_r, mb, mbf, sad_source=0):
+        """Octave-aware Frame::ComputeStereoMatches (rfe_stereo_match_pyramid) on host arrays.  levels_l / levels_r: one view's level
+        images, either the flat [sum_l H_l*W_l] u8 buffer or a list of [H_l,W_l] arrays, level 0 first; returns (uRight[N], depth[N])."""
+        def flat(lv):
+            if isinstance(lv, (list, tuple)):
+                return np.concatenate([np.ascontiguousarray(a, np.uint8).reshape(-1) for a in lv])
+            return np.ascontiguousarray(lv, np.uint8).reshape(-1)
+        vl, vr = flat(levels_l), flat(levels_r)
+        lh, lw, _ = pyramid_geometry(H, W, nlevels, scale_factor)
+        need = int((lh.astype(np.int64) * lw).sum())
+        if vl.size != need or vr.size != need:
+            raise RfeError(f"stereo_match_pyramid: level buffers hold {vl.size} / {vr.size} bytes, the geometry needs {need}")
+        kl = np.ascontiguousarray(k_l, np.float32).reshape(-1, 2); kr = np.ascontiguousarray(k_r, np.float32).reshape(-1, 2)
+        ol = np.ascontiguousarray(oct_l, np.int32).reshape(-1); orr = np.ascontiguousarray(oct_r, np.int32).reshape(-1)
+        dl = np.ascontiguousarray(d_l, np.float32).reshape(-1, 256); dr = np.ascontiguousarray(d_r, np.float32).reshape(-1, 256)
+        N, Nr = kl.shape[0], kr.shape[0]
+        assert ol.shape[0] == N and orr.shape[0] == Nr and dl.shape[0] == N and dr.shape[0] == Nr
+        u = np.full((max(N, 1),), -1, np.float32); z = np.full((max(N, 1),), -1, np.float32)
+        self._chk(lib.rfe_stereo_match_pyramid(self.h, vl.ctypes.data, vr.ctypes.data, H, W, nlevels, scale_factor, kl.ctypes.data,
+                                               ol.ctypes.data, N, kr.ctypes.data, orr.ctypes.data, Nr, dl.ctypes.data, dr.ctypes.data,
+                                               mb, mbf, sad_source, u.ctypes.data, z.ctypes.data))
         return u[:N], z[:N]
 
     def search_candidates(self, q, f, offsets, cand, skip=None):

@@ -981,8 +981,10 @@ int pyr_prepare(rfe_ctx* c, int H, int W, int B, float sf, const PyrPlan& P, boo
 }
 
 // img: level 0 (caller's pitch); lv: the level buffer [B, P.frame] (caller's or ws_pyr's); outputs device pointers
+// img_frame: bytes from frame b to b + 1 of img (0 = stride * H)
 int pyr_forward(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, const PyrPlan& P, float thr, uint8_t* lv, bool copy_level0,
-                int32_t* n, int32_t* level_n, float* kpts, int32_t* octave, float* score, float* desc) {
+                int32_t* n, int32_t* level_n, float* kpts, int32_t* octave, float* score, float* desc, long long img_frame = 0) {
+    if (img_frame == 0) img_frame = (long long)stride * H;
     hipStream_t s = c->stream;
     // the level chain runs on the side stream, concurrently with level 0's backbone; with events around every stage (full profiling
     // pass) it runs at the front of the main stream, so that the stage times stay clean
@@ -990,11 +992,11 @@ int pyr_forward(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B,
     hipStream_t sc = side ? c->side_stream : s;
     if (side) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(sc, c->ev_fork, 0)); }
     { ProfScope p(c, "sp_pyramid", sc);
-      if (copy_level0) launch_pyr_resample(sc, img, (long long)stride * H, stride, H, W, lv, (long long)P.frame, H, W, B, nullptr, nullptr);
+      if (copy_level0) launch_pyr_resample(sc, img, img_frame, stride, H, W, lv, (long long)P.frame, H, W, B, nullptr, nullptr);
       const int2* tab = (const int2*)c->ws_ptab;
       for (int l = 1; l < P.L; ++l) {
           const uint8_t* src = l == 1 ? img : lv + P.off[l - 1];
-          const long long src_frame = l == 1 ? (long long)stride * H : (long long)P.frame;
+          const long long src_frame = l == 1 ? img_frame : (long long)P.frame;
           const int src_stride = l == 1 ? stride : P.w[l - 1];
           launch_pyr_resample(sc, src, src_frame, src_stride, P.h[l - 1], P.w[l - 1], lv + P.off[l], (long long)P.frame, P.h[l], P.w[l], B,
                               tab + c->ptab_off[l], tab + c->ptab_off[l] + P.w[l]);
@@ -1013,7 +1015,7 @@ int pyr_forward(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B,
         int32_t* ln = a.take<int32_t>((size_t)B); int32_t* lk = a.take<int32_t>((size_t)B * P.kmax[l] * 2);
         float* ls = a.take<float>((size_t)B * P.kmax[l]); float* ld = a.take<float>((size_t)B * P.kmax[l] * 256);
         if (l >= 1 && !joined) { RFE_HIP(c, hipStreamWaitEvent(s, c->ev_pyr, 0)); joined = true; }   // levels >= 1 read the chain's output
-        if (l == 0) rc = sp_forward(c, img, H, W, stride, B, P.kmax[0], thr, ln, lk, ls, ld);
+        if (l == 0) rc = sp_forward(c, img, H, W, stride, B, P.kmax[0], thr, ln, lk, ls, ld, nullptr, false, img_frame);
         else rc = sp_forward(c, lv + P.off[l], P.h[l], P.w[l], P.w[l], B, P.kmax[l], thr, ln, lk, ls, ld, nullptr, false, (long long)P.frame);
         if (rc) return rc;
         m.n[l] = ln; m.kxy[l] = lk; m.sc[l] = ls; m.desc_l[l] = ld;
@@ -1497,11 +1499,13 @@ __global__ void st_zero_count_kernel(int32_t* S) { S[0] = 0; }
 //           the state slot that becomes "previous" for the next frame (two slots, flipped per frame: nothing is copied after the match);
 //   side 1: the stored normalised keypoint / descriptor of the previous view -> x, csn;
 // workgroup 0: clamped lengths, cross-attention map, the next slot's keypoint count.  have_prev = 0 (first frame of a stream): side 1 is zero-filled, length 0.
-__global__ __launch_bounds__(256) void st_stage_kernel(const int32_t* __restrict__ kxy, const float* __restrict__ desc, const int32_t* __restrict__ n, int Kmax, int L,
-                                                       float sx, float sy, float scale, const float* __restrict__ kn_prev, const float* __restrict__ desc_prev,
-                                                       const int32_t* __restrict__ n_prev, int have_prev, const float* __restrict__ wr, float* __restrict__ x,
-                                                       float* __restrict__ kn, float2* __restrict__ csn, int32_t* __restrict__ lens, int32_t* __restrict__ kvmap,
-                                                       float* __restrict__ kn_next, float* __restrict__ desc_next, int32_t* __restrict__ n_next) {
+// KT: int32 (rfe_stereo_frame_dev: the extractor's integer pixels) or float (rfe_stereo_frame_pyramid_dev: level-0 coordinates of the merged levels)
+template <typename KT>
+__device__ __forceinline__ void st_stage_body(const KT* __restrict__ kxy, const float* __restrict__ desc, const int32_t* __restrict__ n, int Kmax, int L,
+                                              float sx, float sy, float scale, const float* __restrict__ kn_prev, const float* __restrict__ desc_prev,
+                                              const int32_t* __restrict__ n_prev, int have_prev, const float* __restrict__ wr, float* __restrict__ x,
+                                              float* __restrict__ kn, float2* __restrict__ csn, int32_t* __restrict__ lens, int32_t* __restrict__ kvmap,
+                                              float* __restrict__ kn_next, float* __restrict__ desc_next, int32_t* __restrict__ n_next) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         int v0 = n[0]; v0 = v0 < 0 ? 0 : (v0 > Kmax ? Kmax : v0);
         int v1 = have_prev ? n_prev[0] : 0; v1 = v1 < 0 ? 0 : (v1 > Kmax ? Kmax : v1);
@@ -1532,6 +1536,20 @@ __global__ __launch_bounds__(256) void st_stage_kernel(const int32_t* __restrict
         csn[(size_t)row * 32 + lane] = make_float2(cosf(th), sinf(th));
     }
 }
+__global__ __launch_bounds__(256) void st_stage_kernel(const int32_t* __restrict__ kxy, const float* __restrict__ desc, const int32_t* __restrict__ n, int Kmax, int L,
+                                                       float sx, float sy, float scale, const float* __restrict__ kn_prev, const float* __restrict__ desc_prev,
+                                                       const int32_t* __restrict__ n_prev, int have_prev, const float* __restrict__ wr, float* __restrict__ x,
+                                                       float* __restrict__ kn, float2* __restrict__ csn, int32_t* __restrict__ lens, int32_t* __restrict__ kvmap,
+                                                       float* __restrict__ kn_next, float* __restrict__ desc_next, int32_t* __restrict__ n_next) {
+    st_stage_body<int32_t>(kxy, desc, n, Kmax, L, sx, sy, scale, kn_prev, desc_prev, n_prev, have_prev, wr, x, kn, csn, lens, kvmap, kn_next, desc_next, n_next);
+}
+__global__ __launch_bounds__(256) void st_stage_f32_kernel(const float* __restrict__ kpts, const float* __restrict__ desc, const int32_t* __restrict__ n, int Kmax, int L,
+                                                           float sx, float sy, float scale, const float* __restrict__ kn_prev, const float* __restrict__ desc_prev,
+                                                           const int32_t* __restrict__ n_prev, int have_prev, const float* __restrict__ wr, float* __restrict__ x,
+                                                           float* __restrict__ kn, float2* __restrict__ csn, int32_t* __restrict__ lens, int32_t* __restrict__ kvmap,
+                                                           float* __restrict__ kn_next, float* __restrict__ desc_next, int32_t* __restrict__ n_next) {
+    st_stage_body<float>(kpts, desc, n, Kmax, L, sx, sy, scale, kn_prev, desc_prev, n_prev, have_prev, wr, x, kn, csn, lens, kvmap, kn_next, desc_next, n_next);
+}
 
 extern "C" int rfe_stereo_frame_dev(rfe_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int H, int W, int stride, int Kmax,
                                     float thr, float filter_thr, float mb, float mbf, int reset, int32_t* n, int32_t* kxy,
@@ -1547,9 +1565,9 @@ extern "C" int rfe_stereo_frame_dev(rfe_ctx* c, const uint8_t* imgL, const uint8
     // state: sadv [Kmax] | two slots of { kn [Kmax,2], desc [Kmax,256], n [1] }: the previous left
     // view lives in slot st_flip, this frame's staging kernel fills the other one, then the slots swap -- nothing is copied behind the match
     const size_t b_sad = al((size_t)Kmax * 4), b_kn = al((size_t)Kmax * 8), b_desc = al((size_t)Kmax * 1024), b_n = al(4);
-    const bool fresh = c->st_H != H || c->st_W != W || c->st_K != Kmax;
+    const bool fresh = c->st_H != H || c->st_W != W || c->st_K != Kmax || !c->st_pyr_key.empty();   // st_pyr_key: the stored view is rfe_stereo_frame_pyramid_dev's
     if ((rc = ensure_ws(c, &c->ws_st, &c->ws_st_bytes, b_sad + 2 * (b_kn + b_desc + b_n) + 256))) return rc;
-    if (fresh || reset) { c->st_have_prev = false; c->st_H = H; c->st_W = W; c->st_K = Kmax; }
+    if (fresh || reset) { c->st_have_prev = false; c->st_H = H; c->st_W = W; c->st_K = Kmax; c->st_pyr_key.clear(); }
     char* p = (char*)c->ws_st;
     int32_t* sadv = (int32_t*)p; p += b_sad;
     float* kn_slot[2]; float* desc_slot[2]; int32_t* n_slot[2];
@@ -1598,6 +1616,162 @@ extern "C" int rfe_stereo_frame_dev(rfe_ctx* c, const uint8_t* imgL, const uint8
     }
     c->st_flip = next;
     if (st_fork) { join_guard.on = false; RFE_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0)); }   // uRight / depth are complete when the ctx stream is
+    c->st_have_prev = true;
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+// =====================================================================================
+// octave-aware sparse stereo matching: Frame::ComputeStereoMatches for keypoints of a scale pyramid
+// =====================================================================================
+namespace {
+
+// validation shared by the three entries + the kernel's level table; frame = sum_l H_l * W_l
+int stereo_pyr_table(rfe_ctx* c, int H, int W, int L, float sf, int sad_source, float mb, StereoPyrTable& T, size_t& frame) {
+    int32_t h[RFE_MAX_LEVELS], w[RFE_MAX_LEVELS]; float sc[RFE_MAX_LEVELS];
+    if (pyramid_geometry(H, W, L, sf, h, w, sc) != RFE_OK)
+        return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: H, W >= 8, nlevels in 1..16, scale_factor in (1, 4] when nlevels > 1, no level of zero pixels");
+    if (sad_source != RFE_STEREO_SAD_LEVEL && sad_source != RFE_STEREO_SAD_LEVEL0)
+        return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: sad_source must be RFE_STEREO_SAD_LEVEL or RFE_STEREO_SAD_LEVEL0");
+    if (!(mb > 0.f)) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: mb must be positive");
+    memset(&T, 0, sizeof(T));
+    T.L = L; frame = 0;
+    for (int l = 0; l < L; ++l) {
+        T.h[l] = h[l]; T.w[l] = w[l]; T.off[l] = (uint32_t)frame; T.s[l] = sc[l]; T.inv[l] = 1.0f / sc[l];
+        frame += (size_t)h[l] * w[l];
+    }
+    if (frame > 0x7fffffffull) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: level buffer above 2 GiB");
+    return RFE_OK;
+}
+
+}  // namespace
+
+extern "C" int rfe_stereo_match_pyramid_dev(rfe_ctx* c, const uint8_t* levelsL, const uint8_t* levelsR, int H, int W, int nlevels, float scale_factor,
+                                            const float* kL, const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr,
+                                            const float* dL, const float* dR, float mb, float mbf, int sad_source, float* uRight, float* depth) {
+    if (!c) return RFE_ERR_INVALID;
+    StereoPyrTable T; size_t frame;
+    int rc = stereo_pyr_table(c, H, W, nlevels, scale_factor, sad_source, mb, T, frame);
+    if (rc) return rc;
+    if (N < 0 || Nr < 0 || N > 4096 || Nr > 4096) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: N and Nr must be in 0..4096");
+    if (N == 0) return RFE_OK;
+    if (!levelsL || !levelsR || !kL || !octL || !dL || !uRight || !depth || (Nr > 0 && (!kR || !octR || !dR)))
+        return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_ws(c, &c->ws_tmp, &c->ws_tmp_bytes, al((size_t)N * 4)))) return rc;
+    ProfScope p(c, "stereo_match");
+    launch_stereo_match_pyr(c->stream, levelsL, levelsR, T, kL, octL, N, kR, octR, Nr, nullptr, dL, dR, mb, mbf, sad_source == RFE_STEREO_SAD_LEVEL0,
+                            uRight, depth, (int32_t*)c->ws_tmp);
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_stereo_match_pyramid(rfe_ctx* c, const uint8_t* levelsL, const uint8_t* levelsR, int H, int W, int nlevels, float scale_factor,
+                                        const float* kL, const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr,
+                                        const float* dL, const float* dR, float mb, float mbf, int sad_source, float* uRight, float* depth) {
+    if (!c) return RFE_ERR_INVALID;
+    StereoPyrTable T; size_t frame;
+    int rc = stereo_pyr_table(c, H, W, nlevels, scale_factor, sad_source, mb, T, frame);
+    if (rc) return rc;
+    if (N < 0 || Nr < 0 || N > 4096 || Nr > 4096) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: N and Nr must be in 0..4096");
+    if (N == 0) return RFE_OK;
+    if (!levelsL || !levelsR || !kL || !octL || !dL || !uRight || !depth || (Nr > 0 && (!kR || !octR || !dR)))
+        return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: null pointer");
+    // the kernel treats an octave outside [0, nlevels) as "no match / not a candidate"; here the arrays are readable, so it is refused
+    for (int i = 0; i < N; ++i) if (octL[i] < 0 || octL[i] >= nlevels) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: left octave outside [0, nlevels)");
+    for (int i = 0; i < Nr; ++i) if (octR[i] < 0 || octR[i] >= nlevels) return fail(c, RFE_ERR_INVALID, "stereo_match_pyramid: right octave outside [0, nlevels)");
+    RFE_HIP(c, hipSetDevice(c->device));
+    const int Nr1 = std::max(Nr, 1);
+    const size_t bi = al(frame), bkl = al((size_t)N * 8), bkr = al((size_t)Nr1 * 8), bol = al((size_t)N * 4), bor = al((size_t)Nr1 * 4),
+                 bdl = al((size_t)N * 1024), bdr = al((size_t)Nr1 * 1024), bo = al((size_t)N * 4);
+    if ((rc = ensure_ws(c, &c->ws_io, &c->ws_io_bytes, 2 * bi + bkl + bkr + bol + bor + bdl + bdr + 2 * bo))) return rc;
+    char* p = (char*)c->ws_io;
+    uint8_t* dVL = (uint8_t*)p; p += bi; uint8_t* dVR = (uint8_t*)p; p += bi;
+    float* dkl = (float*)p; p += bkl; float* dkr = (float*)p; p += bkr; int32_t* dol = (int32_t*)p; p += bol; int32_t* dor = (int32_t*)p; p += bor;
+    float* ddl = (float*)p; p += bdl; float* ddr = (float*)p; p += bdr; float* du = (float*)p; p += bo; float* dz = (float*)p;
+    hipStream_t s = c->stream;
+    RFE_HIP(c, hipMemcpyAsync(dVL, levelsL, frame, hipMemcpyHostToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(dVR, levelsR, frame, hipMemcpyHostToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(dkl, kL, (size_t)N * 8, hipMemcpyHostToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(dol, octL, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(ddl, dL, (size_t)N * 1024, hipMemcpyHostToDevice, s));
+    if (Nr > 0) {
+        RFE_HIP(c, hipMemcpyAsync(dkr, kR, (size_t)Nr * 8, hipMemcpyHostToDevice, s));
+        RFE_HIP(c, hipMemcpyAsync(dor, octR, (size_t)Nr * 4, hipMemcpyHostToDevice, s));
+        RFE_HIP(c, hipMemcpyAsync(ddr, dR, (size_t)Nr * 1024, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = rfe_stereo_match_pyramid_dev(c, dVL, dVR, H, W, nlevels, scale_factor, dkl, dol, N, dkr, dor, Nr, ddl, ddr, mb, mbf, sad_source, du, dz))) return rc;
+    RFE_HIP(c, hipMemcpyAsync(uRight, du, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    RFE_HIP(c, hipMemcpyAsync(depth, dz, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    RFE_HIP(c, hipStreamSynchronize(s));
+    prof_collect(c);
+    return RFE_OK;
+}
+
+// rfe_stereo_frame_dev for pyramids: the same three stages, with pyr_forward in place of sp_forward, the octave-aware stereo kernels and the
+// float-keypoint staging kernel.  The previous-view state lives in the same ws_st slots; st_pyr_key names the shape it was stored under.
+extern "C" int rfe_stereo_frame_pyramid_dev(rfe_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int H, int W, int stride, int nlevels,
+                                            float scale_factor, const int32_t* kmax, float thr, float filter_thr, float mb, float mbf,
+                                            int sad_source, int reset, int32_t* n, int32_t* level_n, float* kpts, int32_t* octave,
+                                            float* score, float* desc, float* uRight, float* depth, int32_t* S, int32_t* pairs, float* ms) {
+    PyrPlan P;
+    int rc = pyr_check(c, H, W, stride, 2, nlevels, scale_factor, kmax, P);
+    if (rc) return rc;
+    if (P.Ktot > 4096) return fail(c, RFE_ERR_INVALID, "stereo_frame_pyramid: the sum of kmax must be at most 4096");
+    const int K = P.Ktot;
+    if ((rc = lg_check(c, 1, K, K))) return rc;
+    StereoPyrTable T; size_t frame;
+    if ((rc = stereo_pyr_table(c, H, W, nlevels, scale_factor, sad_source, mb, T, frame))) return rc;
+    if (!imgL || !imgR || !n || !kpts || !octave || !score || !desc || !uRight || !depth || !S || !pairs || !ms)
+        return fail(c, RFE_ERR_INVALID, "stereo_frame_pyramid: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t b_sad = al((size_t)K * 4), b_kn = al((size_t)K * 8), b_desc = al((size_t)K * 1024), b_n = al(4);
+    int sf_bits; memcpy(&sf_bits, &scale_factor, 4);
+    std::string key = std::to_string(H) + "x" + std::to_string(W) + "|" + std::to_string(nlevels) + "|" + std::to_string(nlevels > 1 ? sf_bits : 0);
+    for (int l = 0; l < nlevels; ++l) key += "," + std::to_string(kmax[l]);
+    const bool fresh = c->st_pyr_key != key;
+    const int L = ((K + 3) / 4) * 4;
+    // every allocation before the first kernel of the call (ensure_ws synchronises the ctx stream only; the side stream is idle between calls)
+    if ((rc = ensure_ws(c, &c->ws_st, &c->ws_st_bytes, b_sad + 2 * (b_kn + b_desc + b_n) + 256))) return rc;
+    if ((rc = ensure_ws(c, &c->ws_lg, &c->ws_lg_bytes, lg_ws_bytes(1, L)))) return rc;
+    if ((rc = pyr_prepare(c, H, W, 2, scale_factor, P, true))) return rc;
+    if (fresh || reset) { c->st_have_prev = false; c->st_H = H; c->st_W = W; c->st_K = K; c->st_pyr_key = key; }
+    char* p = (char*)c->ws_st;
+    int32_t* sadv = (int32_t*)p; p += b_sad;
+    float* kn_slot[2]; float* desc_slot[2]; int32_t* n_slot[2];
+    for (int q = 0; q < 2; ++q) { kn_slot[q] = (float*)p; p += b_kn; desc_slot[q] = (float*)p; p += b_desc; n_slot[q] = (int32_t*)p; p += b_n; }
+    const int prev = c->st_flip & 1, next = prev ^ 1;
+    // both views as one batch of 2, read where the caller has them (frame distance imgR - imgL); every level image, level 0 included, is
+    // kept in ws_pyr for the SAD refinement: view b's levels at lv + b * frame
+    uint8_t* lv = (uint8_t*)c->ws_pyr;
+    if ((rc = pyr_forward(c, imgL, H, W, stride, 2, P, thr, lv, true, n, level_n, kpts, octave, score, desc, (long long)(imgR - imgL)))) return rc;
+    // the stereo kernels on the side stream next to the temporal match, joined on every exit path, as in rfe_stereo_frame_dev
+    const bool st_fork = c->st_have_prev && !(c->prof && c->prof_filter.empty());
+    hipStream_t ss = st_fork ? c->side_stream : s;
+    if (st_fork) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(ss, c->ev_fork, 0)); }
+    { ProfScope ps(c, "stereo_match", ss);
+      launch_stereo_match_pyr(ss, lv, lv + frame, T, kpts, octave, K, kpts + (size_t)K * 2, octave + K, K, n, desc, desc + (size_t)K * 256, mb, mbf,
+                              sad_source == RFE_STEREO_SAD_LEVEL0, uRight, depth, sadv); }
+    if (st_fork) RFE_HIP(c, hipEventRecord(c->ev_join, ss));
+    struct JoinGuard { rfe_ctx* c; hipStream_t s; bool on; ~JoinGuard() { if (on) (void)hipStreamWaitEvent(s, c->ev_join, 0); } } join_guard{c, s, st_fork};
+    // temporal match: THIS left view (set 0) against the previous left view (set 1), true image size, NormalizeKeypoints of the float keypoints
+    {
+        LgBuffers b;
+        lg_carve(c->ws_lg, 1, L, b);
+        const float sx = (float)W / 2, sy = (float)H / 2, scale = (float)(H > W ? H : W) / 2;
+        { ProfScope ps(c, "lg_misc");
+          hipLaunchKernelGGL(st_stage_f32_kernel, dim3((unsigned)((2 * L + 3) / 4)), dim3(256), 0, s, kpts, desc, n, K, L, sx, sy, scale, kn_slot[prev], desc_slot[prev],
+                             n_slot[prev], c->st_have_prev ? 1 : 0, c->lg.wr, b.x, b.kn, reinterpret_cast<float2*>(b.csn), b.lens, b.kvmap, kn_slot[next], desc_slot[next],
+                             n_slot[next]); }
+        if (c->st_have_prev) {
+            if ((rc = lg_forward(c, b, 1, L, filter_thr, K, S, pairs, ms, nullptr, false, true))) return rc;
+        } else {
+            hipLaunchKernelGGL(st_zero_count_kernel, dim3(1), dim3(1), 0, s, S);
+        }
+    }
+    c->st_flip = next;
+    if (st_fork) { join_guard.on = false; RFE_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0)); }
     c->st_have_prev = true;
     RFE_HIP(c, hipGetLastError());
     return RFE_OK;

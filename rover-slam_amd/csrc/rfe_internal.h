@@ -135,7 +135,7 @@ struct rfe_ctx {
     int32_t* sp_cnt = nullptr;           // [4][2] (count, tickets) of the fused detector tail (sp_post.hip: sp_tail_lat_kernel); zero between calls
     bool sp_cnt_dirty = false;           // the tail ran and its ranking kernel was not enqueued behind it (an error in between): zeroed before the next use
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
-    int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0;   // st_flip: which of the two state slots holds the previous left view
+    int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
     // copies the final token states / log-assignment matrix of one pair to these device buffers
     struct { bool armed = false; int pair = 0; float *x0 = nullptr, *x1 = nullptr, *scores = nullptr; } tap;
@@ -285,6 +285,19 @@ struct PyrMergeArgs {
     int32_t* n_out; int32_t* level_n /*optional [B, L]*/; float* kpts; int32_t* octave; float* score; float* desc;
 };
 void launch_pyr_merge(hipStream_t s, const PyrMergeArgs& a, int B);
+
+// level table of the octave-aware stereo match (by-value kernel argument): level l is h[l] x w[l] at byte off[l] of one view's level
+// buffer, s[l] = mvScaleFactors[l], inv[l] = 1.0f / s[l]
+struct StereoPyrTable {
+    int L;
+    int32_t h[RFE_MAX_LEVELS], w[RFE_MAX_LEVELS];
+    uint32_t off[RFE_MAX_LEVELS];
+    float s[RFE_MAX_LEVELS], inv[RFE_MAX_LEVELS];
+};
+void launch_stereo_match_pyr(hipStream_t s, const uint8_t* levL, const uint8_t* levR, const StereoPyrTable& T, const float* kL,
+                             const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr, const int32_t* counts,
+                             const float* dL, const float* dR, float mb, float mbf, int sad_level0, float* uRight, float* depth,
+                             int32_t* sadv);
 
 void launch_l2_matrix(hipStream_t s, const float* a, int M, const float* b, int N, float* out);
 void launch_binarize(hipStream_t s, const float* d, int64_t rows, uint8_t* out);

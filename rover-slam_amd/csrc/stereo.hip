@@ -1,7 +1,7 @@
 // stereo.hip -- sparse stereo matching on the extracted features: Frame::ComputeStereoMatches of the
 // reference (src/Frame.cc:1159-1446), which runs right after the two extractor calls on every stereo frame
 // (src/Frame.cc:142-171).  SURVEY.md section 8(f) row N2.  nLevels == 1 only (octave 0, scale 1), like the
-// SuperPoint path itself.
+// SuperPoint path itself; the octave-aware form for scale-pyramid keypoints is stereo_match_pyr_kernel below.
 //   kernel 1 (one wave per left keypoint): row-band (+-2 px) / disparity-range candidate scan over the right
 //     keypoints, 256-d L2 distance (DescriptorDistance_sp, src/Matchers/SPmatcher.cc:2184) -- float
 //     differences, double accumulation in a fixed lane/butterfly order shared with the oracle --, best
@@ -169,6 +169,122 @@ void launch_stereo_match_counts(hipStream_t s, const uint8_t* imgL, const uint8_
     int P2 = 1;
     while (P2 < Kmax) P2 <<= 1;
     hipLaunchKernelGGL(stereo_filter_kernel, dim3(1), dim3(1024), (size_t)P2 * 8, s, Kmax, P2, counts, sadv, uRight, depth);
+}
+
+// ------------------------------------------------------------------------------------------
+// Octave-aware form: keypoints of an RFE_SP_PYRAMID extraction -- level-0 coordinates + octave.  The four places where
+// the reference's loop reads a scale (src/Frame.cc:1207-1218 row band 2 * s[octR] per RIGHT keypoint, :1273 level gate |octR - octL| <= 1,
+// :1302-1307 SAD at the left keypoint's level, :1405 back to level 0) on top of the arithmetic of stereo_match_kernel; T.L == 1 gives
+// that kernel's results bit for bit.  levL / levR: one view's level buffer each (rfe_extract_pyramid_u8's `levels` layout, tight pitch).
+// sad_level0: patches from level 0 at the level-scaled coordinates (the reference as written) instead of from level octL.
+// A keypoint whose octave is outside [0, T.L) never indexes the table: left -> no match, right -> not a candidate.
+__global__ __launch_bounds__(256) void stereo_match_pyr_kernel(
+    const uint8_t* __restrict__ levL, const uint8_t* __restrict__ levR, const StereoPyrTable T, const float* __restrict__ kL,
+    const int32_t* __restrict__ octL, int N, const float* __restrict__ kR, const int32_t* __restrict__ octR, int Nr,
+    const int32_t* __restrict__ counts, const float* __restrict__ dL, const float* __restrict__ dR, float maxD, float mbf,
+    int sad_level0, float* __restrict__ uRight, float* __restrict__ depth, int32_t* __restrict__ sadv) {
+    const int lane = threadIdx.x & 63;
+    const int iL = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (counts) { N = counts[0] < N ? counts[0] : N; Nr = counts[1] < Nr ? counts[1] : Nr; }
+    if (iL >= N) return;
+    const float TH_HIGH = 1.4f, TH_LOW = 1.2f;
+    const float thOrbDist = (TH_HIGH + TH_LOW) / 2;
+    const float minD = 0.f;
+    float outU = -1.0f, outZ = -1.0f; int outS = -1;
+    const float uL = kL[2 * iL], vL = kL[2 * iL + 1];
+    const int lvl = octL[iL];
+    const float minU = uL - maxD, maxU = uL - minD;
+    float bestDist = TH_HIGH; int bestIdx = -1;
+    if (!(maxU < 0) && lvl >= 0 && lvl < T.L) {
+        const float4 a = reinterpret_cast<const float4*>(dL + (size_t)iL * 256)[lane];
+        const int row = (int)vL;
+        for (int base = 0; base < Nr; base += 64) {
+            const int iR = base + lane;
+            bool cand = false;
+            if (iR < Nr) {
+                const int oR = octR[iR];
+                if (oR >= 0 && oR < T.L && oR >= lvl - 1 && oR <= lvl + 1) {
+                    const float uR = kR[2 * iR], yR = kR[2 * iR + 1];
+                    const float r = 2.0f * T.s[oR];
+                    cand = !(row < (int)floorf(yR - r) || row > (int)ceilf(yR + r)) && uR >= minU && uR <= maxU;
+                }
+            }
+            unsigned long long mask = __ballot(cand);
+            while (mask) {
+                const int j = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const int ic = base + j;
+                const float4 b = reinterpret_cast<const float4*>(dR + (size_t)ic * 256)[lane];
+                const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
+                double p = 0.0;
+                p += (double)d0 * (double)d0; p += (double)d1 * (double)d1; p += (double)d2 * (double)d2; p += (double)d3 * (double)d3;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off);
+                const float dist = (float)sqrt(p);
+                if (dist < bestDist) { bestDist = dist; bestIdx = ic; }
+            }
+        }
+    }
+    if (bestDist < thOrbDist && bestIdx >= 0) {
+        const float uR0 = kR[2 * bestIdx];
+        const float inv = T.inv[lvl], sc = T.s[lvl];
+        const int su = (int)roundf(uL * inv), sv = (int)roundf(vL * inv), sr = (int)roundf(uR0 * inv);
+        const int li = sad_level0 ? 0 : lvl;
+        const int Hs = T.h[li], Ws = T.w[li];
+        const uint8_t* __restrict__ imgL = levL + T.off[li];
+        const uint8_t* __restrict__ imgR = levR + T.off[li];
+        const int w = 5, Lh = 5;
+        const bool ok = !(sr - Lh - w < 0 || sr + Lh + w + 1 >= Ws) && !(sv - w < 0 || sv + w >= Hs || su - w < 0 || su + w >= Ws);
+        if (ok) {
+            float vd[11]; float best = 2147483647.0f; int bestinc = 0;
+            // this lane's two patch pixels (121 = 64 + 57)
+            const int p0 = lane, p1 = lane + 64;
+            const int y0 = p0 / 11 - w, x0 = p0 % 11 - w, y1 = p1 / 11 - w, x1 = p1 % 11 - w;
+            const int l0 = imgL[(size_t)(sv + y0) * Ws + su + x0];
+            const int l1 = p1 < 121 ? imgL[(size_t)(sv + y1) * Ws + su + x1] : 0;
+#pragma unroll
+            for (int inc = -Lh; inc <= Lh; ++inc) {
+                int sad = abs(l0 - (int)imgR[(size_t)(sv + y0) * Ws + sr + inc + x0]);
+                if (p1 < 121) sad += abs(l1 - (int)imgR[(size_t)(sv + y1) * Ws + sr + inc + x1]);
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) sad += __shfl_xor(sad, off);
+                const float dist = (float)sad;
+                if (dist < best) { best = dist; bestinc = inc; }
+                vd[Lh + inc] = dist;
+            }
+            if (!(bestinc == -Lh || bestinc == Lh)) {
+                float d1 = 0.f, d2 = 0.f, d3 = 0.f;
+#pragma unroll
+                for (int t = 1; t < 10; ++t) if (t == Lh + bestinc) { d1 = vd[t - 1]; d2 = vd[t]; d3 = vd[t + 1]; }
+                const float deltaR = (d1 - d3) / (2.0f * (d1 + d3 - 2.0f * d2));
+                if (!(deltaR < -1 || deltaR > 1)) {
+                    float bestuR = sc * ((float)sr + (float)bestinc + deltaR);
+                    float disparity = uL - bestuR;
+                    if (disparity >= minD && disparity < maxD) {
+                        if (disparity <= 0) { disparity = 0.01f; bestuR = uL - 0.01f; }
+                        outZ = mbf / disparity; outU = bestuR; outS = (int)best;
+                    }
+                }
+            }
+        }
+    }
+    if (lane == 0) { uRight[iL] = outU; depth[iL] = outZ; sadv[iL] = outS; }
+}
+
+// N / Nr: the counts, or with `counts` (device {n_left, n_right}) the capacities: the grid covers the capacity and entries >= n_left of
+// uRight / depth are -1, as launch_stereo_match_counts does.  The outlier cut is the single-level one (the SADs are level pixels either way).
+void launch_stereo_match_pyr(hipStream_t s, const uint8_t* levL, const uint8_t* levR, const StereoPyrTable& T, const float* kL,
+                             const int32_t* octL, int N, const float* kR, const int32_t* octR, int Nr, const int32_t* counts,
+                             const float* dL, const float* dR, float mb, float mbf, int sad_level0, float* uRight, float* depth,
+                             int32_t* sadv) {
+    if (N <= 0) return;
+    const float maxD = mbf / mb;
+    if (counts) hipLaunchKernelGGL(stereo_fill_kernel, dim3((N + 255) / 256), dim3(256), 0, s, uRight, depth, sadv, N);
+    hipLaunchKernelGGL(stereo_match_pyr_kernel, dim3((N + 3) / 4), dim3(256), 0, s, levL, levR, T, kL, octL, N, kR, octR, Nr, counts, dL,
+                       dR, maxD, mbf, sad_level0, uRight, depth, sadv);
+    int P2 = 1;
+    while (P2 < N) P2 <<= 1;
+    hipLaunchKernelGGL(stereo_filter_kernel, dim3(1), dim3(1024), (size_t)P2 * 8, s, N, P2, counts, sadv, uRight, depth);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,0 +1,143 @@
+"""CPU: the numpy restatement of the octave-aware stereo match (tests/stereo_pyramid_ref.py) pinned to the existing
+oracle -- equal to oracle.stereo_match at one level, descriptor distance equal to the oracle's bit for bit -- and checked on a constructed
+case with a known answer that exercises each octave rule once; plus the link-level checks of the new C ABI entries."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import pyramid_ref as PR
+import stereo_pyramid_ref as SR
+from rover_slam_amd import weights as Wt, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MB, MBF = 0.11, 0.11 * 435.0
+
+
+def shifted_pair(H, W, disp, seed):
+    """tests/test_stereo.py:_shifted_pair -- one textured scene, pure horizontal shift, independent sensor noise per view"""
+    rng = np.random.default_rng(seed)
+    scene = synth.make_scene(rng, H, W + disp, margin=0)
+    left = np.clip(scene[:, :W] + rng.integers(0, 8, (H, W)), 0, 255).astype(np.uint8)
+    right = np.clip(scene[:, disp:disp + W] + rng.integers(0, 8, (H, W)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(left), np.ascontiguousarray(right)
+
+
+def test_geometry_is_the_library_contract():
+    for H, W, L, sf in ((480, 752, 8, 1.2), (240, 320, 4, 1.2), (96, 240, 3, 1.5), (120, 160, 1, 1.2)):
+        for a, b in zip(SR.geometry(H, W, L, sf), PR.geometry(H, W, L, sf)):
+            assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("H,W,disp", [(120, 160, 9), (240, 320, 17)])
+def test_one_level_equals_oracle(oracle, H, W, disp):
+    wsp = Wt.make_superpoint(seed=7)
+    left, right = shifted_pair(H, W, disp, seed=disp)
+    ex = PR.extract(oracle, wsp, np.stack([left, right]), 1, 1.2, 400)
+    nl, nr = int(ex["n"][0]), int(ex["n"][1])
+    kl, kr, dl, dr = ex["kpts"][0, :nl], ex["kpts"][1, :nr], ex["desc"][0, :nl], ex["desc"][1, :nr]
+    assert (ex["octave"] == 0).all()
+    u_ref, z_ref = oracle.stereo_match(left, right, kl, kr, dl, dr, MB, MBF)
+    assert (u_ref >= 0).sum() > 10
+    for mode in (SR.SAD_LEVEL, SR.SAD_LEVEL0):
+        u, z = SR.stereo_match([left], [right], np.ones(1, np.float32), kl, np.zeros(nl, np.int32), kr, np.zeros(nr, np.int32), dl, dr,
+                               MB, MBF, mode)
+        assert np.array_equal(u, u_ref) and np.array_equal(z, z_ref)
+
+
+def test_descriptor_distance_equals_oracle(oracle):
+    rng = np.random.default_rng(5)
+    n = 300
+    f = rng.standard_normal((n, 256)).astype(np.float32); f /= np.linalg.norm(f, axis=1, keepdims=True)
+    q = f + rng.uniform(0.01, 0.1, (n, 1)).astype(np.float32) * rng.standard_normal((n, 256)).astype(np.float32)
+    q = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
+    off = np.arange(n + 1, dtype=np.int32)                      # one candidate per query: best_dist is that pair's distance
+    cand = rng.permutation(n).astype(np.int32)
+    cand[::2] = np.arange(n, dtype=np.int32)[::2]               # half of them close pairs, half unrelated ones
+    _, bd, _ = oracle.search_candidates(q, f, off, cand)
+    mine = np.array([SR.desc_dist(q[i], f[cand[i]])[0] for i in range(n)], np.float32)
+    assert np.array_equal(mine, bd)
+    assert (bd < 1.3).sum() > 100 and (bd > 1.3).sum() > 100
+
+
+def constructed_case():
+    """Hand-built level images (level l of the left view = the right one rolled by d_l LEVEL pixels, +-2 of noise) and hand-placed
+    keypoints, scale factor 1.5 (s = 1, 1.5, 2.25)."""
+    H, W, L, sf = 96, 240, 3, 1.5
+    lh, lw, s = SR.geometry(H, W, L, sf)
+    assert lh.tolist() == [96, 64, 43] and lw.tolist() == [240, 160, 107] and s.tolist() == [1.0, 1.5, 2.25]
+    rng = np.random.default_rng(0)
+    d_l = [7, 5, 3]
+    lev_l, lev_r = [], []
+    for l in range(L):
+        r = rng.integers(0, 256, (int(lh[l]), int(lw[l]))).astype(np.uint8)
+        lt = np.roll(r, d_l[l], axis=1)                         # left(x) = right(x - d_l)
+        lev_r.append(r)
+        lev_l.append(np.clip(lt.astype(np.int32) + rng.integers(-2, 3, lt.shape), 0, 255).astype(np.uint8))
+    # (level x, level y, octave) of the left keypoints and of the right keypoint carrying the same descriptor
+    left = [(60, 20, 0), (50, 30, 1), (40, 20, 2), (100, 60, 0), (140, 30, 0), (50, 40, 2)]
+    right = [(53, 20, 0), (45, 30, 1), (37, 20, 2), (93, 60, 2), (133, 33, 0), (47, 40, 2)]
+    #  0-2: a clean match on each octave;  3: identical descriptor two octaves away (its coordinates are level-0 pixels);
+    #  4: 3 rows off;  5: the 11x11 patch leaves level 2 (43 rows) but not level 0
+    level0 = lambda pts, raw: np.array([[np.float32(x) * (np.float32(1) if i in raw else s[o]),   # noqa: E731
+                                         np.float32(y) * (np.float32(1) if i in raw else s[o])] for i, (x, y, o) in enumerate(pts)], np.float32)
+    kl, kr = level0(left, ()), level0(right, (3,))
+    ol = np.array([o for _, _, o in left], np.int32); orr = np.array([o for _, _, o in right], np.int32)
+    d = rng.standard_normal((6, 256)).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return dict(H=H, W=W, L=L, sf=sf, s=s, d_l=d_l, lev_l=lev_l, lev_r=lev_r, kl=kl, kr=kr, ol=ol, orr=orr, dl=d, dr=d.copy(), left=left)
+
+
+def check_constructed(run):
+    """run(case, octR, mb, mbf, sad_source) -> (u, z); shared with the GPU test of the same case"""
+    c = constructed_case()
+    s, d_l = c["s"], c["d_l"]
+    u, z = run(c, c["orr"], MB, MBF, SR.SAD_LEVEL)
+    for i in range(3):                                          # rule 3 + 4: SAD at the level, back to level 0 with s_l
+        x, _, o = c["left"][i]
+        want = float(s[o]) * (x - d_l[o])
+        assert abs(u[i] - want) < 0.05 * s[o], (i, u[i], want)
+        assert abs(z[i] - MBF / (c["kl"][i, 0] - want)) < 0.05 * MBF / (c["kl"][i, 0] - want)
+    assert u[3] == -1 and z[3] == -1                            # rule 2: two octaves away is not a candidate ...
+    assert u[4] == -1                                           # rule 1: 3 rows off at octave 0 (band 2) ...
+    assert u[5] == -1 and z[5] == -1                            # left patch leaves the LEVEL image
+    o2 = c["orr"].copy(); o2[3] = 1; o2[4] = 1
+    u2, _ = run(c, o2, MB, MBF, SR.SAD_LEVEL)
+    assert abs(u2[3] - 93) < 0.05                               # ... one octave away it is taken (SAD at the LEFT keypoint's level 0)
+    assert abs(u2[4] - 133) < 0.05                              # ... and inside the band 2 * 1.5 = 3 of an octave-1 right keypoint
+    assert np.array_equal(u2[:3], u[:3])
+    u0, _ = run(c, c["orr"], MB, MBF, SR.SAD_LEVEL0)            # level 0 at level-scaled coordinates: octave 0 rows are the same ones
+    assert u0[0] == u[0] and u0[3] == -1 and u0[4] == -1
+    u3, z3 = run(c, c["orr"], 10.0, 10.0 * 0.5, SR.SAD_LEVEL)   # a disparity beyond mbf / mb is rejected
+    assert (u3 == -1).all() and (z3 == -1).all()
+    # an octave outside [0, L): a left keypoint gets no match, a right one is never a candidate
+    ob = c["orr"].copy(); ob[1] = 3
+    olb = c["ol"].copy(); olb[2] = -1
+    c2 = dict(c, ol=olb)
+    ub, _ = run(c2, ob, MB, MBF, SR.SAD_LEVEL)
+    assert ub[1] == -1 and ub[2] == -1 and ub[0] == u[0]
+
+
+def test_constructed_case_known_answer():
+    check_constructed(lambda c, octr, mb, mbf, mode: SR.stereo_match(c["lev_l"], c["lev_r"], c["s"], c["kl"], c["ol"], c["kr"], octr,
+                                                                     c["dl"], c["dr"], mb, mbf, mode))
+
+
+def test_exports_hold_the_new_entries():
+    from rover_slam_amd import capi
+    for name in ("rfe_stereo_match_pyramid", "rfe_stereo_match_pyramid_dev", "rfe_stereo_frame_pyramid_dev"):
+        assert name in capi.EXPORTS
+        getattr(capi.lib, name)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+@pytest.mark.parametrize("macro", [True, False])
+def test_driver_compiles_and_links(tmp_path, macro):
+    exe = str(tmp_path / "stereo_pyramid_driver")
+    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + (["-DRFE_SP_PYRAMID=1"] if macro else [])
+    subprocess.check_call(cmd + [os.path.join(ROOT, "tests", "cpp", "stereo_pyramid_driver.cpp"), "-o", exe,
+                                 "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
+                                 "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    assert os.path.exists(exe)
