@@ -199,7 +199,9 @@ int rfe_extract_u8_bin_dev(rfe_ctx* ctx, const uint8_t* img_dev, int H, int W, i
 
 /* ---- SuperPoint on a scale pyramid (SPextractor with nlevels > 1) ----
  * The reference's ExtractMultiLayers (src/Extractors/SPextractor.cc:619-653) over the levels of ComputePyramid (:686-712): level l is
- * W_l x H_l = lrintf(W / s_l) x lrintf(H / s_l), s_0 = 1, s_l = (float)((double)s_{l-1} * scale_factor), made from level l-1 by 11-bit
+ * W_l x H_l = lrintf((float)W * (1.0f / s_l)) x lrintf((float)H * (1.0f / s_l)) (src/Extractors/SPextractor.cc:691-692), s_0 = 1,
+ * s_l = (float)((double)s_{l-1} * scale_factor) (the constructor, src/Extractors/SPextractor.cc:109-129; its per-level feature budget
+ * mnFeaturesPerLevel, :133-146, is what a caller passes as kmax), made from level l-1 by 11-bit
  * fixed-point bilinear resampling with half-pixel centres (modelled on cv::resize INTER_LINEAR; bit parity with OpenCV is NOT claimed).
  * Every level runs the rfe_extract_u8 pipeline with Kmax = kmax[l] (a level below 8 px or with kmax[l] == 0 yields no keypoints), and
  * the rows are merged per frame in level order: row i of level l lands at sum_{j<l} n_j + i with kpts = (x * s_l, y * s_l) (one fp32
@@ -237,7 +239,7 @@ int rfe_match_dev(rfe_ctx* ctx, const float* k0n, const float* k1n, const float*
 
 /* One pair, pixel keypoints in, vnMatches12 out (length M, -1 = unmatched); returns the number
  * of accepted matches (>= 0) or a negative rfe_status.  (rows, cols) is the image size used by
- * NormalizeKeypoints; pass 300,400 to reproduce the hard-coded quirk of three of the reference's
+ * NormalizeKeypoints (src/Matchers/transform.cpp:19-32); pass 300,400 to reproduce the hard-coded quirk of three of the reference's
  * four overloads (SPmatcher.cc:360-361,376-377,414-415). */
 int rfe_match_fused(rfe_ctx* ctx, const float* kpts0_xy, int M, const float* kpts1_xy, int N,
                     const float* desc0, const float* desc1, int rows, int cols, float filter_thr,
@@ -254,7 +256,7 @@ int rfe_extract_match_stream_dev(rfe_ctx* ctx, const uint8_t* img_dev, int H, in
 /* ---- sparse stereo matching ----
  * Frame::ComputeStereoMatches (src/Frame.cc:1159-1446) for nLevels == 1 (rfe_stereo_match_pyramid below for nLevels > 1): for every left keypoint, best right
  * keypoint within +-2 rows and the disparity range [0, mbf/mb) by 256-d L2 distance
- * (SPmatcher::DescriptorDistance_sp, src/Matchers/SPmatcher.cc:2184-2189; accepted below (TH_HIGH+TH_LOW)/2 = 1.3),
+ * (SPmatcher::DescriptorDistance_sp, src/Matchers/SPmatcher.cc:2184-2189; accepted below (TH_HIGH+TH_LOW)/2 = 1.3, SPmatcher.cc:13-14),
  * 11x11 SAD refinement over +-5 px on the raw images, parabola sub-pixel fit, median outlier cut.
  * kL/kR: pixel keypoints [N,2]/[Nr,2]; dL/dR: descriptors [N,256]/[Nr,256]; mb, mbf: baseline (m) and
  * baseline*fx of the Frame.  Outputs mvuRight / mvDepth: [N], -1 = no match.  Deviation: left keypoints whose

@@ -1,7 +1,9 @@
 """ctypes wrapper over oracle/librfe_oracle.so -- CPU ORACLE, test infrastructure only.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
-PARITY UNPINNED w.r.t. the true reference (see oracle/rfe_oracle.h header).
+PARITY UNPINNED w.r.t. the true reference for SuperPoint and LightGlue (see oracle/rfe_oracle.h header); the classic stages
+(stereo_match, distinctive_descriptors, normalize_keypoints, the descriptor distance) are held to the reference's own C++ by
+tests/test_ref_classic.py (oracle/ref_classic/).
 """
 import ctypes as C
 import os

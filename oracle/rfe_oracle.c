@@ -751,7 +751,9 @@ void rfo_distinctive_descriptors(const float* desc, const int32_t* offsets, int 
         const int o = offsets[p], n = offsets[p + 1] - o;
         if (n <= 0) { best[p] = -1; median[p] = 0.f; continue; }
         float* D = (float*)malloc((size_t)n * n * sizeof(float));
-        float* row = (float*)malloc((size_t)n * sizeof(float));
+        float* meds = (float*)malloc((size_t)n * sizeof(float));
+        /* rows in parallel for large points (every D cell has one writer: the thread of min(i, j)); the pick below stays serial */
+        #pragma omp parallel for schedule(dynamic, 8) if (n >= 256)
         for (int i = 0; i < n; ++i) {
             D[(size_t)i * n + i] = 0.f;
             for (int j = i + 1; j < n; ++j) {
@@ -759,15 +761,22 @@ void rfo_distinctive_descriptors(const float* desc, const int32_t* offsets, int 
                 D[(size_t)i * n + j] = d; D[(size_t)j * n + i] = d;
             }
         }
-        float bestMedian = 2147483647.0f; int bestIdx = 0;
-        for (int i = 0; i < n; ++i) {
-            memcpy(row, D + (size_t)i * n, (size_t)n * sizeof(float));
-            qsort(row, n, sizeof(float), float_cmp);
-            const float med = row[(int)(0.5 * (n - 1))];
-            if (med < bestMedian) { bestMedian = med; bestIdx = i; }
+        #pragma omp parallel if (n >= 256)
+        {
+            float* row = (float*)malloc((size_t)n * sizeof(float));
+            #pragma omp for schedule(dynamic, 8)
+            for (int i = 0; i < n; ++i) {
+                memcpy(row, D + (size_t)i * n, (size_t)n * sizeof(float));
+                qsort(row, n, sizeof(float), float_cmp);
+                meds[i] = row[(int)(0.5 * (n - 1))];
+            }
+            free(row);
         }
+        float bestMedian = 2147483647.0f; int bestIdx = 0;
+        for (int i = 0; i < n; ++i)
+            if (meds[i] < bestMedian) { bestMedian = meds[i]; bestIdx = i; }
         best[p] = bestIdx; median[p] = bestMedian;
-        free(D); free(row);
+        free(D); free(meds);
     }
 }
 
