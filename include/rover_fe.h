@@ -365,6 +365,47 @@ int rfe_search_candidates_dev(rfe_ctx* ctx, const float* q_dev, int Nq, const fl
 int rfe_distinctive_descriptors_dev(rfe_ctx* ctx, const float* desc_dev, const int32_t* offsets_dev, int Np, int total, int maxn,
                                     int32_t* best_dev, float* median_dev);
 
+/* ---- SPmatcher::SearchByProjection1 as one call ----
+ * The left-camera branch of SearchByProjection1 (src/Matchers/SPmatcher.cc:1190-1283), which Tracking::SearchLocalPoints runs on every
+ * tracked frame, from the projected map points to what the loop leaves in F.mvpMapPoints: the feature grid (Frame::AssignFeaturesToGrid /
+ * PosInGrid, src/Frame.cc:488-523, 998-1014; 32 x 24 cells over [min_x, max_x) x [min_y, max_y) = mnMinX..mnMaxY, cell = roundf), the
+ * candidate list of every map point (Frame::GetFeaturesInArea, src/Frame.cc:895-987, in its visiting order: cell column, cell row,
+ * feature index), the best / second-best scan of rfe_search_candidates over it, and the loop's SEQUENTIAL assignment: map points are
+ * processed in index order, feature j is blocked for map point i when skip[j] != 0 (it owned an observed MapPoint before the call) or
+ * when a map point k < i with observed[k] != 0 was accepted on j; map point i is accepted when its best distance <= th_high (the
+ * reference's TH_HIGH is 1.4f).  The result is exact, not an approximation of the loop.
+ *   q [Nq,256] map-point descriptors, proj [Nq,2] (mTrackProjX, mTrackProjY), radius [Nq] the final window half size
+ *   (RadiusByViewingCos * th * mvScaleFactors[level]; a feature is a candidate when |dx| < radius and |dy| < radius, both strict),
+ *   pred_level [Nq] or NULL = 0 (a feature passes with pred_level - 1 <= octave <= pred_level), observed [Nq] or NULL = all 1
+ *   (Observations() > 0 of the map point);
+ *   f [Nf,256] frame descriptors; the feature positions as EXACTLY ONE of kpts [Nf,2] f32 (mvKeysUn, the pyramid entries' output) and
+ *   kxy [Nf,2] i32 (rfe_extract_u8_dev / rfe_stereo_frame_dev's output, read as float); octave [Nf] or NULL = 0; skip [Nf] or NULL.
+ *   assign [Nf]: the LAST accepted map point whose best feature is this one (an unobserved earlier writer is overwritten), -1 = none;
+ *   best_idx / best_dist / second_dist [Nq] (each may be NULL): what map point i saw at its turn, best_idx even when best_dist > th_high
+ *   (-1 / 256 / 256 without an unblocked candidate); stats [4]: accepted map points (overwritten ones count, as the reference's
+ *   nmatches), candidates over all lists, rounds the assignment took, overflow flag.
+ * rfe_search_by_projection_dev: DEVICE pointers, asynchronous on the ctx stream; no host synchronisation and no host read of device data
+ *   once the workspace has its size.  nf_dev (device [1], or NULL): the feature count is min(*nf_dev, Nf), read on the device -- the n
+ *   rfe_stereo_frame_dev leaves there; rows past it are never candidates and their assign is -1.  cand_cap: (index, distance) slots for
+ *   all lists together, kept in the ctx workspace.  When the lists need more the call still completes inside its buffers: stats[3] = 1,
+ *   stats[1] = the slots needed, every assign / best_idx -1, every distance 256, stats[0] = 0.  stats is required.  A non-finite
+ *   projection or radius, or a pred_level outside 0..RFE_MAX_LEVELS-1, gives that map point an empty list.
+ * rfe_search_by_projection: HOST pointers; sizes the slots itself (never reports overflow; stats may be NULL) and returns stats[0] >= 0.
+ * Refused (RFE_ERR_INVALID): Nq outside 0..16384; Nf outside 0..4096; max_x <= min_x or max_y <= min_y; cand_cap < 0; both or neither of
+ *   kpts / kxy; a NULL required pointer; host form only: a pred_level outside 0..RFE_MAX_LEVELS-1, a non-finite projection, radius,
+ *   keypoint, bound or th_high.  Nq == 0 or Nf == 0 is valid (nothing matches).
+ * Out of scope: the right-camera branch of two-camera rigs (:1285-1351) -- the caller keeps it. */
+int rfe_search_by_projection_dev(rfe_ctx* ctx, const float* q_dev, const float* proj_dev, const float* radius_dev,
+                                 const int32_t* pred_level_dev, const uint8_t* observed_dev, int Nq, const float* f_dev,
+                                 const float* kpts_dev, const int32_t* kxy_dev, const int32_t* octave_dev, const uint8_t* skip_dev, int Nf,
+                                 const int32_t* nf_dev, float min_x, float min_y, float max_x, float max_y, float th_high, int cand_cap,
+                                 int32_t* assign_dev, int32_t* best_idx_dev, float* best_dist_dev, float* second_dist_dev,
+                                 int32_t* stats_dev);
+int rfe_search_by_projection(rfe_ctx* ctx, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
+                             const uint8_t* observed, int Nq, const float* f, const float* kpts, const int32_t* kxy, const int32_t* octave,
+                             const uint8_t* skip, int Nf, float min_x, float min_y, float max_x, float max_y, float th_high,
+                             int32_t* assign, int32_t* best_idx, float* best_dist, float* second_dist, int32_t* stats);
+
 /* ---- multi-device pool (BASELINE configs[3] for a C / C++ host) ----
  * The reference runs on ONE device (device_id = 0, src/Extractors/superpoint_onnx.cc:19, src/Matchers/lightglue_onnx.cpp:24) and
  * is a C++ program (src/Tracking.cc:645-651); a pool gives such a host the frame sharding of rover-slam_amd/sharding.py without

@@ -24,6 +24,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix", "rfe_binarize_descriptors",
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
+    "rfe_search_by_projection", "rfe_search_by_projection_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
@@ -108,6 +109,10 @@ lib.rfe_l2_distance_matrix_dev.argtypes = [C.c_void_p, _fp, C.c_int, _fp, C.c_in
 lib.rfe_binarize_descriptors_dev.argtypes = [C.c_void_p, _fp, C.c_int, _u8p]
 lib.rfe_search_candidates_dev.argtypes = [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _ip, _ip, _u8p, _ip, _fp, _fp]
 lib.rfe_distinctive_descriptors_dev.argtypes = [C.c_void_p, _fp, _ip, C.c_int, C.c_int, C.c_int, _ip, _fp]
+_psq = [C.c_void_p, _fp, _fp, _fp, _ip, _u8p, C.c_int, _fp, _fp, _ip, _ip, _u8p, C.c_int]
+_psb = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]
+lib.rfe_search_by_projection.argtypes = _psq + _psb + [_ip, _ip, _fp, _fp, _ip]
+lib.rfe_search_by_projection_dev.argtypes = _psq + [_ip] + _psb + [C.c_int, _ip, _ip, _fp, _fp, _ip]
 lib.rfe_profile_enable.argtypes = [C.c_void_p, C.c_int]
 lib.rfe_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
 lib.rfe_profile_reset.argtypes = [C.c_void_p]
@@ -585,6 +590,36 @@ class Context:
                                             cd.ctypes.data, None if sk is None else sk.ctypes.data, bi.ctypes.data,
                                             bd.ctypes.data, sd.ctypes.data))
         return bi[:Nq], bd[:Nq], sd[:Nq]
+
+    def search_by_projection(self, q, proj, radius, f, bounds, kpts=None, kxy=None, pred_level=None, observed=None, octave=None, skip=None,
+                             th_high=1.4):
+        """SPmatcher::SearchByProjection1 as one call (rfe_search_by_projection, host arrays).  bounds = (min_x, min_y, max_x, max_y);
+        exactly one of kpts [Nf,2] f32 and kxy [Nf,2] i32.  Returns a dict: assign [Nf], best_idx / best_dist / second_dist [Nq],
+        nmatches, stats [4] (nmatches, candidates, rounds, overflow)."""
+        qa = np.ascontiguousarray(q, np.float32).reshape(-1, 256); fa = np.ascontiguousarray(f, np.float32).reshape(-1, 256)
+        pa = np.ascontiguousarray(proj, np.float32).reshape(-1, 2); ra = np.ascontiguousarray(radius, np.float32).reshape(-1)
+        Nq, Nf = qa.shape[0], fa.shape[0]
+        assert pa.shape[0] == Nq and ra.shape[0] == Nq
+        opt = lambda a, dt, n: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
+        ka, xa = opt(kpts, np.float32, Nf), opt(kxy, np.int32, Nf)
+        lv, ob = opt(pred_level, np.int32, Nq), opt(observed, np.uint8, Nq)
+        oc, sk = opt(octave, np.int32, Nf), opt(skip, np.uint8, Nf)
+        asg = np.full((max(Nf, 1),), -1, np.int32); st = np.zeros((4,), np.int32)
+        bi = np.full((max(Nq, 1),), -1, np.int32); bd = np.full((max(Nq, 1),), 256, np.float32); sd = np.full((max(Nq, 1),), 256, np.float32)
+        n = self._chk(lib.rfe_search_by_projection(self.h, qa.ctypes.data, pa.ctypes.data, ra.ctypes.data, _addr(lv), _addr(ob), Nq,
+                                                   fa.ctypes.data, _addr(ka), _addr(xa), _addr(oc), _addr(sk), Nf, *[float(b) for b in bounds],
+                                                   th_high, asg.ctypes.data, bi.ctypes.data, bd.ctypes.data, sd.ctypes.data, st.ctypes.data))
+        return {"assign": asg[:Nf], "best_idx": bi[:Nq], "best_dist": bd[:Nq], "second_dist": sd[:Nq], "nmatches": n, "stats": st}
+
+    def search_by_projection_dev(self, q, proj, radius, Nq, f, Nf, bounds, cand_cap, assign, stats, kpts=None, kxy=None, pred_level=None,
+                                 observed=None, octave=None, skip=None, nf_dev=None, th_high=1.4, best_idx=None, best_dist=None,
+                                 second_dist=None):
+        """rfe_search_by_projection_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
+        outputs land in assign [Nf], stats [4] and the optional best_idx / best_dist / second_dist [Nq]."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_search_by_projection_dev(self.h, a(q), a(proj), a(radius), a(pred_level), a(observed), Nq, a(f), a(kpts), a(kxy),
+                                                   a(octave), a(skip), Nf, a(nf_dev), *[float(b) for b in bounds], th_high, cand_cap,
+                                                   a(assign), a(best_idx), a(best_dist), a(second_dist), a(stats)))
 
     def distinctive_descriptors(self, desc, offsets):
         """MapPoint::ComputeDistinctiveDescriptors for many map points (MapPoint.cc:438-530)."""

@@ -205,7 +205,7 @@ extern "C" void rfe_destroy(rfe_ctx* c) {
     host_graph_release(c->g_match);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     c->sp_hold.reset(); c->lg_hold.reset();   // the last ctx holding a device copy frees it
-    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->sp_cnt); fr(c->ws_pyr); fr(c->ws_ptab);
+    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->ws_ps); fr(c->sp_cnt); fr(c->ws_pyr); fr(c->ws_ptab);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -517,7 +517,7 @@ extern "C" void rfe_host_free(void* p) {
 }
 
 extern "C" int64_t rfe_workspace_bytes(rfe_ctx* c) {
-    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes + c->ws_pyr_bytes + c->ws_ptab_bytes) : 0;
+    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes + c->ws_ps_bytes + c->ws_pyr_bytes + c->ws_ptab_bytes) : 0;
 }
 
 extern "C" uint64_t rfe_weights_id(rfe_ctx* c, int kind) {
@@ -1890,6 +1890,114 @@ extern "C" int rfe_search_candidates(rfe_ctx* c, const float* q, int Nq, const f
     RFE_HIP(c, hipStreamSynchronize(s));
     prof_collect(c);
     return RFE_OK;
+}
+
+// SPmatcher::SearchByProjection1, left-camera branch (src/Matchers/SPmatcher.cc:1190-1283), device resident: grid, candidate lists, scan and
+// the sequential assignment (proj_search.hip).  Four kernels on the ctx stream, nothing read back.
+static int ps_check(rfe_ctx* c, const void* q, const void* proj, const void* radius, int Nq, const void* f, const void* kpts, const void* kxy,
+                    int Nf, float min_x, float min_y, float max_x, float max_y, int cand_cap, const void* assign) {
+    if (Nq < 0 || Nq > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nq outside 0..16384");
+    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nf outside 0..4096");
+    if (!(max_x > min_x) || !(max_y > min_y)) return fail(c, RFE_ERR_INVALID, "search_by_projection: empty image bounds");
+    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_by_projection: negative cand_cap");
+    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pass exactly one of kpts and kxy");
+    if ((Nq > 0 && (!q || !proj || !radius)) || (Nf > 0 && (!f || !assign))) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection_dev(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
+                                            const uint8_t* observed, int Nq, const float* f, const float* kpts, const int32_t* kxy,
+                                            const int32_t* octave, const uint8_t* skip, int Nf, const int32_t* nf_dev, float min_x,
+                                            float min_y, float max_x, float max_y, float th_high, int cand_cap, int32_t* assign,
+                                            int32_t* best_idx, float* best_dist, float* second_dist, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, cand_cap, assign);
+    if (rc) return rc;
+    if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    const size_t b_cs = al(770 * 4), b_it = al((size_t)std::max(Nf, 1) * 4), b_xy = al((size_t)std::max(Nf, 1) * 8),
+                 b_so = al((size_t)(Nq + 1) * 4), b_c = al((size_t)std::max(cand_cap, 1) * 4);
+    if ((rc = ensure_ws(c, &c->ws_ps, &c->ws_ps_bytes, b_cs + b_it + b_xy + b_so + 2 * b_c))) return rc;
+    char* p = (char*)c->ws_ps;
+    int32_t* cell_start = (int32_t*)p; p += b_cs; int32_t* cell_items = (int32_t*)p; p += b_it; float* fxy = (float*)p; p += b_xy;
+    int32_t* seg_off = (int32_t*)p; p += b_so; int32_t* cand_idx = (int32_t*)p; p += b_c; float* cand_dist = (float*)p;
+    const float inv_w = 32.f / (max_x - min_x), inv_h = 24.f / (max_y - min_y);      // Frame::mfGridElementWidthInv / HeightInv
+    hipStream_t s = c->stream;
+    { ProfScope ps(c, "ps_grid"); launch_proj_grid(s, kpts, kxy, Nf, nf_dev, min_x, min_y, inv_w, inv_h, cell_start, cell_items, fxy); }
+    { ProfScope ps(c, "ps_count");
+      launch_proj_count(s, proj, radius, pred_level, Nq, cell_start, cell_items, fxy, octave, min_x, min_y, inv_w, inv_h, cand_cap, seg_off,
+                        cand_idx, stats); }
+    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist); }
+    { ProfScope ps(c, "ps_resolve");
+      launch_proj_resolve(s, seg_off, cand_idx, cand_dist, observed, Nq, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
+                                        const uint8_t* observed, int Nq, const float* f, const float* kpts, const int32_t* kxy,
+                                        const int32_t* octave, const uint8_t* skip, int Nf, float min_x, float min_y, float max_x,
+                                        float max_y, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist,
+                                        float* second_dist, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, 0, assign);
+    if (rc) return rc;
+    auto fin = [](float v) { return v - v == 0.f; };
+    if (!fin(min_x) || !fin(min_y) || !fin(max_x) || !fin(max_y) || !fin(th_high))
+        return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite argument");
+    for (int i = 0; i < Nq; ++i) {
+        if (!fin(proj[2 * i]) || !fin(proj[2 * i + 1]) || !fin(radius[i])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite projection or radius");
+        if (pred_level && (pred_level[i] < 0 || pred_level[i] >= RFE_MAX_LEVELS)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pred_level outside 0..15");
+    }
+    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite keypoint");
+    RFE_HIP(c, hipSetDevice(c->device));
+    const int nq1 = std::max(Nq, 1), nf1 = std::max(Nf, 1);
+    const size_t bq = al((size_t)nq1 * 1024), bp = al((size_t)nq1 * 8), b4q = al((size_t)nq1 * 4), b1q = al((size_t)nq1),
+                 bf = al((size_t)nf1 * 1024), bk = al((size_t)nf1 * 8), b4f = al((size_t)nf1 * 4), b1f = al((size_t)nf1), bs = al(16);
+    if ((rc = ensure_ws(c, &c->ws_io, &c->ws_io_bytes, bq + bp + 5 * b4q + b1q + bf + bk + 2 * b4f + b1f + bs))) return rc;
+    char* p = (char*)c->ws_io;
+    float* dq = (float*)p; p += bq; float* dproj = (float*)p; p += bp; float* drad = (float*)p; p += b4q; int32_t* dlev = (int32_t*)p; p += b4q;
+    uint8_t* dobs = (uint8_t*)p; p += b1q; float* df = (float*)p; p += bf; void* dk = p; p += bk; int32_t* doct = (int32_t*)p; p += b4f;
+    uint8_t* dsk = (uint8_t*)p; p += b1f; int32_t* dasg = (int32_t*)p; p += b4f; int32_t* dbi = (int32_t*)p; p += b4q;
+    float* dbd = (float*)p; p += b4q; float* dsd = (float*)p; p += b4q; int32_t* dst = (int32_t*)p;
+    hipStream_t s = c->stream;
+    if (Nq > 0) {
+        RFE_HIP(c, hipMemcpyAsync(dq, q, (size_t)Nq * 1024, hipMemcpyHostToDevice, s));
+        RFE_HIP(c, hipMemcpyAsync(dproj, proj, (size_t)Nq * 8, hipMemcpyHostToDevice, s));
+        RFE_HIP(c, hipMemcpyAsync(drad, radius, (size_t)Nq * 4, hipMemcpyHostToDevice, s));
+        if (pred_level) RFE_HIP(c, hipMemcpyAsync(dlev, pred_level, (size_t)Nq * 4, hipMemcpyHostToDevice, s));
+        if (observed) RFE_HIP(c, hipMemcpyAsync(dobs, observed, (size_t)Nq, hipMemcpyHostToDevice, s));
+    }
+    if (Nf > 0) {
+        RFE_HIP(c, hipMemcpyAsync(df, f, (size_t)Nf * 1024, hipMemcpyHostToDevice, s));
+        RFE_HIP(c, hipMemcpyAsync(dk, kpts ? (const void*)kpts : (const void*)kxy, (size_t)Nf * 8, hipMemcpyHostToDevice, s));
+        if (octave) RFE_HIP(c, hipMemcpyAsync(doct, octave, (size_t)Nf * 4, hipMemcpyHostToDevice, s));
+        if (skip) RFE_HIP(c, hipMemcpyAsync(dsk, skip, (size_t)Nf, hipMemcpyHostToDevice, s));
+    }
+    // the candidate total is known on the device only: run with the largest slot count used so far (at least 16 per map point) and,
+    // when the lists need more, once again with exactly what they need
+    int32_t st[4] = {0, 0, 0, 0};
+    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * nq1), (long long)Nq * Nf);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = rfe_search_by_projection_dev(c, dq, dproj, drad, pred_level ? dlev : nullptr, observed ? dobs : nullptr, Nq, df,
+                                               kpts ? (const float*)dk : nullptr, kpts ? nullptr : (const int32_t*)dk,
+                                               octave ? doct : nullptr, skip ? dsk : nullptr, Nf, nullptr, min_x, min_y, max_x, max_y,
+                                               th_high, cap, dasg, dbi, dbd, dsd, dst))) return rc;
+        RFE_HIP(c, hipMemcpyAsync(st, dst, 16, hipMemcpyDeviceToHost, s));
+        RFE_HIP(c, hipStreamSynchronize(s));
+        if (!st[3]) break;
+        cap = st[1];
+    }
+    if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection: candidate lists still overflow");
+    c->ps_cap = std::max(c->ps_cap, cap);
+    if (Nf > 0) RFE_HIP(c, hipMemcpyAsync(assign, dasg, (size_t)Nf * 4, hipMemcpyDeviceToHost, s));
+    if (Nq > 0 && best_idx) RFE_HIP(c, hipMemcpyAsync(best_idx, dbi, (size_t)Nq * 4, hipMemcpyDeviceToHost, s));
+    if (Nq > 0 && best_dist) RFE_HIP(c, hipMemcpyAsync(best_dist, dbd, (size_t)Nq * 4, hipMemcpyDeviceToHost, s));
+    if (Nq > 0 && second_dist) RFE_HIP(c, hipMemcpyAsync(second_dist, dsd, (size_t)Nq * 4, hipMemcpyDeviceToHost, s));
+    RFE_HIP(c, hipStreamSynchronize(s));
+    prof_collect(c);
+    if (stats) memcpy(stats, st, 16);
+    return st[0];
 }
 
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:438-530) for Np map points whose observed descriptors and CSR

@@ -134,6 +134,8 @@ struct rfe_ctx {
     void* ws_ptab = nullptr; size_t ws_ptab_bytes = 0; std::string ptab_key; std::vector<size_t> ptab_off;
     int32_t* sp_cnt = nullptr;           // [4][2] (count, tickets) of the fused detector tail (sp_post.hip: sp_tail_lat_kernel); zero between calls
     bool sp_cnt_dirty = false;           // the tail ran and its ranking kernel was not enqueued behind it (an error in between): zeroed before the next use
+    void* ws_ps = nullptr; size_t ws_ps_bytes = 0;   // rfe_search_by_projection*: grid, segment offsets, (index, distance) slots
+    int ps_cap = 0;                                  // rfe_search_by_projection (host form): most slots any call has needed
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -305,5 +307,29 @@ void launch_search_candidates(hipStream_t s, const float* q, int Nq, const float
                               const uint8_t* skip, int32_t* best_idx, float* best_dist, float* second_dist);
 void launch_distinctive(hipStream_t s, const float* desc, const int32_t* offsets, int total /*>= offsets[Np]*/, int Np, int maxn,
                         float* med /*[total] scratch*/, int32_t* best, float* median);
+
+// DescriptorDistance_sp (SPmatcher.cc:2184-2189) of one descriptor pair held as a float4 per lane, in the canonical order of search.hip,
+// proj_search.hip and the oracle: float differences, double accumulation, a lane's four elements then an xor butterfly over the wave
+__device__ __forceinline__ float desc_dist_wave(const float4 a, const float4 b) {
+    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
+    double p = 0.0;
+    p += (double)d0 * (double)d0; p += (double)d1 * (double)d1; p += (double)d2 * (double)d2; p += (double)d3 * (double)d3;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off);
+    return (float)sqrt(p);
+}
+
+// proj_search.hip: SearchByProjection1 on the device.  cell_start [770], cell_items [Nf], fxy [Nf,2], seg_off [Nq+1],
+// cand_idx / cand_dist [cand_cap]
+void launch_proj_grid(hipStream_t s, const float* kpts, const int32_t* kxy, int Nf, const int32_t* nf_dev, float min_x, float min_y,
+                      float inv_w, float inv_h, int32_t* cell_start, int32_t* cell_items, float* fxy);
+void launch_proj_count(hipStream_t s, const float* proj, const float* radius, const int32_t* pred_level, int Nq, const int32_t* cell_start,
+                       const int32_t* cell_items, const float* fxy, const int32_t* octave, float min_x, float min_y, float inv_w,
+                       float inv_h, int cand_cap, int32_t* seg_off, int32_t* cand_idx, int32_t* stats);
+void launch_proj_fill(hipStream_t s, const float* q, int Nq, const float* f, int Nf, const int32_t* seg_off, const int32_t* cand_idx,
+                      const uint8_t* skip, float* cand_dist);
+void launch_proj_resolve(hipStream_t s, const int32_t* seg_off, const int32_t* cand_idx, const float* cand_dist, const uint8_t* observed,
+                         int Nq, int Nf, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist, float* second_dist,
+                         int32_t* stats);
 
 }  // namespace rfe

@@ -14,15 +14,6 @@
 
 namespace rfe {
 
-__device__ __forceinline__ float desc_dist_wave(const float4 a, const float4 b) {
-    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-    double p = 0.0;
-    p += (double)d0 * (double)d0; p += (double)d1 * (double)d1; p += (double)d2 * (double)d2; p += (double)d3 * (double)d3;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off);
-    return (float)sqrt(p);
-}
-
 __global__ __launch_bounds__(256) void search_candidates_kernel(const float* __restrict__ q, int Nq, const float* __restrict__ f, int Nf,
                                                                 const int32_t* __restrict__ offsets, const int32_t* __restrict__ cand,
                                                                 const uint8_t* __restrict__ skip, int32_t* __restrict__ best_idx,
