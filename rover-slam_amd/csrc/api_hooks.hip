@@ -1,0 +1,191 @@
+// api_hooks.hip -- C ABI of librover_fe.so: the kernel-level test hooks (every rfe_k_*), which drive single kernels and stages of the two
+// pipelines through the forward passes' own code.
+#include <algorithm>
+#include "api_internal.h"
+
+using namespace rfe;
+
+// =====================================================================================
+// kernel-level test hooks
+// =====================================================================================
+extern "C" int rfe_k_conv3x3(rfe_ctx* c, const float* in, int B, int H, int W, int Cin, const float* w, const float* bias,
+                             int Cout, int relu, int pool, float* out) {
+    if (!c) return RFE_ERR_INVALID;
+    if ((Cin != 16 && Cin != 32 && Cin != 64 && Cin != 128) || (Cout % 64)) return fail(c, RFE_ERR_INVALID, "k_conv3x3: Cin in {16,32,64,128}, Cout % 64 == 0");
+    RFE_HIP(c, hipSetDevice(c->device));
+    std::vector<float> packed;
+    pack_conv3x3_weights(w, Cin, Cout, pool != 0, packed);
+    float *dw, *db;
+    int rc = ws_carve(c, &c->ws_tmp, &c->ws_tmp_bytes, [&](Bump& a) { dw = a.take<float>(packed.size()); db = a.take<float>(Cout); });
+    if (rc) return rc;
+    RFE_HIP(c, hipMemcpyAsync(dw, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, c->stream));
+    RFE_HIP(c, hipMemcpyAsync(db, bias, (size_t)Cout * 4, hipMemcpyHostToDevice, c->stream));
+    launch_conv3x3(c->stream, in, B, H, W, Cin, dw, db, Cout, relu != 0, pool != 0, out, 0);
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}
+
+extern "C" int rfe_k_linear(rfe_ctx* c, const float* a, int M, int K, const float* w, const float* bias, int N, int relu,
+                            float* out) {
+    if (!c) return RFE_ERR_INVALID;
+    if (K % 32) return fail(c, RFE_ERR_INVALID, "k_linear: K % 32 == 0 required");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dw, *db;
+    int rc = ws_carve(c, &c->ws_tmp, &c->ws_tmp_bytes, [&](Bump& a) { dw = a.take<float>((size_t)N * K); db = a.take<float>(N); });
+    if (rc) return rc;
+    RFE_HIP(c, hipMemcpyAsync(dw, w, (size_t)N * K * 4, hipMemcpyHostToDevice, c->stream));
+    if (bias) RFE_HIP(c, hipMemcpyAsync(db, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    GemmArgs g = gemm_plain(a, K, dw, K, bias ? db : nullptr, out, N, M, N, K);
+    g.relu = relu;
+    launch_gemm_nt(c->stream, g);
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}
+
+extern "C" int rfe_k_scoremap(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, float* scoremap,
+                              float* nms, float* descmap) {
+    int rc = sp_check(c, H, W, B, 1);
+    if (rc) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    SpBuffers b;
+    bool forked;
+    if ((rc = sp_forward_maps(c, img, H, W, stride, B, b, true, forked, false, 0, 0.0005f, true))) return rc;   // sp_cnt stays dirty: zeroed before the next forward
+    const size_t hw = (size_t)B * (H / 8 * 8) * (W / 8 * 8);   // maps are on the score-map frame: [B, 8*(H/8), 8*(W/8)]
+    if (scoremap) RFE_HIP(c, hipMemcpyAsync(scoremap, b.smap, hw * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (nms) RFE_HIP(c, hipMemcpyAsync(nms, b.nmap, hw * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (descmap) RFE_HIP(c, hipMemcpyAsync(descmap, b.dmap, hw / 64 * 256 * 4, hipMemcpyDeviceToDevice, c->stream));
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}
+
+// keypoint selection alone on a caller-provided post-NMS map [B,H,W] (device): candidates > thr, the top Kmax by (score descending, pixel
+// index ascending) or row-major order, through the forward's own launch_select -- so B selects the form (rank-all up to 4 frames, radix
+// select + rank sort above).  Lets the tests drive candidate counts and tie patterns no network output produces.
+extern "C" int rfe_k_select(rfe_ctx* c, const float* nms, int B, int H, int W, int Kmax, float thr, int topk_always, int32_t* n, int32_t* kxy,
+                            float* score) {
+    int rc = sp_check(c, H, W, B, Kmax);
+    if (rc) return rc;
+    if (!nms || !n || !kxy || !score) return fail(c, RFE_ERR_INVALID, "k_select: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    SpBuffers b;
+    if ((rc = sp_carve(c, B, H, W, b))) return rc;
+    launch_select(c->stream, nms, B, H, W, Kmax, thr, b.cand_score, b.cand_idx, n, kxy, score, (int32_t*)b.ss, topk_always != 0, b.sel_keys, b.sel_n);
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}
+
+// the same selection through the latency regime's key form (B <= 4): the map's candidates are appended as 64-bit keys in a scrambled order by a helper
+// kernel (one atomic per candidate -- the order sp_tail_lat_kernel's workgroups leave is just as arbitrary), then select_rankall_keys_kernel ranks them
+extern "C" int rfe_k_select_keys(rfe_ctx* c, const float* nms, int B, int H, int W, int Kmax, float thr, int topk_always, int32_t* n, int32_t* kxy,
+                                 float* score) {
+    int rc = sp_check(c, H, W, B, Kmax);
+    if (rc) return rc;
+    if (!nms || !n || !kxy || !score || B > 4) return fail(c, RFE_ERR_INVALID, "k_select_keys: null pointer or more than four frames");
+    RFE_HIP(c, hipSetDevice(c->device));
+    SpBuffers b;
+    if ((rc = sp_carve(c, B, H, W, b))) return rc;
+    if (!c->sp_cnt) RFE_HIP(c, hipMalloc((void**)&c->sp_cnt, 8 * sizeof(int32_t)));
+    RFE_HIP(c, hipMemsetAsync(c->sp_cnt, 0, 8 * sizeof(int32_t), c->stream));
+    launch_keys_from_map(c->stream, nms, B, H * W, thr, (unsigned long long*)b.cand_score, c->sp_cnt);
+    launch_select_keys(c->stream, (const unsigned long long*)b.cand_score, c->sp_cnt, B, H, W, Kmax, topk_always != 0, n, kxy, score);
+    c->sp_cnt_dirty = false;
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    int32_t left[8];
+    RFE_HIP(c, hipMemcpy(left, c->sp_cnt, sizeof(left), hipMemcpyDeviceToHost));
+    for (int q = 0; q < 8; ++q) if (left[q] != 0) return fail(c, RFE_ERR_HIP, "k_select_keys: the ranking kernel did not leave the candidate counters at zero");
+    return RFE_OK;
+}
+
+// x + ffn([x | second]) of one LightGlue block with the loaded weights (unfolded W1: `second` is the attention message), through
+// the same lg_ffn the forward uses -- so `rows` selects the path: >= 32768 rows take the 128x256 tiles with the LayerNorm + GELU
+// fused across ffn.0 / ffn.3, a few thousand rows the 64-row tiles with the stand-alone lg_ln_gelu pass.
+extern "C" int rfe_k_lightglue_ffn(rfe_ctx* c, int layer, int cross, const float* x, const float* second, int rows, float* out) {
+    int rc = lg_check(c, 1, 4, 4);
+    if (rc) return rc;
+    if (layer < 0 || layer >= LG_LAYERS || rows <= 0 || !x || !second || !out) return fail(c, RFE_ERR_INVALID, "k_lightglue_ffn: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    const int L = 1024, P = (rows + 2 * L - 1) / (2 * L);
+    LgBuffers b;
+    if ((rc = lg_carve(c, P, L, b))) return rc;
+    const LgLayerDev& Lw = c->lg.L[layer];
+    RFE_HIP(c, hipMemcpyAsync(out, x, (size_t)rows * 1024, hipMemcpyDeviceToDevice, c->stream));
+    if (cross) lg_ffn(c, b, out, second, rows, Lw.cw1, Lw.cb1, Lw.clng, Lw.clnb, Lw.cw2, Lw.cb2);
+    else lg_ffn(c, b, out, second, rows, Lw.w1, Lw.b1, Lw.lng, Lw.lnb, Lw.w2, Lw.b2);
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}
+
+extern "C" int rfe_k_attention(rfe_ctx* c, const float* q, const float* k, const float* v, int ld, float* out, int nseq, int Lq, int Lk,
+                               const int32_t* qlen, const int32_t* klen, const int32_t* kv_map, const float* rope) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!q || !k || !v || !out || nseq <= 0 || Lq <= 0 || Lk <= 0 || ld < 256) return fail(c, RFE_ERR_INVALID, "k_attention: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float* part = nullptr;
+    const size_t pb = lg_attention_part_bytes(nseq, Lq);
+    if (pb) RFE_HIP(c, hipMalloc((void**)&part, pb));
+    launch_lg_attention(c->stream, q, k, v, ld, out, nseq, Lq, Lk, qlen, klen, kv_map, part, rope, c->opt_lg_fp16x2);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (part) (void)hipFree(part);
+    RFE_HIP(c, e);
+    return RFE_OK;
+}
+
+extern "C" int rfe_k_set_lightglue_tap(rfe_ctx* c, int pair, float* x0, float* x1, float* scores) {
+    if (!c) return RFE_ERR_INVALID;
+    if (pair < 0) { c->tap.armed = false; return RFE_OK; }
+    c->tap.armed = true; c->tap.pair = pair; c->tap.x0 = x0; c->tap.x1 = x1; c->tap.scores = scores;
+    return RFE_OK;
+}
+
+// projection + attention of layer `layer`'s self block on caller-provided token rows x [nseq * L, 256] with the rotary table csn [nseq * L, 32] (cos, sin),
+// through the forward's own lg_self_qkv_attention -- so nseq * L selects the path (throughput: rotary in gemm.hip's epilogue + lg_attention_dma_kernel;
+// one / few pairs: gemm_lat.hip + lg_attention_lat_kernel; shapes neither takes: plain epilogue + rotary on load).  qkv_out [nseq * L, 768], ctx_out [nseq * L, 256];
+// *qk_rotated = 1 when qkv_out's q | k columns are rotated.
+extern "C" int rfe_k_lightglue_self_attention(rfe_ctx* c, int layer, const float* x, const float* csn, const int32_t* lens, int nseq, int L,
+                                              float* qkv_out, float* ctx_out, int32_t* qk_rotated) {
+    int rc = lg_check(c, 1, 4, 4);
+    if (rc) return rc;
+    if (layer < 0 || layer >= LG_LAYERS || nseq <= 0 || L <= 0 || (L % 4) || !x || !csn || !lens) return fail(c, RFE_ERR_INVALID, "k_lightglue_self_attention: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    const int P = (nseq + 1) / 2;
+    LgBuffers b;
+    if ((rc = lg_carve(c, P, L, b))) return rc;
+    const bool rot = lg_self_qkv_attention(c, b, c->lg.L[layer], x, csn, lens, nseq, L);
+    RFE_HIP(c, hipGetLastError());
+    if (qkv_out) RFE_HIP(c, hipMemcpyAsync(qkv_out, b.qkv, (size_t)nseq * L * 768 * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (ctx_out) RFE_HIP(c, hipMemcpyAsync(ctx_out, b.ctx, (size_t)nseq * L * 256 * 4, hipMemcpyDeviceToDevice, c->stream));
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    if (qk_rotated) *qk_rotated = rot ? 1 : 0;
+    return RFE_OK;
+}
+
+extern "C" int rfe_k_lightglue_taps(rfe_ctx* c, const float* k0n, const float* k1n, const float* d0, const float* d1,
+                                    int M, int N, float* x0, float* x1, float* scores) {
+    int rc = lg_check(c, 1, M, N);
+    if (rc) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    const int L = ((std::max(M, N) + 3) / 4) * 4, cap = std::min(M, N);
+    LgBuffers b;
+    float *sc, *dms; int32_t *dm, *dn, *dS, *dp;
+    if ((rc = lg_carve(c, 1, L, b, [&](Bump& a) {
+             sc = a.take<float>((size_t)L * L);
+             dm = a.take<int32_t>(1); dn = a.take<int32_t>(1); dS = a.take<int32_t>(1);
+             dp = a.take<int32_t>((size_t)cap * 2); dms = a.take<float>(cap);
+         }))) return rc;
+    RFE_HIP(c, hipMemcpyAsync(dm, &M, 4, hipMemcpyHostToDevice, c->stream));
+    RFE_HIP(c, hipMemcpyAsync(dn, &N, 4, hipMemcpyHostToDevice, c->stream));
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = lg_stage(c, b, k0n, k1n, d0, d1, dm, dn, 1, M, N, L))) return rc;
+    if ((rc = lg_forward(c, b, 1, L, 0.1f, cap, dS, dp, dms, scores ? sc : nullptr, false, true))) return rc;
+    if (x0) RFE_HIP(c, hipMemcpyAsync(x0, b.x, (size_t)M * 1024, hipMemcpyDeviceToDevice, c->stream));
+    if (x1) RFE_HIP(c, hipMemcpyAsync(x1, b.x + (size_t)L * 256, (size_t)N * 1024, hipMemcpyDeviceToDevice, c->stream));
+    if (scores) RFE_HIP(c, hipMemcpy2DAsync(scores, (size_t)N * 4, sc, (size_t)L * 4, (size_t)N * 4, M, hipMemcpyDeviceToDevice, c->stream));
+    RFE_HIP(c, hipStreamSynchronize(c->stream));
+    return RFE_OK;
+}

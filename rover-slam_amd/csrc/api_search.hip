@@ -1,0 +1,250 @@
+// api_search.hip -- C ABI of librover_fe.so: the descriptor helpers of the callers' classic searches (L2 matrix, binarisation, candidate
+// scan, SearchByProjection1, distinctive descriptors).
+#include <string.h>
+#include <algorithm>
+#include "api_internal.h"
+
+using namespace rfe;
+
+// =====================================================================================
+// descriptor helpers of the callers' classic searches.  The "_dev" forms take device pointers and are
+// asynchronous on the ctx stream (descriptors usually ARE device resident: they come out of rfe_extract_u8_dev /
+// rfe_stereo_frame_dev); the host-pointer forms validate, stage through ws_io and call them.
+// =====================================================================================
+// Every pair below: one argument check for both forms (it passes an empty problem without a look at the pointers, which are the caller's,
+// whichever side they live on); the host form adds the checks only it can make, stages its arrays and calls the device form.
+static int l2_check(rfe_ctx* c, const void* a, int M, const void* b, int N, const void* out) {
+    if (!c) return RFE_ERR_INVALID;
+    if (M < 0 || N < 0 || (M > 0 && N > 0 && (!a || !b || !out))) return fail(c, RFE_ERR_INVALID, "l2_distance_matrix: bad argument");
+    return RFE_OK;
+}
+extern "C" int rfe_l2_distance_matrix_dev(rfe_ctx* c, const float* a, int M, const float* b, int N, float* out) {
+    int rc = l2_check(c, a, M, b, N, out);
+    if (rc || M == 0 || N == 0) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    { ProfScope ps(c, "l2_matrix"); launch_l2_matrix(c->stream, a, M, b, N, out); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+extern "C" int rfe_l2_distance_matrix(rfe_ctx* c, const float* a, int M, const float* b, int N, float* out) {
+    int rc = l2_check(c, a, M, b, N, out);
+    if (rc || M == 0 || N == 0) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *da, *db, *dout;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(da, a, (size_t)M * 256); io.in(db, b, (size_t)N * 256);
+    io.out(dout, out, (size_t)M * N);
+    if ((rc = io.upload())) return rc;
+    if ((rc = rfe_l2_distance_matrix_dev(c, da, M, db, N, dout))) return rc;
+    return io.download();
+}
+
+static int binarize_check(rfe_ctx* c, const void* desc, int rows, const void* out) {
+    if (!c) return RFE_ERR_INVALID;
+    if (rows < 0 || (rows > 0 && (!desc || !out))) return fail(c, RFE_ERR_INVALID, "binarize_descriptors: bad argument");
+    return RFE_OK;
+}
+extern "C" int rfe_binarize_descriptors_dev(rfe_ctx* c, const float* desc, int rows, uint8_t* out) {
+    int rc = binarize_check(c, desc, rows, out);
+    if (rc || rows == 0) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    launch_binarize(c->stream, desc, rows, out);
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+extern "C" int rfe_binarize_descriptors(rfe_ctx* c, const float* desc, int rows, uint8_t* out) {
+    int rc = binarize_check(c, desc, rows, out);
+    if (rc || rows == 0) return rc;
+    RFE_HIP(c, hipSetDevice(c->device));
+    float* dd; uint8_t* dout;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dd, desc, (size_t)rows * 256);
+    io.out(dout, out, (size_t)rows * 256);
+    if ((rc = io.upload())) return rc;
+    if ((rc = rfe_binarize_descriptors_dev(c, dd, rows, dout))) return rc;
+    return io.download();
+}
+
+// best / second-best scan of SPmatcher::SearchByProjection1 (src/Matchers/SPmatcher.cc:1218-1248) over device-resident CSR
+// candidate lists.  The lists cannot be validated from the host without a synchronisation: the kernel ignores candidate
+// indices outside [0, Nf); offsets must be non-decreasing with offsets[0] = 0 (the caller's contract, as for the host form).
+static int sc_check(rfe_ctx* c, const void* q, int Nq, int Nf, const void* offsets, const void* best_idx, const void* best_dist, const void* second_dist) {
+    if (!c) return RFE_ERR_INVALID;
+    if (Nq < 0 || Nf < 0) return fail(c, RFE_ERR_INVALID, "search_candidates: negative count");
+    if (Nq == 0) return RFE_OK;
+    if (!q || !offsets || !best_idx || !best_dist || !second_dist) return fail(c, RFE_ERR_INVALID, "search_candidates: null pointer");
+    return RFE_OK;
+}
+extern "C" int rfe_search_candidates_dev(rfe_ctx* c, const float* q, int Nq, const float* f, int Nf, const int32_t* offsets,
+                                         const int32_t* cand, const uint8_t* skip, int32_t* best_idx, float* best_dist,
+                                         float* second_dist) {
+    int rc = sc_check(c, q, Nq, Nf, offsets, best_idx, best_dist, second_dist);
+    if (rc || Nq == 0) return rc;
+    if (Nf > 0 && (!f || !cand)) return fail(c, RFE_ERR_INVALID, "search_candidates: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    { ProfScope ps(c, "search_candidates");
+      launch_search_candidates(c->stream, q, Nq, f, Nf, offsets, cand, skip, best_idx, best_dist, second_dist); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_candidates(rfe_ctx* c, const float* q, int Nq, const float* f, int Nf, const int32_t* offsets,
+                                     const int32_t* cand, const uint8_t* skip, int32_t* best_idx, float* best_dist,
+                                     float* second_dist) {
+    int rc = sc_check(c, q, Nq, Nf, offsets, best_idx, best_dist, second_dist);
+    if (rc || Nq == 0) return rc;
+    if (offsets[0] != 0) return fail(c, RFE_ERR_INVALID, "search_candidates: offsets[0] must be 0");
+    for (int i = 0; i < Nq; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(c, RFE_ERR_INVALID, "search_candidates: offsets must be non-decreasing");
+    const int nnz = offsets[Nq];
+    if (nnz > 0 && (!cand || !f)) return fail(c, RFE_ERR_INVALID, "search_candidates: null candidate list");
+    for (int k = 0; k < nnz; ++k)
+        if (cand[k] < 0 || cand[k] >= Nf) return fail(c, RFE_ERR_INVALID, "search_candidates: candidate index out of range");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dq, *df, *dbd, *dsd; int32_t *doff, *dc, *dbi; uint8_t* dsk;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dq, q, (size_t)Nq * 256); io.in(df, f, f ? (size_t)Nf * 256 : 0); io.in(doff, offsets, (size_t)Nq + 1); io.in(dc, cand, nnz);
+    io.in_opt(dsk, skip, Nf);
+    io.out(dbi, best_idx, Nq); io.out(dbd, best_dist, Nq); io.out(dsd, second_dist, Nq);
+    if ((rc = io.upload())) return rc;
+    if ((rc = rfe_search_candidates_dev(c, dq, Nq, df, Nf, doff, dc, dsk, dbi, dbd, dsd))) return rc;
+    return io.download();
+}
+
+// SPmatcher::SearchByProjection1, left-camera branch (src/Matchers/SPmatcher.cc:1190-1283), device resident: grid, candidate lists, scan and
+// the sequential assignment (proj_search.hip).  Four kernels on the ctx stream, nothing read back.
+static int ps_check(rfe_ctx* c, const void* q, const void* proj, const void* radius, int Nq, const void* f, const void* kpts, const void* kxy,
+                    int Nf, float min_x, float min_y, float max_x, float max_y, int cand_cap, const void* assign) {
+    if (Nq < 0 || Nq > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nq outside 0..16384");
+    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nf outside 0..4096");
+    if (!(max_x > min_x) || !(max_y > min_y)) return fail(c, RFE_ERR_INVALID, "search_by_projection: empty image bounds");
+    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_by_projection: negative cand_cap");
+    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pass exactly one of kpts and kxy");
+    if ((Nq > 0 && (!q || !proj || !radius)) || (Nf > 0 && (!f || !assign))) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection_dev(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
+                                            const uint8_t* observed, int Nq, const float* f, const float* kpts, const int32_t* kxy,
+                                            const int32_t* octave, const uint8_t* skip, int Nf, const int32_t* nf_dev, float min_x,
+                                            float min_y, float max_x, float max_y, float th_high, int cand_cap, int32_t* assign,
+                                            int32_t* best_idx, float* best_dist, float* second_dist, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, cand_cap, assign);
+    if (rc) return rc;
+    if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    // ws_ps: the grid (cell starts, items, positions), the segment offsets and cand_cap (index, distance) slots -- one element at least of each
+    int32_t *cell_start, *cell_items, *seg_off, *cand_idx; float *fxy, *cand_dist;
+    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
+        const size_t nf1 = (size_t)std::max(Nf, 1), cap1 = (size_t)std::max(cand_cap, 1);
+        cell_start = a.take<int32_t>(770); cell_items = a.take<int32_t>(nf1); fxy = a.take<float>(nf1 * 2);
+        seg_off = a.take<int32_t>((size_t)Nq + 1); cand_idx = a.take<int32_t>(cap1); cand_dist = a.take<float>(cap1);
+    });
+    if (rc) return rc;
+    const float inv_w = 32.f / (max_x - min_x), inv_h = 24.f / (max_y - min_y);      // Frame::mfGridElementWidthInv / HeightInv
+    hipStream_t s = c->stream;
+    { ProfScope ps(c, "ps_grid"); launch_proj_grid(s, kpts, kxy, Nf, nf_dev, min_x, min_y, inv_w, inv_h, cell_start, cell_items, fxy); }
+    { ProfScope ps(c, "ps_count");
+      launch_proj_count(s, proj, radius, pred_level, Nq, cell_start, cell_items, fxy, octave, min_x, min_y, inv_w, inv_h, cand_cap, seg_off,
+                        cand_idx, stats); }
+    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist); }
+    { ProfScope ps(c, "ps_resolve");
+      launch_proj_resolve(s, seg_off, cand_idx, cand_dist, observed, Nq, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
+                                        const uint8_t* observed, int Nq, const float* f, const float* kpts, const int32_t* kxy,
+                                        const int32_t* octave, const uint8_t* skip, int Nf, float min_x, float min_y, float max_x,
+                                        float max_y, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist,
+                                        float* second_dist, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, 0, assign);
+    if (rc) return rc;
+    auto fin = [](float v) { return v - v == 0.f; };
+    if (!fin(min_x) || !fin(min_y) || !fin(max_x) || !fin(max_y) || !fin(th_high))
+        return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite argument");
+    for (int i = 0; i < Nq; ++i) {
+        if (!fin(proj[2 * i]) || !fin(proj[2 * i + 1]) || !fin(radius[i])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite projection or radius");
+        if (pred_level && (pred_level[i] < 0 || pred_level[i] >= RFE_MAX_LEVELS)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pred_level outside 0..15");
+    }
+    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite keypoint");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dq, *dproj, *drad, *df, *dbd, *dsd; int32_t *dlev, *doct, *dasg, *dbi, *dst; uint8_t *dobs, *dsk; float* dkp; int32_t* dkx;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dq, q, (size_t)Nq * 256); io.in(dproj, proj, (size_t)Nq * 2); io.in(drad, radius, Nq); io.in_opt(dlev, pred_level, Nq); io.in_opt(dobs, observed, Nq);
+    io.in(df, f, (size_t)Nf * 256); io.in_opt(dkp, kpts, (size_t)Nf * 2); io.in_opt(dkx, kxy, (size_t)Nf * 2); io.in_opt(doct, octave, Nf); io.in_opt(dsk, skip, Nf);
+    io.out(dasg, assign, Nf); io.out(dbi, best_idx, Nq); io.out(dbd, best_dist, Nq); io.out(dsd, second_dist, Nq); io.scratch(dst, 4);
+    if ((rc = io.upload())) return rc;
+    hipStream_t s = c->stream;
+    // the candidate total is known on the device only: run with the largest slot count used so far (at least 16 per map point) and,
+    // when the lists need more, once again with exactly what they need
+    int32_t st[4] = {0, 0, 0, 0};
+    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Nq, 1)), (long long)Nq * Nf);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = rfe_search_by_projection_dev(c, dq, dproj, drad, dlev, dobs, Nq, df, dkp, dkx, doct, dsk, Nf, nullptr, min_x, min_y, max_x, max_y,
+                                               th_high, cap, dasg, dbi, dbd, dsd, dst))) return rc;
+        RFE_HIP(c, hipMemcpyAsync(st, dst, 16, hipMemcpyDeviceToHost, s));
+        RFE_HIP(c, hipStreamSynchronize(s));
+        if (!st[3]) break;
+        cap = st[1];
+    }
+    if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection: candidate lists still overflow");
+    c->ps_cap = std::max(c->ps_cap, cap);
+    if ((rc = io.download())) return rc;
+    if (stats) memcpy(stats, st, 16);
+    return st[0];
+}
+
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:438-530) for Np map points whose observed descriptors and CSR
+// offsets live on the device.  `total` >= offsets[Np] (the number of descriptors, grid size) and `maxn` >= the largest
+// observation count (LDS row, <= 8192) come from the caller, who built the lists; a point with more observations than maxn
+// rounded up to a power of two is reported as best = -2 instead of computed.
+static int dd_check(rfe_ctx* c, const void* offsets, int Np, const void* best, const void* median) {
+    if (Np < 0) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: negative count");
+    if (Np == 0) return RFE_OK;
+    if (!offsets || !best || !median) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: null pointer");
+    return RFE_OK;
+}
+extern "C" int rfe_distinctive_descriptors_dev(rfe_ctx* c, const float* desc, const int32_t* offsets, int Np, int total, int maxn,
+                                               int32_t* best, float* median) {
+    if (!c) return RFE_ERR_INVALID;
+    if (total < 0 || maxn < 0) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: negative count");
+    int rc = dd_check(c, offsets, Np, best, median);
+    if (rc || Np == 0) return rc;
+    if (total > 0 && !desc) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: null pointer");
+    if (maxn > 8192) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: more than 8192 observations of one map point");
+    RFE_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_ws(c, &c->ws_tmp, &c->ws_tmp_bytes, al((size_t)std::max(total, 1) * 4)))) return rc;   // per-descriptor medians
+    { ProfScope ps(c, "distinctive");
+      launch_distinctive(c->stream, desc, offsets, total, Np, std::max(maxn, 1), (float*)c->ws_tmp, best, median); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_distinctive_descriptors(rfe_ctx* c, const float* desc, const int32_t* offsets, int Np, int32_t* best,
+                                           float* median) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = dd_check(c, offsets, Np, best, median);
+    if (rc || Np == 0) return rc;
+    if (offsets[0] != 0) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: offsets[0] must be 0");
+    int maxn = 0;
+    for (int p = 0; p < Np; ++p) {
+        const int n = offsets[p + 1] - offsets[p];
+        if (n < 0) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: offsets must be non-decreasing");
+        maxn = std::max(maxn, n);
+    }
+    if (maxn > 8192) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: more than 8192 observations of one map point");
+    const int total = offsets[Np];
+    if (total > 0 && !desc) return fail(c, RFE_ERR_INVALID, "distinctive_descriptors: null descriptors");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dd, *dmedian; int32_t *doff, *dbest;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dd, desc, (size_t)total * 256); io.in(doff, offsets, (size_t)Np + 1);
+    io.out(dbest, best, Np); io.out(dmedian, median, Np);
+    if ((rc = io.upload())) return rc;
+    if ((rc = rfe_distinctive_descriptors_dev(c, dd, doff, Np, total, maxn, dbest, dmedian))) return rc;
+    return io.download();
+}

@@ -9,7 +9,7 @@
 // attention contexts and LayerNorm'd activations are O(1 .. 100).  SuperPoint never takes this path (bit-exact by fmaf-chain
 // equivalence).  The reference runs these Linears inside Session::Run(lightglue_sim.onnx), src/Matchers/lightglue_onnx.cpp:210-214.
 //
-// Weights (B) are split ONCE at load time into two fp16 planes (rfe_api.hip: set_lg_upload); activations (A) are split while they
+// Weights (B) are split ONCE at load time into two fp16 planes (api_weights.hip: set_lg_upload); activations (A) are split while they
 // are staged into LDS (3 VALU per element pair, h2_split.h; LNA: LayerNorm + GELU of ffn.3's operand is applied in the same pass, before the
 // split).  Tile 128 x 256 x 32, 256 threads = 2x2 waves of 64 x 128, two workgroups per CU (as gemm.hip); LDS: per plane [rows][32
 // fp16] = 64-byte rows of four 16-byte slots, slot s = 2 c + h stored at s ^ ((row >> 2) & 3) -- ds_read_b128 fragment reads and the

@@ -20,7 +20,7 @@
 #include <vector>
 #include "../../include/rover_fe.h"
 
-// the two C-ABI helpers rfe_k_onnx_convert leans on live in rfe_api.hip (GPU code); the driver links the reader alone
+// the two C-ABI helpers rfe_k_onnx_convert leans on live in rfe_internal.h and api_weights.hip (GPU code); the driver links the reader alone
 extern "C" rfe_hparams rfe_default_hparams(void) { rfe_hparams h; memset(&h, 0, sizeof h); return h; }
 extern "C" int64_t rfe_weight_count(int kind) { return kind == RFE_KIND_SUPERPOINT ? 1300865 : kind == RFE_KIND_LIGHTGLUE ? 11321153 : -1; }
 extern "C" int rfe_k_onnx_convert(const char* path, int kind, int weights_only, float* blob, rfe_hparams* hp, char* err, int errlen);
