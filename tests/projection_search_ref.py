@@ -175,8 +175,9 @@ def static_scan(oracle, q, f, lists, skip=None):
     return oracle.search_candidates(np.ascontiguousarray(q, F32), np.ascontiguousarray(f, F32), off, cand, skip)
 
 
-def make_case(seed, W=160, H=120, Nf=300, Nq=400, ncent=40, th=3):
-    """The contention case: clustered descriptors, about 2.7 map points per source feature, an exact-tie pair (features 3 and 7)."""
+def make_case(seed, W=160, H=120, Nf=300, Nq=400, ncent=40, th=3, src_hi=None):
+    """The contention case: clustered descriptors, about 2.7 map points per source feature (src_hi=None: the sources are the first half of
+    the features), an exact-tie pair (features 3 and 7)."""
     rng = np.random.default_rng(seed)
     kxy = np.stack([rng.integers(0, W, Nf), rng.integers(0, H, Nf)], 1).astype(np.int32)
     kxy[3] = (min(int(kxy[3, 0]), W - 12), min(int(kxy[3, 1]), H - 12))   # the tie pair stays inside the grid (x >= W - 2.5 is column 32)
@@ -186,7 +187,7 @@ def make_case(seed, W=160, H=120, Nf=300, Nq=400, ncent=40, th=3):
     desc = centre[cluster] + F32(0.03) * rng.standard_normal((Nf, 256)).astype(F32)
     desc = (desc / np.linalg.norm(desc, axis=1, keepdims=True)).astype(F32)
     desc[7] = desc[3]
-    src = rng.integers(0, Nf // 2, Nq)
+    src = rng.integers(0, Nf // 2 if src_hi is None else src_hi, Nq)
     src[Nq // 2] = 3                                             # somebody wants the tie pair, whatever the draw
     q = (desc[src] + F32(0.02) * rng.standard_normal((Nq, 256)).astype(F32)).astype(F32)
     proj = (kxy[src].astype(F32) + rng.uniform(-3, 3, (Nq, 2)).astype(F32)).astype(F32)
@@ -195,6 +196,42 @@ def make_case(seed, W=160, H=120, Nf=300, Nq=400, ncent=40, th=3):
     observed = (rng.random(Nq) < 0.9).astype(np.uint8)
     return {"W": W, "H": H, "bounds": (0.0, 0.0, float(W), float(H)), "kxy": kxy, "kpts": kxy.astype(F32), "desc": np.ascontiguousarray(desc),
             "q": np.ascontiguousarray(q), "proj": np.ascontiguousarray(proj), "radius": radius, "skip": skip, "observed": observed, "src": src}
+
+
+PLANTED_OUT = ((-20.0, 100.0), (100.0, -15.0))                              # scaled coordinate -0.5: roundf gives -1, outside the grid
+PLANTED_IN = ((-19.75, 100.0), (100.0, -14.75), (-19.75, -14.75))           # scaled coordinate -0.4875: cell 0
+PLANTED = (PLANTED_OUT[0], PLANTED_IN[0], PLANTED_OUT[1], PLANTED_IN[1], PLANTED_IN[2])      # the last five features, in this order
+PLANTED_PROJ = ((-12.0, 100.0), (100.0, -8.0), (-12.0, -8.0))               # the last three map points, radius 12
+
+
+def off_origin(c, seed):
+    """A 640 x 480 case of make_case moved to the bounds (-10, -5, 630, 475) of an undistorted image, with sub-pixel positions.  The cells
+    are 20 pixels wide and high and fl32(0.05) * 10 k is an exact half for odd k, so a feature at a whole pixel 10 k from the origin sits
+    on a rounding tie, where roundf (half away from zero) and round-half-to-even part.  Every position gets a fraction from {0, .25, .5,
+    .75} (exact in fp32; the tie pair keeps 0), the last five features are PLANTED on the negative side, and the last three map points
+    look at them.  Float positions only: no kxy."""
+    assert c["bounds"] == (0.0, 0.0, 640.0, 480.0)
+    rng = np.random.default_rng(seed)
+    shift = np.array([-10.0, -5.0], F32)
+    frac = (rng.integers(0, 4, c["kxy"].shape) * 0.25).astype(F32)
+    frac[3] = frac[7] = 0
+    kpts = (c["kxy"].astype(F32) + shift + frac).astype(F32)
+    kpts[-5:] = np.array(PLANTED, F32)
+    proj = (c["proj"] + shift).astype(F32)
+    proj[-3:] = np.array(PLANTED_PROJ, F32)
+    radius = c["radius"].copy()
+    radius[-3:] = F32(12.0)
+    out = {k: v for k, v in c.items() if k != "kxy"}
+    out.update(bounds=(-10.0, -5.0, 630.0, 475.0), kpts=np.ascontiguousarray(kpts), proj=np.ascontiguousarray(proj), radius=radius)
+    return out
+
+
+def on_half(kpts, bounds):
+    """[Nf] bool: the scaled x or y coordinate of the feature is exactly k + 0.5 (a rounding tie in PosInGrid)"""
+    min_x, min_y, inv_w, inv_h = _inv(bounds)
+    k = np.asarray(kpts, F32).reshape(-1, 2)
+    sx = ((k[:, 0] - min_x).astype(F32) * inv_w).astype(F32); sy = ((k[:, 1] - min_y).astype(F32) * inv_h).astype(F32)
+    return (np.abs(sx - np.trunc(sx)) == F32(0.5)) | (np.abs(sy - np.trunc(sy)) == F32(0.5))
 
 
 def case_lists(c, octave=None, pred_level=None):

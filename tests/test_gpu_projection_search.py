@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import projection_search_ref as PS
-from test_projection_search_ref import build_driver, chain_case, solved, write_driver_case
+from test_projection_search_ref import build_driver, chain_case, solved, solved_big, solved_levels, write_driver_case
 from rover_slam_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +28,8 @@ def same(got, ref, keys=KEYS):
 
 
 def host(ctx, c, **kw):
-    a = dict(kxy=c["kxy"], skip=c.get("skip"), observed=c.get("observed"))
+    a = dict(skip=c.get("skip"), observed=c.get("observed"))
+    a.update({"kxy": c["kxy"]} if "kxy" in c else {"kpts": c["kpts"]})           # a case without kxy has float positions only
     a.update(kw)
     return ctx.search_by_projection(c["q"], c["proj"], c["radius"], c["desc"], c["bounds"], **a)
 
@@ -255,3 +256,110 @@ def test_drop_in_helper(tmp_path, oracle):
     assert r.returncode == 0, r.stdout + r.stderr
     out = np.fromfile(str(tmp_path / "rig_out.bin"), np.int32)
     assert out[0] == -1 and np.array_equal(out[1:], np.where(prior >= 0, -2, -1))
+
+
+# ================================================================ past one pass of the 1024-thread loops ("Sizes covered")
+# A, B, C, B-levels and chain-1024 of tests/test_projection_search_ref.py: every 1024-stride loop takes further trips, a count thread
+# owns several map points (or none), the LDS arrays are full, the bounds do not start at (0, 0) and the rounding of PosInGrid decides.
+def pos(c):
+    return {"kxy": c["kxy"]} if "kxy" in c else {"kpts": c["kpts"]}
+
+
+def empty(o):
+    return (o["assign"] == -1).all() and (o["best_idx"] == -1).all() and (o["best_dist"] == 256).all() and (o["second_dist"] == 256).all()
+
+
+# ---------------------------------------------------------------- 10. host form against the restatement
+@pytest.mark.parametrize("name", ("A", "B", "C", "chain-1024"))
+def test_big_host_form_vs_restatement(ctx, oracle, name):
+    c, lists, seq, _, rounds = solved_big(oracle, name)
+    got = host(ctx, c)
+    st = got["stats"]
+    print(f"{name}: nmatches {st[0]}, candidates {st[1]}, rounds {st[2]} (restatement {rounds}), overflow {st[3]}")
+    same(got, seq)
+    assert st[0] == seq["nmatches"] and st[1] == sum(len(l) for l in lists) and st[3] == 0
+    if name == "chain-1024":
+        assert st[2] >= 64 and np.array_equal(got["best_idx"][1000:1064], c["order"])
+    else:
+        assert st[2] == rounds
+
+
+# ---------------------------------------------------------------- 11. device form: exactly the slots, one too few, the count from the device
+@pytest.mark.parametrize("name", ("B", "C"))
+def test_big_device_form(ctx, oracle, name):
+    c, lists, seq, _, rounds = solved_big(oracle, name)
+    total, Nf = sum(len(l) for l in lists), len(c["kpts"])
+    if name == "C":
+        assert Nf == 4096
+        d = dev(ctx, c, total, skip=c["skip"], observed=c["observed"], nf_dev=np.array([4096], np.int32), **pos(c))
+    else:                            # 4093 features and three zero rows behind them: *nf_dev = 4093 keeps the rows at (0, 0) out of the grid
+        assert Nf == 4093
+        pad = lambda a: np.concatenate([a, np.zeros((3,) + a.shape[1:], a.dtype)])   # noqa: E731
+        d = dev(ctx, c, total, kpts=pad(c["kpts"]), skip=pad(c["skip"]), observed=c["observed"], nf_dev=np.array([Nf], np.int32), Nf=4096,
+                desc=pad(c["desc"]))
+        assert (d["assign"][Nf:] == -1).all()
+        d["assign"] = d["assign"][:Nf]
+    same(d, seq)
+    assert list(d["stats"]) == [seq["nmatches"], total, rounds, 0]
+    o = dev(ctx, c, total - 1, skip=c["skip"], observed=c["observed"], **pos(c))
+    assert o["stats"][3] == 1 and o["stats"][1] == total and o["stats"][0] == 0 and empty(o)
+
+
+# ---------------------------------------------------------------- 12. the level gate with every octave slot in use
+def test_big_levels(ctx, oracle):
+    c, octave, level, lists, _, ref = solved_levels(oracle)
+    total = sum(len(l) for l in lists)
+    h = host(ctx, c, octave=octave, pred_level=level)
+    same(h, ref)
+    assert h["stats"][1] == total and h["stats"][3] == 0
+    d = dev(ctx, c, total, kxy=c["kxy"], skip=c["skip"], observed=c["observed"], octave=octave, pred_level=level)
+    same(d, ref)
+    assert np.array_equal(d["stats"], h["stats"])
+
+
+# ---------------------------------------------------------------- 13. one ctx across sizes: ws_ps after growth, the remembered ps_cap
+def test_big_workspace_reuse(oracle):
+    c = capi.Context(0)
+    try:
+        first = None
+        for name in ("C", 0, "B", "C"):
+            case, lists, seq, _, rounds = solved(oracle, name) if name == 0 else solved_big(oracle, name)
+            got = host(c, case)
+            same(got, seq)
+            assert list(got["stats"]) == [seq["nmatches"], sum(len(l) for l in lists), rounds, 0], name
+            if name == "C" and first is None:
+                first = got
+        for k in KEYS + ("stats",):
+            assert np.array_equal(got[k], first[k]), k           # the second C, bit for bit
+    finally:
+        c.close()
+
+
+# ---------------------------------------------------------------- 14. no contention at B: the existing scan kernel
+def test_big_unobserved_map_points_equal_search_candidates(ctx, oracle):
+    c, lists, _, _, _ = solved_big(oracle, "B")
+    got = host(ctx, c, observed=np.zeros(len(lists), np.uint8))
+    off, cand = PS.to_csr(lists)
+    bi, bd, sd = ctx.search_candidates(c["q"], c["desc"], off, cand, c["skip"])
+    assert np.array_equal(got["best_idx"], bi) and np.array_equal(got["best_dist"], bd) and np.array_equal(got["second_dist"], sd)
+    assert got["stats"][2] <= 2 and got["nmatches"] == int((bd <= PS.TH_HIGH).sum())
+    last = np.full(len(c["kpts"]), -1, np.int32)
+    for i in np.flatnonzero(bd <= PS.TH_HIGH):
+        last[bi[i]] = i
+    assert np.array_equal(got["assign"], last)
+
+
+# ---------------------------------------------------------------- 15. the drop-in helper at B: off-origin bounds through the Frame members
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_big_drop_in_helper(tmp_path, oracle):
+    c, lists, seq, _, _ = solved_big(oracle, "B")
+    exe = build_driver(tmp_path)
+    sel, prior = write_driver_case(str(tmp_path / "case.bin"), c)
+    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = np.fromfile(str(tmp_path / "out.bin"), np.int32)
+    assert out[0] == seq["nmatches"] and len(out) == 1 + len(c["kpts"])
+    want = np.where(seq["assign"] >= 0, sel[np.maximum(seq["assign"], 0)], np.where(prior >= 0, -2, -1))
+    assert np.array_equal(out[1:], want)
+    assert (out[1:][prior == 3] == -2).all()                 # a feature that had an observed map point keeps it
+    assert ((out[1:] >= 0) & (prior == 0)).any()             # one without observations is overwritten

@@ -117,6 +117,131 @@ def chain_case():
             "radius": np.full((80,), 12, np.float32), "order": np.argsort(rank).astype(np.int32)}
 
 
+def chain_1024_case():
+    """chain_case() behind 1000 map points whose lists are empty: the 64 links of the chain are map points 1000..1063, so in the resolve
+    kernel every blocker up to map point 1023 belongs to another trip of the 1024-thread loop than the map points it blocks from 1024 on"""
+    c = chain_case()
+    n = 1000
+    return dict(c, q=np.ascontiguousarray(np.concatenate([np.repeat(c["q"][:1], n, axis=0), c["q"]])),
+                proj=np.ascontiguousarray(np.concatenate([np.tile(np.float32([5.0, 5.0]), (n, 1)), c["proj"]])),
+                radius=np.concatenate([np.full((n,), 2, np.float32), c["radius"]]))
+
+
+# ---------------------------------------------------------------- past one pass of the 1024-thread loops (DESIGN.md 6d, "Sizes covered")
+PS_INFLIGHT = 8                 # proj_search.hip: candidate rows in flight per wave
+BIG = {"A": dict(seed=0, Nf=1100, Nq=1100),       # a second trip of every 1024-stride loop; two map points per count thread, threads >= 550 idle
+       "B": dict(seed=2, Nf=4093, Nq=2500),       # Nf odd and just under the limit; three per count thread, a partial last owner; off_origin
+       "C": dict(seed=1, Nf=4096, Nq=16384)}      # both documented limits: sixteen per count thread, pick[] / minw[] / cell[] full
+
+
+def big_case(name, moved=True):
+    a = BIG[name]
+    c = PS.make_case(a["seed"], W=640, H=480, Nf=a["Nf"], Nq=a["Nq"], src_hi=a["Nf"])
+    return PS.off_origin(c, 202) if name == "B" and moved else c
+
+
+def solved_big(oracle, name):
+    """solved() for the cases of BIG; "chain-1024" gives (case, lists, sequential, Jacobi, rounds) of chain_1024_case()"""
+    if name not in _cache:
+        c = chain_1024_case() if name == "chain-1024" else big_case(name)
+        lists = PS.case_lists(c)
+        seq = PS.search_by_projection_seq(oracle, c["q"], c["desc"], lists, c.get("skip"), c.get("observed"))
+        jac, rounds = PS.search_by_projection_jacobi(oracle, c["q"], c["desc"], lists, c.get("skip"), c.get("observed"))
+        _cache[name] = (c, lists, seq, jac, rounds)
+    return _cache[name]
+
+
+def solved_levels(oracle):
+    """B's geometry before off_origin with octaves and predicted levels: case, octave, level, gated lists, ungated lists, sequential result"""
+    if "B-levels" not in _cache:
+        c = big_case("B", moved=False)
+        rng = np.random.default_rng(33)
+        octave = rng.integers(0, 3, len(c["kpts"])).astype(np.int32)
+        level = rng.integers(0, 3, len(c["proj"])).astype(np.int32)
+        lists = PS.case_lists(c, octave, level)
+        seq = PS.search_by_projection_seq(oracle, c["q"], c["desc"], lists, c["skip"], c["observed"])
+        _cache["B-levels"] = (c, octave, level, lists, PS.case_lists(c), seq)
+    return _cache["B-levels"]
+
+
+@pytest.mark.parametrize("name", tuple(BIG))
+def test_big_case_is_not_vacuous_and_jacobi_equals_sequential(oracle, name):
+    c, lists, seq, jac, rounds = solved_big(oracle, name)
+    v = PS.vacuity(oracle, c, lists, seq, rounds)
+    print(f"{name}: {v}, nmatches {seq['nmatches']}, candidates {sum(len(l) for l in lists)}")
+    PS.check_vacuity(v, len(lists))
+    for k in ("best_idx", "best_dist", "second_dist", "assign"):
+        assert np.array_equal(seq[k], jac[k]), k
+    assert seq["nmatches"] == jac["nmatches"] > 0
+    # the second trip of the 1024-stride loops carries results, not only work
+    assert (np.flatnonzero(seq["assign"] >= 0) >= 1024).any()                       # pick[] holds a feature index >= 1024
+    assert (seq["best_dist"][1024:] <= PS.TH_HIGH).any()                           # a map point >= 1024 is accepted
+    if name != "A":
+        assert max(len(l) for l in lists) > PS_INFLIGHT                            # proj_fill_kernel takes a second batch of rows
+
+
+def test_off_origin_case_rounds_on_both_sides(oracle):
+    c, lists, _, _, _ = solved_big(oracle, "B")
+    Nf = len(c["kpts"])
+    assert "kxy" not in c and c["bounds"][0] < 0 and c["bounds"][1] < 0
+    assert (c["kpts"] != np.round(c["kpts"])).any()                                 # sub-pixel
+    cell = PS.cells(c["kpts"], c["bounds"])
+    member = np.bincount(np.array([j for l in lists for j in l], np.int64), minlength=Nf)
+    for j, xy in zip(range(Nf - 5, Nf), PS.PLANTED):
+        assert tuple(c["kpts"][j]) == xy
+        if xy in PS.PLANTED_OUT:                                                    # round(-0.5) = -1: in no cell, in no list
+            assert cell[j, 0] < 0 and member[j] == 0, (j, xy)
+        else:                                                                       # round(-0.4875) = -0: cell 0 on that axis
+            assert cell[j, 0] >= 0 and 0 in cell[j] and member[j] >= 1, (j, xy, cell[j], member[j])
+    # half-to-even would have put the outside ones into cell 0 of the windows that look at them
+    for i, (px, py) in zip(range(len(lists) - 3, len(lists)), PS.PLANTED_PROJ):
+        assert tuple(c["proj"][i]) == (px, py) and c["radius"][i] == 12 and len(lists[i]) >= 1
+    near = lambda j, i: (abs(c["kpts"][j] - c["proj"][i]) < c["radius"][i]).all()   # noqa: E731
+    assert near(Nf - 5, len(lists) - 3) and near(Nf - 3, len(lists) - 2)            # the window test alone would keep them
+    half = PS.on_half(c["kpts"], c["bounds"])
+    print(f"B: {int(half.sum())} features on an exact half, {int((half & (member > 0)).sum())} of them in a list; planted in lists {member[-5:]}")
+    assert (half & (member > 0) & (cell[:, 0] >= 0)).sum() >= 1
+    # and for some of them the two roundings give different cells: the scaled coordinate is k + 0.5 with k even
+    sx = (c["kpts"][:, 0] - np.float32(c["bounds"][0])) * np.float32(0.05)
+    assert ((np.abs(sx - np.trunc(sx)) == 0.5) & (np.trunc(sx) % 2 == 0) & (member > 0)).any()
+
+
+def test_big_candidate_lists_equal_brute_force(oracle):
+    c, lists, _, _, _ = solved_big(oracle, "B")
+    cl, octave, level, gated, _, _ = solved_levels(oracle)
+    for case, oc, lv, ls, seed in ((c, None, None, lists, 7), (cl, octave, level, gated, 8)):
+        cell = PS.cells(case["kpts"], case["bounds"])              # once per case, not per map point
+        Nq = len(ls)
+        sample = np.concatenate([np.random.default_rng(seed).choice(Nq - 3, 29, replace=False), [Nq - 3, Nq - 2, Nq - 1]])
+        for i in sample:
+            px, py, r = case["proj"][i, 0], case["proj"][i, 1], case["radius"][i]
+            L = 0 if lv is None else int(lv[i])
+            o = np.zeros(len(cell), np.int64) if oc is None else oc.astype(np.int64)
+            keep = (cell[:, 0] >= 0) & (o >= L - 1) & (o <= L) & (np.abs(case["kpts"][:, 0] - px) < r) & (np.abs(case["kpts"][:, 1] - py) < r)
+            want = sorted((cell[j, 0], cell[j, 1], j) for j in np.flatnonzero(keep))
+            assert ls[i] == [j for _, _, j in want], i
+        assert sum(len(ls[i]) for i in sample) > 32
+
+
+def test_big_levels_gate_both_ways(oracle):
+    c, octave, level, lists, ungated, seq = solved_levels(oracle)
+    below = sum(1 for i, l in enumerate(ungated) for j in l if octave[j] < level[i] - 1)
+    above = sum(1 for i, l in enumerate(ungated) for j in l if octave[j] > level[i])
+    print(f"B-levels: {below} gated below, {above} above, {sum(len(l) for l in lists)} of {sum(len(l) for l in ungated)} kept, nmatches {seq['nmatches']}")
+    assert below > 0 and above > 0 and sum(len(l) for l in lists) == sum(len(l) for l in ungated) - below - above
+    assert seq["nmatches"] > 20 and (seq["best_dist"][1024:] <= PS.TH_HIGH).any()
+
+
+def test_chain_1024_hands_over_between_trips(oracle):
+    c, lists, seq, jac, rounds = solved_big(oracle, "chain-1024")
+    assert all(l == [] for l in lists[:1000]) and all(len(l) == 64 for l in lists[1000:]) and len(lists) == 1080
+    assert np.array_equal(seq["best_idx"][1000:1064], c["order"]) and seq["nmatches"] == 64
+    assert (seq["best_idx"][:1000] == -1).all() and (seq["best_idx"][1064:] == -1).all() and (seq["best_dist"][1064:] == 256).all()
+    for k in ("best_idx", "best_dist", "second_dist", "assign"):
+        assert np.array_equal(seq[k], jac[k]), k
+    assert rounds >= 64
+
+
 def write_driver_case(path, c, th=3.0, nleft=-1):
     """the seed case as tests/cpp/projection_search_driver.cpp reads it: every fifth vpMapPoints entry is one the filters of
     SPmatcher.cc:1178-1190 drop (not in view / far / bad), skip becomes a prior map point WITH observations, and every tenth other
