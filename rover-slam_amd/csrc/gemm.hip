@@ -12,6 +12,7 @@
 // Reduction order: k ascending, accumulator initialised with the bias (== oracle rfo_linear, bit-exact).
 // Roofline: fp32 MFMA peak 157.3 TFLOP/s, algorithmic 2*M*N*K FLOP.
 #include <stdlib.h>
+#include <type_traits>
 #include "rfe_internal.h"
 
 namespace rfe {
@@ -274,14 +275,19 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 #undef RFE_LN_SHADOW
     }
 
+    // Lane coordinates of the epilogue, taken again from the thread index behind an opaque copy: i, h and what the compiler derives from them would otherwise
+    // be carried across the K loop, whose register file is full (256 at two workgroups per CU) -- the rotary instance spilled for it.
+    int te = tid;
+    asm volatile("" : "+v"(te));
+    const int ei = te & 31, eh = (te >> 5) & 1;
     {   // bias (+alpha, +ReLU, +residual) epilogue: 128-B coalesced accesses straight from the D layout
         const float* Rz = (RES && g.R) ? g.R + (size_t)z * g.sR : nullptr;
         if (rope) {
-            // rotary epilogue (alpha = 1, no ReLU), IN PLACE and before the first store: in the D layout a lane holds column n = .. + i of 16 rows, the other
-            // element of its pair (n ^ 1) sits in lane i ^ 1 of the same register -> one DPP move.  (c, s) of head dimension (nb & 1) * 32 + i from the LDS
+            // rotary epilogue (alpha = 1, no ReLU), IN PLACE and before the first store: in the D layout a lane holds column n = .. + ei of 16 rows, the other
+            // element of its pair (n ^ 1) sits in lane ei ^ 1 of the same register -> one DPP move.  (c, s) of head dimension (nb & 1) * 32 + ei from the LDS
             // table tile (blocks nb and nb + 2 = the same dimensions of two heads): the copies were requested before the K loop, whose barriers have long
             // published them.
-            const float* csl = lds_dynamic + ((wm * MB) * 32 + 4 * h) * 64 + (i & ~1);
+            const float* csl = lds_dynamic + ((wm * MB) * 32 + 4 * eh) * 64 + (ei & ~1);
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -290,16 +296,77 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
                     float2 c0 = *reinterpret_cast<const float2*>(cp), c1 = *reinterpret_cast<const float2*>(cp + 32);
                     // even lane: t0 c - t1 s = t0 c + t1 (-s); odd lane: t1 c + t0 s -- one signed sine per lane, then the same mul, mul, add in both
                     // (bit-identical to the attention kernels' on-load form: x (-s) = -(x s) and a + (-b) = a - b exactly)
-                    c0.y = (i & 1) ? c0.y : -c0.y; c1.y = (i & 1) ? c1.y : -c1.y;
+                    c0.y = (ei & 1) ? c0.y : -c0.y; c1.y = (ei & 1) ? c1.y : -c1.y;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
                         const float v = acc[mb][nb][r];
-                        const float pv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]: lane i ^ 1
+                        const float pv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]: lane ei ^ 1
                         const float2 t = (nb & 1) ? c1 : c0;
                         acc[mb][nb][r] = v * t.x + pv * t.y;
                     }
                 }
         }
+        // alpha and ReLU IN PLACE, each behind a workgroup-uniform branch that every LightGlue Linear skips (alpha = 1, no ReLU; x * 1.0f is x bit for
+        // bit): the stores and the statistics below read the accumulators as they are
+        if (g.alpha != 1.0f) {
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[mb][nb] *= g.alpha;
+        }
+        if (g.relu) {
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[mb][nb][r] = fmaxf(acc[mb][nb][r], 0.f);
+        }
+        // Full tile (workgroup-uniform; every tile of the throughput shapes): no bounds tests, no exec masking.  A wave's 64 x NB*32 block is addressed from
+        // a scalar base with one 32-bit byte offset per row, the NB column blocks at immediate offsets (+128 B each) -- the SGPR-base + VGPR-offset form of
+        // the K loop's loads -- and the accumulators go out from the registers they are in.  The residual is read the same way, without clamps.
+        // Guard: the tile's largest byte offset, 4 ((BM - 1) ld + BN - 1), must fit in 32 bits; a tile that fails it takes the general path below.
+        const unsigned long long cext = (unsigned long long)((long long)(BM - 1) * g.ldc + (BN - 1));
+        const unsigned long long rext = Rz ? (unsigned long long)((long long)(BM - 1) * g.ldr + (BN - 1)) : 0ull;
+        const bool full = mlast == BM - 1 && nlast == BN - 1 && cext <= 0x3fffffffull && rext <= 0x3fffffffull;
+        if (full) {
+            const int wrow = m0 + wm * MB * 32, wcol = n0 + wn * NB * 32;
+            char* const Cw = reinterpret_cast<char*>(C + (size_t)wrow * g.ldc + wcol);
+            const char* const Rw = Rz ? reinterpret_cast<const char*>(Rz + (size_t)wrow * g.ldr + wcol) : nullptr;
+            const unsigned ldcb = (unsigned)g.ldc * 4u, ldrb = (unsigned)g.ldr * 4u;
+            const unsigned clane = (unsigned)(4 * eh) * ldcb + (unsigned)ei * 4u, rlane = (unsigned)(4 * eh) * ldrb + (unsigned)ei * 4u;
+            // The stores, four rows (one register quad of each accumulator block) at a time.  With a residual, the reads of quad q + 1 are issued in front
+            // of the stores of quad q: the vector-memory counter returns in order, and a read issued behind 16 stores waits for all of them.
+            auto store_tile = [&](auto with_r) {
+                constexpr bool WR = decltype(with_r)::value;
+                constexpr int NQ = MB * 4;
+                float rv[2][4][NB];
+                auto read_quad = [&](int q, float (&dst)[4][NB]) {
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const unsigned off = rlane + (unsigned)((q >> 2) * 32 + rr + 8 * (q & 3)) * ldrb;
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) dst[rr][nb] = *reinterpret_cast<const float*>(Rw + off + nb * 128);
+                    }
+                };
+                if constexpr (WR) read_quad(0, rv[0]);
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    if constexpr (WR) { if (q + 1 < NQ) read_quad(q + 1, rv[(q + 1) & 1]); }
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const unsigned off = clane + (unsigned)((q >> 2) * 32 + rr + 8 * (q & 3)) * ldcb;
+#pragma unroll
+                        for (int nb = 0; nb < NB; ++nb) {
+                            float v = acc[q >> 2][nb][(q & 3) * 4 + rr];
+                            if constexpr (WR) v = rv[q & 1][rr][nb] + v;
+                            *reinterpret_cast<float*>(Cw + off + nb * 128) = v;
+                        }
+                    }
+                }
+            };
+            if (RES && Rz) store_tile(std::true_type{}); else store_tile(std::false_type{});
+        } else {   // edge tiles, and everything that is not a whole tile: clamped loads, tested stores
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -308,11 +375,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
                 if (Rz) {
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
-                        int m = m0 + (wm * MB + mb) * 32 + rr + 8 * rq + 4 * h;
+                        int m = m0 + (wm * MB + mb) * 32 + rr + 8 * rq + 4 * eh;
                         m = m < M ? m : M - 1;
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb) {
-                            int n = n0 + (wn * NB + nb) * 32 + i;
+                            int n = n0 + (wn * NB + nb) * 32 + ei;
                             n = n < g.N ? n : g.N - 1;
                             rv[rr][nb] = Rz[(size_t)m * g.ldr + n];
                         }
@@ -321,27 +388,27 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const int r = rq * 4 + rr;
-                    const int m = m0 + (wm * MB + mb) * 32 + rr + 8 * rq + 4 * h;
+                    const int m = m0 + (wm * MB + mb) * 32 + rr + 8 * rq + 4 * eh;
                     if (m >= M) continue;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
-                        const int n = n0 + (wn * NB + nb) * 32 + i;
+                        const int n = n0 + (wn * NB + nb) * 32 + ei;
                         if (n >= g.N) continue;
-                        float v = acc[mb][nb][r] * g.alpha;
-                        if (g.relu) v = fmaxf(v, 0.f);
+                        float v = acc[mb][nb][r];
                         if (Rz) v = rv[rr][nb] + v;
                         C[(size_t)m * g.ldc + n] = v;
                     }
                 }
             }
+        }
     }
     if (g.stats_out) {
         // Per-row LayerNorm partials of this wave's NB*32 stored columns, as (mean, M2 = sum of squared deviations from that mean):
         // a lane first reduces its own NB values of a row (two passes over registers), then the 32 lanes of a half-wave -- the same
         // rows, 32 different columns -- are merged with the parallel-variance formula for equal counts c
         //   mean = (mean_a + mean_b) / 2,   M2 = M2_a + M2_b + (mean_b - mean_a)^2 * c / 2
-        // in a butterfly that halves the rows kept per lane at every step (T/2, ..., 1 exchanges instead of 5 T): lane i ends
-        // with row i's partial.  Shifted data throughout: no sum of raw squares that would cancel for |mean| >> std.
+        // in a butterfly that halves the rows kept per lane at every step (T/2, ..., 1 exchanges instead of 5 T): lane ei ends
+        // with row ei's partial.  Shifted data throughout: no sum of raw squares that would cancel for |mean| >> std.
         // (launch_gemm_nt only passes stats_out when N is a whole number of column tiles: every column is a real column.)
         constexpr int T = MB * 16;
         float sm[T], s2[T];
@@ -349,13 +416,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float v[NB], a1 = 0.f;
+                float v[NB], a1 = 0.f;   // alpha / ReLU were applied in place above
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    v[nb] = acc[mb][nb][r] * g.alpha;
-                    if (g.relu) v[nb] = fmaxf(v[nb], 0.f);
-                    a1 += v[nb];
-                }
+                for (int nb = 0; nb < NB; ++nb) { v[nb] = acc[mb][nb][r]; a1 += v[nb]; }
                 const float mu = a1 * (1.0f / NB);
                 float a2 = 0.f;
 #pragma unroll
@@ -363,28 +426,41 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
                 sm[mb * 16 + r] = mu; s2[mb * 16 + r] = a2;
             }
         float cnt_half = 0.5f * NB;     // c / 2 of the groups being merged
+        // One butterfly level, its lane distance a compile-time constant: all exchanges first, then ONE wait -- one LDS round trip per level, not one
+        // per exchange -- then the merges.
+        auto level = [&](auto oc) {
+            constexpr int o = decltype(oc)::value;
+            if constexpr (o <= T / 2) {
+                const bool up = (ei & o) != 0;
+                float om[o], o2[o];
 #pragma unroll
-        for (int o = T / 2; o >= 1; o >>= 1) {
-            const bool up = (i & o) != 0;
+                for (int j = 0; j < o; ++j) {
+                    const float tm = up ? sm[j] : sm[j + o], t2 = up ? s2[j] : s2[j + o];
+                    om[j] = __shfl_xor(tm, o); o2[j] = __shfl_xor(t2, o);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < o; ++j) {
-                const float km = up ? sm[j + o] : sm[j], tm = up ? sm[j] : sm[j + o];
-                const float k2 = up ? s2[j + o] : s2[j], t2 = up ? s2[j] : s2[j + o];
-                const float om = __shfl_xor(tm, o), o2 = __shfl_xor(t2, o);
-                const float d = om - km;
-                sm[j] = 0.5f * (km + om);
-                s2[j] = (k2 + o2) + d * d * cnt_half;
+                for (int j = 0; j < o; ++j) {
+                    const float km = up ? sm[j + o] : sm[j], k2 = up ? s2[j + o] : s2[j];
+                    const float d = om[j] - km;
+                    sm[j] = 0.5f * (km + om[j]);
+                    s2[j] = (k2 + o2[j]) + d * d * cnt_half;
+                }
+                cnt_half *= 2.0f;
             }
-            cnt_half *= 2.0f;
-        }
+        };
+        level(std::integral_constant<int, 16>{}); level(std::integral_constant<int, 8>{}); level(std::integral_constant<int, 4>{});
+        level(std::integral_constant<int, 2>{}); level(std::integral_constant<int, 1>{});
         if (T < 32) {   // 16 rows on 32 lanes: lane bit 4 still to fold
             const float om = __shfl_xor(sm[0], 16), o2 = __shfl_xor(s2[0], 16), d = om - sm[0];
             s2[0] = (s2[0] + o2) + d * d * cnt_half; sm[0] = 0.5f * (sm[0] + om);
         }
-        // lane i (< T) of half h now holds local row t = i: mb = t / 16, r = t % 16 -> tile row (r & 3) + 8 (r >> 2) + 4 h
-        if (i < T) {
-            const int r = i & 15;
-            const int m = m0 + (wm * MB + (i >> 4)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        // lane ei (< T) of half eh now holds local row t = ei: mb = t / 16, r = t % 16 -> tile row (r & 3) + 8 (r >> 2) + 4 eh
+        if (ei < T) {
+            const int r = ei & 15;
+            const int m = m0 + (wm * MB + (ei >> 4)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * eh;
             if (m < M) {
                 const int P = (int)gridDim.x * 2;
                 float* sp = g.stats_out + (((size_t)m + (size_t)z * g.M) * P + bxt * 2 + wn) * 2;
