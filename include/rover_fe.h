@@ -406,6 +406,68 @@ int rfe_search_by_projection(rfe_ctx* ctx, const float* q, const float* proj, co
                              const uint8_t* skip, int Nf, float min_x, float min_y, float max_x, float max_y, float th_high,
                              int32_t* assign, int32_t* best_idx, float* best_dist, float* second_dist, int32_t* stats);
 
+/* ---- the Sim3 SearchByProjection overloads of loop closing as one call ----
+ * SPmatcher::SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)
+ * (src/Matchers/SPmatcher.cc:1558-1669) and SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming) (:2076-2182),
+ * which LoopClosing runs several times per loop / merge candidate: the front of the loop (transform, projection, the four gates,
+ * MapPoint::PredictScale, the radius) in one kernel, then the grid, candidate lists (KeyFrame::GetFeaturesInArea: no octave gate), scan and
+ * sequential assignment of rfe_search_by_projection with every map point observed: a feature is blocked when matched_in[f] != 0 or an
+ * earlier accepted map point took it.  All arithmetic is fp32 in the order the reference writes it, without contraction; the pose is the
+ * caller's (the device derives none): Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) as :1566 builds it.
+ *   rfe_sim3_params: quat = Tcw.unit_quaternion() as (x, y, z, w), t = Tcw.translation(), ow = Tcw.inverse().translation(); pinhole
+ *   fx, fy, cx, cy; the keyframe's mnMinX, mnMinY, mnMaxX, mnMaxY; th (an int in the reference); nlevels = mnScaleLevels (1..RFE_MAX_LEVELS),
+ *   log_scale_factor = mfLogScaleFactor, scale_factors = mvScaleFactors; proj_mode: RFE_PROJ_INVZ (:1596-1601, u = fx * (x * (1 / z)) + cx)
+ *   or RFE_PROJ_DIV (Pinhole::project, u = (fx * x) / z + cx); dist_mode: RFE_DIST_FLOAT (:1635-1664) or RFE_DIST_TRUNC (:2149-2177:
+ *   `int dist`, every candidate distance truncated toward zero before the strict <, accepted when (float)best <= th_accept).
+ *   q [Np,256] map-point descriptors, pw [Np,3] GetWorldPos, normal [Np,3] GetNormal, min_dist / max_dist [Np]
+ *   Get{Min,Max}DistanceInvariance (0.8f * mfMinDistance, 1.2f * mfMaxDistance: the distance gate), scale_dist [Np] the BARE mfMaxDistance
+ *   that MapPoint::PredictScale divides by the distance (src/MapPoint.cc:696) -- not max_dist: with the usual scale factor 1.2 that
+ *   would predict one level too many --, valid [Np] or NULL = all 1 (!isBad() && !spAlreadyFound.count(pMP));
+ *   f [Nf,256], kpts / kxy (exactly one), nf_dev as rfe_search_by_projection_dev; matched_in [Nf] or NULL (vpMatched[f] != NULL);
+ *   th_accept: TH_LOW for the first overload, TH_LOW * ratioHamming for the second.
+ *   matched [Nf]: the accepted map point of the feature, -1 = none (a pre-matched feature stays -1); best_idx / best_dist / second_dist
+ *   [Np] as rfe_search_by_projection (truncated values in RFE_DIST_TRUNC); proj [Np,2], radius [Np], level [Np] (0, 0 / 0 / -1 for a
+ *   rejected point); reject [Np]: 0 = searched, else the first gate that failed: 1 invalid, 2 z < 0, 3 outside the image, 4 distance
+ *   outside [min_dist, max_dist], 5 viewing angle (all but matched may be NULL); stats [8]: 0..3 as rfe_search_by_projection, 4 = map
+ *   points that reached the search, 5..7 = 0.
+ * The _dev form takes DEVICE pointers and is asynchronous on the ctx stream (no host synchronisation, no host read of device data once
+ * the workspace has its size; cand_cap and overflow as rfe_search_by_projection_dev; stats is required).  The host form sizes the slots
+ * itself and returns stats[0] >= 0.
+ * Refused (RFE_ERR_INVALID): Np outside 0..16384; Nf outside 0..4096; empty bounds; nlevels outside 1..RFE_MAX_LEVELS; log_scale_factor
+ *   <= 0 when nlevels > 1; an unknown proj_mode / dist_mode; cand_cap < 0; both or neither of kpts / kxy; a NULL required pointer; host
+ *   form only: a non-finite pose, intrinsic, bound, scale factor, log_scale_factor, th_accept or keypoint.  The per-point arrays (pw,
+ *   normal, min_dist, max_dist, scale_dist) are not checked in either form: a NaN there fails a gate on the device (a NaN coordinate
+ *   is "outside the image") or, behind the gates, gives level 0.
+ * Out of scope: KannalaBrandt8 and two-camera keyframes (the caller keeps the reference's loop), both Fuse overloads. */
+#define RFE_PROJ_INVZ 0
+#define RFE_PROJ_DIV 1
+#define RFE_DIST_FLOAT 0
+#define RFE_DIST_TRUNC 1
+typedef struct rfe_sim3_params {
+    float quat[4];                 /* x, y, z, w */
+    float t[3];
+    float ow[3];
+    float fx, fy, cx, cy;
+    float min_x, min_y, max_x, max_y;
+    int32_t th;
+    int32_t nlevels;
+    float log_scale_factor;
+    float scale_factors[RFE_MAX_LEVELS];
+    int32_t proj_mode, dist_mode;
+} rfe_sim3_params;
+int rfe_search_by_projection_sim3_dev(rfe_ctx* ctx, const rfe_sim3_params* params, const float* q_dev, const float* pw_dev,
+                                      const float* normal_dev, const float* min_dist_dev, const float* max_dist_dev,
+                                      const float* scale_dist_dev, const uint8_t* valid_dev, int Np, const float* f_dev, const float* kpts_dev, const int32_t* kxy_dev,
+                                      const uint8_t* matched_in_dev, int Nf, const int32_t* nf_dev, float th_accept, int cand_cap,
+                                      int32_t* matched_dev, int32_t* best_idx_dev, float* best_dist_dev, float* second_dist_dev,
+                                      float* proj_dev, float* radius_dev, int32_t* level_dev, int32_t* reject_dev, int32_t* stats_dev);
+int rfe_search_by_projection_sim3(rfe_ctx* ctx, const rfe_sim3_params* params, const float* q, const float* pw, const float* normal,
+                                  const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np,
+                                  const float* f,
+                                  const float* kpts, const int32_t* kxy, const uint8_t* matched_in, int Nf, float th_accept,
+                                  int32_t* matched, int32_t* best_idx, float* best_dist, float* second_dist, float* proj, float* radius,
+                                  int32_t* level, int32_t* reject, int32_t* stats);
+
 /* ---- multi-device pool (BASELINE configs[3] for a C / C++ host) ----
  * The reference runs on ONE device (device_id = 0, src/Extractors/superpoint_onnx.cc:19, src/Matchers/lightglue_onnx.cpp:24) and
  * is a C++ program (src/Tracking.cc:645-651); a pool gives such a host the frame sharding of rover-slam_amd/sharding.py without

@@ -24,7 +24,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix", "rfe_binarize_descriptors",
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
-    "rfe_search_by_projection", "rfe_search_by_projection_dev",
+    "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
@@ -113,6 +113,39 @@ _psq = [C.c_void_p, _fp, _fp, _fp, _ip, _u8p, C.c_int, _fp, _fp, _ip, _ip, _u8p,
 _psb = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]
 lib.rfe_search_by_projection.argtypes = _psq + _psb + [_ip, _ip, _fp, _fp, _ip]
 lib.rfe_search_by_projection_dev.argtypes = _psq + [_ip] + _psb + [C.c_int, _ip, _ip, _fp, _fp, _ip]
+
+
+MAX_LEVELS = 16                                                   # RFE_MAX_LEVELS
+PROJ_INVZ, PROJ_DIV = 0, 1                                        # RFE_PROJ_*
+DIST_FLOAT, DIST_TRUNC = 0, 1                                     # RFE_DIST_*
+
+
+class Sim3Params(C.Structure):
+    """include/rover_fe.h: rfe_sim3_params -- pose, intrinsics, bounds and scale pyramid of one Sim3 SearchByProjection call."""
+    _fields_ = [("quat", C.c_float * 4), ("t", C.c_float * 3), ("ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float), ("th", C.c_int32),
+                ("nlevels", C.c_int32), ("log_scale_factor", C.c_float), ("scale_factors", C.c_float * MAX_LEVELS),
+                ("proj_mode", C.c_int32), ("dist_mode", C.c_int32)]
+
+
+def sim3_params(quat, t, ow, intrinsics, bounds, th, scale_factors=(1.0,), log_scale_factor=0.0, proj_mode=PROJ_INVZ, dist_mode=DIST_FLOAT,
+                nlevels=None):
+    """rfe_sim3_params from plain values: quat (x, y, z, w), intrinsics (fx, fy, cx, cy), bounds (min_x, min_y, max_x, max_y)"""
+    p = Sim3Params()
+    p.quat[:] = [float(v) for v in quat]; p.t[:] = [float(v) for v in t]; p.ow[:] = [float(v) for v in ow]
+    p.fx, p.fy, p.cx, p.cy = (float(v) for v in intrinsics)
+    p.min_x, p.min_y, p.max_x, p.max_y = (float(v) for v in bounds)
+    p.th, p.nlevels, p.log_scale_factor = int(th), len(scale_factors) if nlevels is None else int(nlevels), float(log_scale_factor)
+    for l, v in enumerate(list(scale_factors)[:MAX_LEVELS]):
+        p.scale_factors[l] = float(v)
+    p.proj_mode, p.dist_mode = int(proj_mode), int(dist_mode)
+    return p
+
+
+_s3q = [C.c_void_p, C.POINTER(Sim3Params), _fp, _fp, _fp, _fp, _fp, _fp, _u8p, C.c_int, _fp, _fp, _ip, _u8p, C.c_int]
+_s3o = [_ip, _ip, _fp, _fp, _fp, _fp, _ip, _ip, _ip]
+lib.rfe_search_by_projection_sim3.argtypes = _s3q + [C.c_float] + _s3o
+lib.rfe_search_by_projection_sim3_dev.argtypes = _s3q + [_ip, C.c_float, C.c_int] + _s3o
 lib.rfe_profile_enable.argtypes = [C.c_void_p, C.c_int]
 lib.rfe_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
 lib.rfe_profile_reset.argtypes = [C.c_void_p]
@@ -620,6 +653,41 @@ class Context:
         self._chk(lib.rfe_search_by_projection_dev(self.h, a(q), a(proj), a(radius), a(pred_level), a(observed), Nq, a(f), a(kpts), a(kxy),
                                                    a(octave), a(skip), Nf, a(nf_dev), *[float(b) for b in bounds], th_high, cand_cap,
                                                    a(assign), a(best_idx), a(best_dist), a(second_dist), a(stats)))
+
+    def search_by_projection_sim3(self, params, q, pw, normal, min_dist, max_dist, scale_dist, f, th_accept, valid=None, kpts=None, kxy=None,
+                                  matched_in=None):
+        """The Sim3 SearchByProjection overloads of loop closing as one call (rfe_search_by_projection_sim3, host arrays).
+        params: a Sim3Params (sim3_params()); scale_dist [Np] is the bare mfMaxDistance of PredictScale; exactly one of kpts [Nf,2] f32 and kxy [Nf,2] i32.  Returns a dict: matched [Nf], best_idx /
+        best_dist / second_dist / radius / level / reject [Np], proj [Np,2], nmatches, stats [8]."""
+        f32 = lambda a, w: np.ascontiguousarray(a, np.float32).reshape(-1, w)   # noqa: E731
+        qa, fa, pa, na = f32(q, 256), f32(f, 256), f32(pw, 3), f32(normal, 3)
+        mn, mx, sc = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (min_dist, max_dist, scale_dist))
+        Np, Nf = qa.shape[0], fa.shape[0]
+        assert pa.shape[0] == Np and na.shape[0] == Np and mn.shape[0] == Np and mx.shape[0] == Np and sc.shape[0] == Np
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
+        va, ka, xa, mi = opt(valid, np.uint8), opt(kpts, np.float32), opt(kxy, np.int32), opt(matched_in, np.uint8)
+        n1, f1 = max(Np, 1), max(Nf, 1)
+        o = {"matched": np.full((f1,), -1, np.int32), "best_idx": np.full((n1,), -1, np.int32), "best_dist": np.full((n1,), 256, np.float32),
+             "second_dist": np.full((n1,), 256, np.float32), "proj": np.zeros((n1, 2), np.float32), "radius": np.zeros((n1,), np.float32),
+             "level": np.full((n1,), -1, np.int32), "reject": np.ones((n1,), np.int32)}
+        st = np.zeros((8,), np.int32)
+        n = self._chk(lib.rfe_search_by_projection_sim3(self.h, C.byref(params), qa.ctypes.data, pa.ctypes.data, na.ctypes.data, mn.ctypes.data,
+                                                        mx.ctypes.data, sc.ctypes.data, _addr(va), Np, fa.ctypes.data, _addr(ka), _addr(xa), _addr(mi), Nf,
+                                                        float(th_accept), *[o[k].ctypes.data for k in o], st.ctypes.data))
+        out = {k: (v[:Nf] if k == "matched" else v[:Np]) for k, v in o.items()}
+        out.update(nmatches=n, stats=st)
+        return out
+
+    def search_by_projection_sim3_dev(self, params, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, Nf, th_accept, cand_cap, matched, stats,
+                                      valid=None, kpts=None, kxy=None, matched_in=None, nf_dev=None, best_idx=None, best_dist=None,
+                                      second_dist=None, proj=None, radius=None, level=None, reject=None):
+        """rfe_search_by_projection_sim3_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
+        outputs land in matched [Nf], stats [8] and the optional per-map-point arrays."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_search_by_projection_sim3_dev(self.h, C.byref(params), a(q), a(pw), a(normal), a(min_dist), a(max_dist), a(scale_dist), a(valid), Np,
+                                                        a(f), a(kpts), a(kxy), a(matched_in), Nf, a(nf_dev), float(th_accept), cand_cap,
+                                                        a(matched), a(best_idx), a(best_dist), a(second_dist), a(proj), a(radius), a(level),
+                                                        a(reject), a(stats)))
 
     def distinctive_descriptors(self, desc, offsets):
         """MapPoint::ComputeDistinctiveDescriptors for many map points (MapPoint.cc:438-530)."""

@@ -1,5 +1,5 @@
 // api_search.hip -- C ABI of librover_fe.so: the descriptor helpers of the callers' classic searches (L2 matrix, binarisation, candidate
-// scan, SearchByProjection1, distinctive descriptors).
+// scan, SearchByProjection1, the Sim3 SearchByProjection overloads, distinctive descriptors).
 #include <string.h>
 #include <algorithm>
 #include "api_internal.h"
@@ -113,6 +113,14 @@ extern "C" int rfe_search_candidates(rfe_ctx* c, const float* q, int Nq, const f
 
 // SPmatcher::SearchByProjection1, left-camera branch (src/Matchers/SPmatcher.cc:1190-1283), device resident: grid, candidate lists, scan and
 // the sequential assignment (proj_search.hip).  Four kernels on the ctx stream, nothing read back.
+// ws_ps: the grid (cell starts, items, positions), the segment offsets and cand_cap (index, distance) slots -- one element at least of each
+struct PsBuffers { int32_t *cell_start, *cell_items, *seg_off, *cand_idx; float *fxy, *cand_dist; };
+static void ps_layout(Bump& a, int Nq, int Nf, int cand_cap, PsBuffers& b) {
+    const size_t nf1 = (size_t)std::max(Nf, 1), cap1 = (size_t)std::max(cand_cap, 1);
+    b.cell_start = a.take<int32_t>(770); b.cell_items = a.take<int32_t>(nf1); b.fxy = a.take<float>(nf1 * 2);
+    b.seg_off = a.take<int32_t>((size_t)Nq + 1); b.cand_idx = a.take<int32_t>(cap1); b.cand_dist = a.take<float>(cap1);
+}
+
 static int ps_check(rfe_ctx* c, const void* q, const void* proj, const void* radius, int Nq, const void* f, const void* kpts, const void* kxy,
                     int Nf, float min_x, float min_y, float max_x, float max_y, int cand_cap, const void* assign) {
     if (Nq < 0 || Nq > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nq outside 0..16384");
@@ -134,23 +142,18 @@ extern "C" int rfe_search_by_projection_dev(rfe_ctx* c, const float* q, const fl
     if (rc) return rc;
     if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
     RFE_HIP(c, hipSetDevice(c->device));
-    // ws_ps: the grid (cell starts, items, positions), the segment offsets and cand_cap (index, distance) slots -- one element at least of each
-    int32_t *cell_start, *cell_items, *seg_off, *cand_idx; float *fxy, *cand_dist;
-    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
-        const size_t nf1 = (size_t)std::max(Nf, 1), cap1 = (size_t)std::max(cand_cap, 1);
-        cell_start = a.take<int32_t>(770); cell_items = a.take<int32_t>(nf1); fxy = a.take<float>(nf1 * 2);
-        seg_off = a.take<int32_t>((size_t)Nq + 1); cand_idx = a.take<int32_t>(cap1); cand_dist = a.take<float>(cap1);
-    });
+    PsBuffers b;
+    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) { ps_layout(a, Nq, Nf, cand_cap, b); });
     if (rc) return rc;
     const float inv_w = 32.f / (max_x - min_x), inv_h = 24.f / (max_y - min_y);      // Frame::mfGridElementWidthInv / HeightInv
     hipStream_t s = c->stream;
-    { ProfScope ps(c, "ps_grid"); launch_proj_grid(s, kpts, kxy, Nf, nf_dev, min_x, min_y, inv_w, inv_h, cell_start, cell_items, fxy); }
+    { ProfScope ps(c, "ps_grid"); launch_proj_grid(s, kpts, kxy, Nf, nf_dev, min_x, min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
     { ProfScope ps(c, "ps_count");
-      launch_proj_count(s, proj, radius, pred_level, Nq, cell_start, cell_items, fxy, octave, min_x, min_y, inv_w, inv_h, cand_cap, seg_off,
-                        cand_idx, stats); }
-    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist); }
+      launch_proj_count(s, proj, radius, pred_level, Nq, b.cell_start, b.cell_items, b.fxy, octave, min_x, min_y, inv_w, inv_h, cand_cap, b.seg_off,
+                        b.cand_idx, stats); }
+    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Nq, f, Nf, b.seg_off, b.cand_idx, skip, b.cand_dist); }
     { ProfScope ps(c, "ps_resolve");
-      launch_proj_resolve(s, seg_off, cand_idx, cand_dist, observed, Nq, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
+      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, observed, Nq, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
     RFE_HIP(c, hipGetLastError());
     return RFE_OK;
 }
@@ -195,6 +198,116 @@ extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float*
     c->ps_cap = std::max(c->ps_cap, cap);
     if ((rc = io.download())) return rc;
     if (stats) memcpy(stats, st, 16);
+    return st[0];
+}
+
+// The Sim3 SearchByProjection overloads of loop closing (src/Matchers/SPmatcher.cc:1558-1669, 2076-2182): sim3_project_kernel
+// (proj_sim3.hip) writes proj / radius / level into ws_ps, behind the layout of rfe_search_by_projection_dev, and the grid, count, fill and
+// resolve kernels of 6d run on them with no octave gate and every map point observed.
+static int s3_check(rfe_ctx* c, const rfe_sim3_params* P, const void* q, const void* pw, const void* normal, const void* min_dist,
+                    const void* max_dist, const void* scale_dist, int Np, const void* f, const void* kpts, const void* kxy, int Nf, int cand_cap,
+                    const void* matched) {
+    if (!P) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
+    if (Np < 0 || Np > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: Np outside 0..16384");
+    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: Nf outside 0..4096");
+    if (!(P->max_x > P->min_x) || !(P->max_y > P->min_y)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: empty image bounds");
+    if (P->nlevels < 1 || P->nlevels > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: nlevels outside 1..16");
+    if (P->nlevels > 1 && !(P->log_scale_factor > 0.f)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: log_scale_factor must be positive");
+    if (P->proj_mode != RFE_PROJ_INVZ && P->proj_mode != RFE_PROJ_DIV) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown proj_mode");
+    if (P->dist_mode != RFE_DIST_FLOAT && P->dist_mode != RFE_DIST_TRUNC) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown dist_mode");
+    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: negative cand_cap");
+    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: pass exactly one of kpts and kxy");
+    if ((Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !matched)))
+        return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection_sim3_dev(rfe_ctx* c, const rfe_sim3_params* P, const float* q, const float* pw, const float* normal,
+                                                 const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np,
+                                                 const float* f,
+                                                 const float* kpts, const int32_t* kxy, const uint8_t* matched_in, int Nf,
+                                                 const int32_t* nf_dev, float th_accept, int cand_cap, int32_t* matched, int32_t* best_idx,
+                                                 float* best_dist, float* second_dist, float* proj, float* radius, int32_t* level,
+                                                 int32_t* reject, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = s3_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, cand_cap, matched);
+    if (rc) return rc;
+    if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    PsBuffers b; float *wproj, *wradius; int32_t* wlevel;
+    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
+        ps_layout(a, Np, Nf, cand_cap, b);
+        const size_t np1 = (size_t)std::max(Np, 1);
+        wproj = a.take<float>(np1 * 2); wradius = a.take<float>(np1); wlevel = a.take<int32_t>(np1);
+    });
+    if (rc) return rc;
+    const float inv_w = 32.f / (P->max_x - P->min_x), inv_h = 24.f / (P->max_y - P->min_y);   // KeyFrame::mfGridElementWidthInv / HeightInv
+    hipStream_t s = c->stream;
+    RFE_HIP(c, hipMemsetAsync(stats + 4, 0, 16, s));
+    { ProfScope ps(c, "s3_project"); launch_sim3_project(s, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, reject, stats); }
+    { ProfScope ps(c, "ps_grid");
+      launch_proj_grid(s, kpts, kxy, Nf, nf_dev, P->min_x, P->min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
+    { ProfScope ps(c, "ps_count");
+      launch_proj_count(s, wproj, wradius, nullptr, Np, b.cell_start, b.cell_items, b.fxy, nullptr, P->min_x, P->min_y, inv_w, inv_h, cand_cap,
+                        b.seg_off, b.cand_idx, stats); }
+    { ProfScope ps(c, "ps_fill");
+      if (P->dist_mode == RFE_DIST_TRUNC) launch_proj_fill_trunc(s, q, Np, f, Nf, b.seg_off, b.cand_idx, matched_in, b.cand_dist);
+      else launch_proj_fill(s, q, Np, f, Nf, b.seg_off, b.cand_idx, matched_in, b.cand_dist); }
+    { ProfScope ps(c, "ps_resolve");
+      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, nullptr, Np, Nf, th_accept, matched, best_idx, best_dist, second_dist, stats); }
+    if (Np > 0) {
+        if (proj) RFE_HIP(c, hipMemcpyAsync(proj, wproj, (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
+        if (radius) RFE_HIP(c, hipMemcpyAsync(radius, wradius, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
+        if (level) RFE_HIP(c, hipMemcpyAsync(level, wlevel, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
+    }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_by_projection_sim3(rfe_ctx* c, const rfe_sim3_params* P, const float* q, const float* pw, const float* normal,
+                                             const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np,
+                                                 const float* f,
+                                             const float* kpts, const int32_t* kxy, const uint8_t* matched_in, int Nf, float th_accept,
+                                             int32_t* matched, int32_t* best_idx, float* best_dist, float* second_dist, float* proj,
+                                             float* radius, int32_t* level, int32_t* reject, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = s3_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, 0, matched);
+    if (rc) return rc;
+    auto fin = [](float v) { return v - v == 0.f; };
+    bool ok = fin(th_accept) && fin(P->log_scale_factor);
+    for (float v : P->quat) ok = ok && fin(v);
+    for (float v : P->t) ok = ok && fin(v);
+    for (float v : P->ow) ok = ok && fin(v);
+    for (float v : {P->fx, P->fy, P->cx, P->cy, P->min_x, P->min_y, P->max_x, P->max_y}) ok = ok && fin(v);
+    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->scale_factors[l]);
+    if (!ok) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite argument");
+    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite keypoint");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dq, *dpw, *dn, *dmin, *dmax, *dsc, *df, *dkp, *dbd, *dsd, *dproj, *drad; int32_t *dkx, *dm, *dbi, *dlev, *drej, *dst; uint8_t *dval, *dmi;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dq, q, (size_t)Np * 256); io.in(dpw, pw, (size_t)Np * 3); io.in(dn, normal, (size_t)Np * 3); io.in(dmin, min_dist, Np);
+    io.in(dmax, max_dist, Np); io.in(dsc, scale_dist, Np); io.in_opt(dval, valid, Np);
+    io.in(df, f, (size_t)Nf * 256); io.in_opt(dkp, kpts, (size_t)Nf * 2); io.in_opt(dkx, kxy, (size_t)Nf * 2); io.in_opt(dmi, matched_in, Nf);
+    io.out(dm, matched, Nf); io.out_opt(dbi, best_idx, Np); io.out_opt(dbd, best_dist, Np); io.out_opt(dsd, second_dist, Np);
+    io.out_opt(dproj, proj, (size_t)Np * 2); io.out_opt(drad, radius, Np); io.out_opt(dlev, level, Np); io.out_opt(drej, reject, Np);
+    io.scratch(dst, 8);
+    if ((rc = io.upload())) return rc;
+    hipStream_t s = c->stream;
+    // the slots: as rfe_search_by_projection -- the largest count used so far (at least 16 per map point), then once more with what is needed
+    int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Np, 1)), (long long)Np * Nf);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = rfe_search_by_projection_sim3_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, Np, df, dkp, dkx, dmi, Nf, nullptr, th_accept, cap, dm,
+                                                    dbi, dbd, dsd, dproj, drad, dlev, drej, dst))) return rc;
+        RFE_HIP(c, hipMemcpyAsync(st, dst, 32, hipMemcpyDeviceToHost, s));
+        RFE_HIP(c, hipStreamSynchronize(s));
+        if (!st[3]) break;
+        cap = st[1];
+    }
+    if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection_sim3: candidate lists still overflow");
+    c->ps_cap = std::max(c->ps_cap, cap);
+    if ((rc = io.download())) return rc;
+    if (stats) memcpy(stats, st, 32);
     return st[0];
 }
 

@@ -183,6 +183,9 @@ __global__ __launch_bounds__(1024) void proj_count_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------- 3. fill + distance
+// TRUNC: the `int dist = DescriptorDistance_sp(...)` of the second Sim3 SearchByProjection overload (SPmatcher.cc:2164): the
+// distance is truncated toward zero once, where it is stored, and the resolve kernel's strict < keeps the first least one as the loop does.
+template <bool TRUNC>
 __global__ __launch_bounds__(256) void proj_fill_kernel(const float* __restrict__ q, int Nq, const float* __restrict__ f, int Nf,
                                                         const int32_t* __restrict__ seg_off, const int32_t* __restrict__ cand_idx,
                                                         const uint8_t* __restrict__ skip, float* __restrict__ cand_dist) {
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(256) void proj_fill_kernel(const float* __restrict_
         for (int j = 0; j < PS_INFLIGHT; ++j) {
             if (c + j >= e) break;                       // wave-uniform
             const float d = live[j] ? desc_dist_wave(a, b[j]) : __builtin_inff();
-            if (lane == 0) cand_dist[c + j] = d;
+            if (lane == 0) cand_dist[c + j] = TRUNC ? truncf(d) : d;
         }
     }
 }
@@ -294,7 +297,13 @@ void launch_proj_count(hipStream_t s, const float* proj, const float* radius, co
 void launch_proj_fill(hipStream_t s, const float* q, int Nq, const float* f, int Nf, const int32_t* seg_off, const int32_t* cand_idx,
                       const uint8_t* skip, float* cand_dist) {
     if (Nq <= 0 || Nf <= 0) return;
-    hipLaunchKernelGGL(proj_fill_kernel, dim3((Nq + 3) / 4), dim3(256), 0, s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist);
+    hipLaunchKernelGGL(proj_fill_kernel<false>, dim3((Nq + 3) / 4), dim3(256), 0, s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist);
+}
+
+void launch_proj_fill_trunc(hipStream_t s, const float* q, int Nq, const float* f, int Nf, const int32_t* seg_off, const int32_t* cand_idx,
+                            const uint8_t* skip, float* cand_dist) {
+    if (Nq <= 0 || Nf <= 0) return;
+    hipLaunchKernelGGL(proj_fill_kernel<true>, dim3((Nq + 3) / 4), dim3(256), 0, s, q, Nq, f, Nf, seg_off, cand_idx, skip, cand_dist);
 }
 
 void launch_proj_resolve(hipStream_t s, const int32_t* seg_off, const int32_t* cand_idx, const float* cand_dist, const uint8_t* observed,

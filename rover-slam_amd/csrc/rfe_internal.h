@@ -328,8 +328,15 @@ void launch_proj_count(hipStream_t s, const float* proj, const float* radius, co
                        float inv_h, int cand_cap, int32_t* seg_off, int32_t* cand_idx, int32_t* stats);
 void launch_proj_fill(hipStream_t s, const float* q, int Nq, const float* f, int Nf, const int32_t* seg_off, const int32_t* cand_idx,
                       const uint8_t* skip, float* cand_dist);
+void launch_proj_fill_trunc(hipStream_t s, const float* q, int Nq, const float* f, int Nf, const int32_t* seg_off, const int32_t* cand_idx,
+                            const uint8_t* skip, float* cand_dist);   // every distance truncated toward zero where it is stored
 void launch_proj_resolve(hipStream_t s, const int32_t* seg_off, const int32_t* cand_idx, const float* cand_dist, const uint8_t* observed,
                          int Nq, int Nf, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist, float* second_dist,
                          int32_t* stats);
+
+// proj_sim3.hip: the front of the Sim3 SearchByProjection loops; adds the searched map points to stats[4]
+void launch_sim3_project(hipStream_t s, const rfe_sim3_params& P, const float* pw, const float* normal, const float* min_dist,
+                         const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np, float* proj, float* radius,
+                         int32_t* level, int32_t* reject, int32_t* stats);
 
 }  // namespace rfe
