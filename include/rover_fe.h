@@ -551,6 +551,16 @@ int rfe_k_attention(rfe_ctx* ctx, const float* q_dev, const float* k_dev, const 
  * fallback that rotates on load).  L % 4 == 0. */
 int rfe_k_lightglue_self_attention(rfe_ctx* ctx, int layer, const float* x_dev, const float* csn_dev, const int32_t* lens_dev, int nseq, int L,
                                    float* qkv_out_dev, float* ctx_out_dev, int32_t* qk_rotated);
+/* LightGlue's assignment stage alone, through the forward's own code, on caller-provided inputs (device pointers; a ctx is enough, no weights):
+ * sim_dev [P,L,L] similarities, x_dev [2,P,L,256] final token states (side-major: all side-0 sequences, then all side-1), wm_dev [256] / bm_dev [1] the
+ * matchability head, lens_dev [2P] valid rows (all m, then all n; each within [0, L]); L % 4 == 0, 4 <= L <= 4096; thr the match filter, cap the list
+ * capacity per pair.  (P, L) selects the kernels as inside a match call.  Before the stage runs, every output buffer is filled with the 32-bit word
+ * `sentinel`, so words the stage did not write read back as the sentinel.  Outputs (each may be NULL): z_dev [2,P,L] log sigmoid of the matchability
+ * logits (written for EVERY padded row), rowlse_dev / collse_dev / mx0_dev [P,L] f32, a0_dev / a1_dev [P,L] i32, S_dev [P], pairs_dev [P,cap,2],
+ * ms_dev [P,cap], and the log-assignment dump scores_dev: [P,L,L] (scores_pair < 0) or [L,L] of pair `scores_pair`; only live m x n blocks are written. */
+int rfe_k_lightglue_assign(rfe_ctx* ctx, const float* sim_dev, const float* x_dev, const float* wm_dev, const float* bm_dev, const int32_t* lens_dev,
+                           int P, int L, float thr, int cap, int scores_pair, int32_t sentinel, float* z_dev, float* rowlse_dev, float* collse_dev,
+                           float* mx0_dev, int32_t* a0_dev, int32_t* a1_dev, int32_t* S_dev, int32_t* pairs_dev, float* ms_dev, float* scores_dev);
 /* One-shot tap for the NEXT LightGlue forward of this ctx, whichever entry point runs it (rfe_match[_dev] with P pairs,
  * rfe_extract_match_stream_dev, rfe_stereo_frame_dev) and therefore whichever tiling it selects: after the last layer the final
  * token states of pair `pair` are copied to x0_dev / x1_dev ([L,256] each, L = max(Mmax,Nmax) rounded up to 4; rows past the

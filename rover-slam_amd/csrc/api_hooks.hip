@@ -165,6 +165,48 @@ extern "C" int rfe_k_lightglue_self_attention(rfe_ctx* c, int layer, const float
     return RFE_OK;
 }
 
+// LightGlue's assignment stage alone (lg_assign_stage, the forward's own) on caller-provided similarities, token states and matchability head: needs a
+// ctx and no weights.  Every buffer the stage leaves behind, the match list and the score dump are pre-filled with the 32-bit word `sentinel`, so the
+// caller sees exactly which words the stage wrote; (P, L) selects the form as inside a match call.
+extern "C" int rfe_k_lightglue_assign(rfe_ctx* c, const float* sim, const float* x, const float* wm, const float* bm, const int32_t* lens, int P, int L,
+                                      float thr, int cap, int scores_pair, int32_t sentinel, float* z, float* rowlse, float* collse, float* mx0,
+                                      int32_t* a0, int32_t* a1, int32_t* S, int32_t* pairs, float* ms, float* scores) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!sim || !x || !wm || !bm || !lens || P <= 0 || L < 4 || L > 4096 || (L % 4) || cap <= 0 || scores_pair >= P)
+        return fail(c, RFE_ERR_INVALID, "k_lightglue_assign: null input, P <= 0, L not a multiple of 4 in [4, 4096], cap <= 0 or scores_pair >= P");
+    RFE_HIP(c, hipSetDevice(c->device));
+    {   // the kernels trust the lengths (lg_stage clamps them for the forward): refuse what would index past a padded sequence
+        std::vector<int32_t> hl((size_t)2 * P);
+        RFE_HIP(c, hipMemcpy(hl.data(), lens, hl.size() * 4, hipMemcpyDeviceToHost));
+        for (int32_t v : hl) if (v < 0 || v > L) return fail(c, RFE_ERR_INVALID, "k_lightglue_assign: a length outside [0, L]");
+    }
+    const size_t PL = (size_t)P * L, n_scores = scores ? (scores_pair < 0 ? PL * L : (size_t)L * L) : 0;
+    LgBuffers b;
+    float *dsc = nullptr, *dms; int32_t *dS, *dp;
+    int rc = lg_carve(c, P, L, b, [&](Bump& a) {
+        dS = a.take<int32_t>(P); dp = a.take<int32_t>((size_t)P * cap * 2); dms = a.take<float>((size_t)P * cap);
+        if (n_scores) dsc = a.take<float>(n_scores);
+    });
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    RFE_HIP(c, hipMemcpyAsync(b.sim, sim, PL * L * 4, hipMemcpyDeviceToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(b.x, x, 2 * PL * 1024, hipMemcpyDeviceToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(b.lens, lens, (size_t)2 * P * 4, hipMemcpyDeviceToDevice, s));
+    const struct { void* p; size_t words; } fill[] = {{b.z, 2 * PL}, {b.rowlse, PL}, {b.collse, PL}, {b.mx0, PL}, {b.a0, PL}, {b.a1, PL},
+                                                      {dS, (size_t)P}, {dp, (size_t)P * cap * 2}, {dms, (size_t)P * cap}, {dsc, n_scores}};
+    for (const auto& f : fill)
+        if (f.words) RFE_HIP(c, hipMemsetD32Async((hipDeviceptr_t)f.p, sentinel, f.words, s));
+    lg_assign_stage(s, b, P, L, thr, cap, dS, dp, dms, dsc, scores_pair, wm, bm);
+    RFE_HIP(c, hipGetLastError());
+    const struct { void* dst; const void* src; size_t words; } out[] = {{z, b.z, 2 * PL}, {rowlse, b.rowlse, PL}, {collse, b.collse, PL}, {mx0, b.mx0, PL},
+                                                                       {a0, b.a0, PL}, {a1, b.a1, PL}, {S, dS, (size_t)P}, {pairs, dp, (size_t)P * cap * 2},
+                                                                       {ms, dms, (size_t)P * cap}, {scores, dsc, n_scores}};
+    for (const auto& o : out)
+        if (o.dst && o.words) RFE_HIP(c, hipMemcpyAsync(o.dst, o.src, o.words * 4, hipMemcpyDeviceToDevice, s));
+    RFE_HIP(c, hipStreamSynchronize(s));
+    return RFE_OK;
+}
+
 extern "C" int rfe_k_lightglue_taps(rfe_ctx* c, const float* k0n, const float* k1n, const float* d0, const float* d1,
                                     int M, int N, float* x0, float* x1, float* scores) {
     int rc = lg_check(c, 1, M, N);

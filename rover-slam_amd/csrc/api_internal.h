@@ -174,6 +174,8 @@ bool lg_self_qkv_attention(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, const
 void lg_self_block(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, float* x, const float* csn, const int32_t* lens, int nseq, int L);
 int lg_forward(rfe_ctx* c, LgBuffers& b, int P, int L, float thr, int cap, int32_t* S, int32_t* pairs, float* ms,
                float* scores_opt, bool first_self_done = false, bool posenc_done = false);
+void lg_assign_stage(hipStream_t s, LgBuffers& b, int P, int L, float thr, int cap, int32_t* S, int32_t* pairs, float* ms,
+                     float* scores_opt, int scores_pair /*launch_lg_assign's*/, const float* wm, const float* bm);
 int lg_stage(rfe_ctx* c, LgBuffers& b, const float* k0n, const float* k1n, const float* d0, const float* d1,
              const int32_t* m, const int32_t* n, int P, int Mmax, int Nmax, int L);
 

@@ -114,6 +114,15 @@ void lg_self_block(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, float* x, con
     }
 }
 
+// the assignment stage on b.sim / b.x / b.lens: matchability head (z = log sigmoid), row and column log-sum-exp, both argmaxes, mutual check + filter +
+// ordered compaction.  Leaves b.z, b.rowlse, b.collse, b.a0, b.mx0, b.a1 behind; (P, L) selects the form (launch_lg_assign).  rfe_k_lightglue_assign runs it alone.
+void lg_assign_stage(hipStream_t s, LgBuffers& b, int P, int L, float thr, int cap, int32_t* S, int32_t* pairs, float* ms,
+                     float* scores_opt, int scores_pair, const float* wm, const float* bm) {
+    if (!lg_assign_few_pairs(P, L)) launch_lg_matchability(s, b.x, wm, bm, (int64_t)2 * P * L, b.z);   // few pairs: inside the row log-sum-exp launch
+    launch_lg_assign(s, b.sim, b.z, b.z + (size_t)P * L, P, L, cap, b.lens, b.lens + P, thr, scores_opt, b.rowlse,
+                     b.collse, b.a0, b.mx0, b.a1, S, pairs, ms, scores_pair, b.x, wm, bm, b.z);
+}
+
 // runs the 9 layers + assignment on already staged b.x / b.kn / b.lens / b.kvmap.
 // first_self_done: b.x already holds the output of layer 0's self block and b.csn the rotary table
 // (stream mode computes them once per FRAME instead of once per pair side).
@@ -153,9 +162,7 @@ int lg_forward(rfe_ctx* c, LgBuffers& b, int P, int L, float thr, int cap, int32
     int scores_pair = -1;
     if (tap && c->tap.scores && !scores_opt) { scores_opt = c->tap.scores; scores_pair = c->tap.pair; }
     { ProfScope p(c, "lg_assign");
-      if (!lg_assign_few_pairs(P, L)) launch_lg_matchability(s, b.x, W.wm, W.bm, rows, b.z);   // few pairs: inside the row log-sum-exp launch
-      launch_lg_assign(s, b.sim, b.z, b.z + (size_t)P * L, P, L, cap, b.lens, b.lens + P, thr, scores_opt, b.rowlse,
-                       b.collse, b.a0, b.mx0, b.a1, S, pairs, ms, scores_pair, b.x, W.wm, W.bm, b.z); }
+      lg_assign_stage(s, b, P, L, thr, cap, S, pairs, ms, scores_opt, scores_pair, W.wm, W.bm); }
     if (tap) {
         if (c->tap.x0) RFE_HIP(c, hipMemcpyAsync(c->tap.x0, b.x + (size_t)c->tap.pair * L * 256, (size_t)L * 1024, hipMemcpyDeviceToDevice, s));
         if (c->tap.x1) RFE_HIP(c, hipMemcpyAsync(c->tap.x1, b.x + (size_t)(P + c->tap.pair) * L * 256, (size_t)L * 1024, hipMemcpyDeviceToDevice, s));

@@ -849,7 +849,7 @@ void launch_lg_assign(hipStream_t s, const float* sim, const float* z0, const fl
                       const int* m, const int* n, float thr, float* scores_opt, float* rowlse, float* collse,
                       int32_t* a0, float* mx0, int32_t* a1, int32_t* S, int32_t* pairs, float* ms, int scores_pair,
                       const float* x, const float* wm, const float* bm, float* z) {
-    if (lg_assign_few_pairs(P, L) && x) {
+    if (lg_assign_few_pairs(P, L)) {
         hipLaunchKernelGGL(lg_rowlse_z_kernel, dim3((L + 3) / 4, P, 2), dim3(256), 0, s, sim, L, P, m, n, rowlse, x, wm, bm, z);
         if (L <= 1024) hipLaunchKernelGGL((lg_col_kernel<16, 64, true>), dim3((L + 15) / 16, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);   // m <= L <= 16 x 64 rows: the column in registers
         else hipLaunchKernelGGL((lg_col_kernel<16, 64>), dim3((L + 15) / 16, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);
@@ -860,8 +860,6 @@ void launch_lg_assign(hipStream_t s, const float* sim, const float* z0, const fl
     hipLaunchKernelGGL(lg_rowlse_kernel, dim3((L + 3) / 4, P), dim3(256), 0, s, sim, L, m, n, rowlse);
     if (L <= 1024 && L % 32 == 0 && (long long)P * (L / 32) >= 256)   // throughput shape: stripe resident in LDS, read from HBM once
         hipLaunchKernelGGL(lg_col_lds_kernel, dim3(L / 32, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);
-    else if ((long long)P * ((L + 31) / 32) < 128)   // a few pairs: narrower stripes, 4x the threads per workgroup
-        hipLaunchKernelGGL((lg_col_kernel<16, 64>), dim3((L + 15) / 16, P), dim3(1024), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);
     else
         hipLaunchKernelGGL((lg_col_kernel<32, 8>), dim3((L + 31) / 32, P), dim3(256), 0, s, sim, z0, z1, rowlse, L, m, n, collse, a1);
     hipLaunchKernelGGL(lg_rowarg_kernel, dim3((L + 3) / 4, P), dim3(256), 0, s, sim, z0, z1, rowlse, collse, L, m, n, a0, mx0, scores_opt, scores_pair);
