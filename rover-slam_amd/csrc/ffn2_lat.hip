@@ -19,14 +19,12 @@
 //     (one workgroup per panel) would leave half the chip idle and need a 64 KB weight stage;
 //   * fragment layout, slot swizzle (slot c of row R at c ^ (R & 15), applied on the source side of the weight copy), transposed product
 //     (a lane ends with four consecutive output columns of one row: bias / residual / store are one 16-byte access each) and the k order
-//     inside a 16-k group are gemm_lat.hip's; the GELU is lg_ln_gelu_kernel's (Abramowitz-Stegun erf, |error| <= 1.5e-7).
+//     inside a 16-k group are gemm_lat.hip's; the GELU is gelu_short (dev_prims.h).
 // LDS: 32 KB panel + 4 x 32 KB ring = 160 KB (one workgroup per CU).  Roofline: fp32 MFMA, algorithmic 2 M N K FLOP.
 #include "rfe_internal.h"
+#include "dev_prims.h"
 
 namespace rfe {
-
-typedef __attribute__((address_space(3))) void* f2l_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* f2l_gptr_t;
 
 namespace {
 constexpr int F2_K = 512, F2_BM = 16, F2_BN = 128, F2_LBK = 64, F2_ST = 4, F2_NW = 8;
@@ -34,14 +32,6 @@ constexpr int F2_PANEL_F = F2_BM * F2_K;            // 8192 floats
 constexpr int F2_STAGE_F = F2_BN * F2_LBK;          // 8192 floats
 constexpr int F2_NDMA = F2_BN / (4 * F2_NW);        // 4 copy instructions per wave and stage (one moves 4 rows of 256 B)
 constexpr int F2_LDS_BYTES = F2_ST * F2_STAGE_F * 4;   // dynamic part (the ring); the panel is a static 32 KB array
-
-__device__ __forceinline__ float f2_gelu(float t) {   // == lg_kernels.hip gelu_short_ / gemm.hip gelu_short: one GELU for every LightGlue tiling
-    const float x = t * 0.70710678118654752f, ax = fabsf(x);
-    const float k = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    const float poly = fmaf(fmaf(fmaf(fmaf(1.061405429f, k, -1.453152027f), k, 1.421413741f), k, -0.284496736f), k, 0.254829592f) * k;
-    const float er = 1.0f - poly * __builtin_amdgcn_exp2f(-(ax * ax) * 1.44269504088896341f);
-    return 0.5f * t * (1.0f + copysignf(er, x));
-}
 }  // namespace
 
 __global__ __launch_bounds__(64 * F2_NW, 1) void ffn2_ln_lat_kernel(const float* __restrict__ h, const float* __restrict__ W, const float* __restrict__ bias,
@@ -54,9 +44,9 @@ __global__ __launch_bounds__(64 * F2_NW, 1) void ffn2_ln_lat_kernel(const float*
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
-    // both column tiles of a row panel on one XCD (blocks are dealt round-robin over the 8 XCDs): the panel crosses the fabric once
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int nt = t_ & 1, mt = (t_ >> 1) * 8 + xcd;
+    // both column tiles of a row panel on one XCD: the panel crosses the fabric once
+    const XcdBlock blk = xcd_decode_pow2<2>(blockIdx.x);
+    const int nt = blk.inner, mt = blk.unit;
     if (mt >= MT) return;
     const int n0 = nt * F2_BN, m0 = mt * F2_BM;
 
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(64 * F2_NW, 1) void ffn2_ln_lat_kernel(const float*
     auto issue = [&](int t, int st) {
 #pragma unroll
         for (int u = 0; u < F2_NDMA; ++u)
-            __builtin_amdgcn_global_load_lds((f2l_gptr_t)(src[u] + t * F2_LBK), (f2l_lds_ptr_t)(ring + st * F2_STAGE_F + (wave + F2_NW * u) * 4 * F2_LBK), 16, 0, 0);
+            lds_dma16(src[u] + t * F2_LBK, ring + st * F2_STAGE_F + (wave + F2_NW * u) * 4 * F2_LBK);
     };
     constexpr int T = F2_K / F2_LBK;   // 8
 #pragma unroll
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(64 * F2_NW, 1) void ffn2_ln_lat_kernel(const float*
         const int c = psub + 32 * i;                               // 16-byte slot of the 512-k row: k = 4 c .. 4 c + 3
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2_gelu(hv[i][e] * rs * gg[i][e] + bb[i][e]);
+        for (int e = 0; e < 4; ++e) o[e] = gelu_short(hv[i][e] * rs * gg[i][e] + bb[i][e]);
         // 64-k block c >> 4, slot c & 15 of row prow stored at (c & 15) ^ prow: the fragment reads below are conflict-free ds_read_b128
         *reinterpret_cast<f32x4*>(panel + (c >> 4) * (F2_BM * F2_LBK) + prow * F2_LBK + ((((c & 15) ^ prow)) << 2)) = o;
     }
@@ -166,7 +156,7 @@ bool launch_ffn2_ln_lat(hipStream_t s, const float* h, const float* w2, const fl
     const int MT = (M + F2_BM - 1) / F2_BM;
     static bool ls_[64];
     ensure_dynamic_lds((const void*)ffn2_ln_lat_kernel, F2_LDS_BYTES, ls_);
-    hipLaunchKernelGGL(ffn2_ln_lat_kernel, dim3(2 * ((MT + 7) / 8 * 8)), dim3(64 * F2_NW), F2_LDS_BYTES, s, h, w2, b2, ln_g, ln_b, R, ldr, C, ldc, M, MT);
+    hipLaunchKernelGGL(ffn2_ln_lat_kernel, dim3(2 * xcd_padded(MT)), dim3(64 * F2_NW), F2_LDS_BYTES, s, h, w2, b2, ln_g, ln_b, R, ldr, C, ldc, M, MT);
     return true;
 }
 

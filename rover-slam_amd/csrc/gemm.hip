@@ -14,21 +14,11 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "rfe_internal.h"
+#include "dev_prims.h"
 
 namespace rfe {
 
 constexpr int BK = 32, LDT = BK + 1;
-
-// GELU(erf) with a short branch-free erf: Abramowitz-Stegun 7.1.26, |erf error| <= 1.5e-7 (libm erff: <= 1 ulp = 6e-8), about a
-// third of the instructions of the library erff (ffn.3 with the fused LayerNorm + GELU: 3.30 -> 3.13 ms per step).  Over the 20-case
-// tolerance study the match-score deviation from the oracle is unchanged (<= 1.9e-4, lists identical): profiles/r02_ab_notes.md.
-__device__ __forceinline__ float gelu_short(float t) {
-    const float x = t * 0.70710678118654752f, ax = fabsf(x);
-    const float k = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    const float poly = fmaf(fmaf(fmaf(fmaf(1.061405429f, k, -1.453152027f), k, 1.421413741f), k, -0.284496736f), k, 0.254829592f) * k;
-    const float er = 1.0f - poly * __builtin_amdgcn_exp2f(-(ax * ax) * 1.44269504088896341f);
-    return 0.5f * t * (1.0f + copysignf(er, x));
-}
 
 // NB = 32-column MFMA blocks per wave: wave tile 64 x (NB*32), workgroup tile 128 x (NB*64).
 // NB = 4 (128x256 tile, 49 KB LDS, 3 workgroups/CU) measured best for N % 256 == 0
@@ -46,8 +36,6 @@ __device__ __forceinline__ float gelu_short(float t) {
 // of the K tile is summed, in a different order than k ascending -- LightGlue only (SuperPoint's 1x1 heads stay bit-exact on the
 // padded path).  LDS instructions per K tile and wave: 36 instead of 144.
 // (The B tile by LDS-DMA on this tile measured within 1.3 % -- ffn.0 269.5 -> 266.1 us, qkv 218.6 -> 216.3 -- and was not adopted: profiles/r03_ab_notes.md.)
-typedef __attribute__((address_space(3))) void* gemm_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gemm_gptr_t;
 // ROPE (the qkv projection on the k-permuted throughput tile): LightGlue's rotary encoding of the q | k column tiles in the epilogue, so that the attention
 // kernel takes K tiles straight into LDS (lg_attention_dma_kernel for the self blocks too).  The table rows of the workgroup's 128 token rows (256 B
 // each = the 32 (cos, sin) pairs every head shares) are copied by global_load_lds_dwordx4 into a 32 KB dynamic LDS tile when the workgroup STARTS --
@@ -175,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
         for (int u = 0; u < 8; ++u) {
             int row = m0 + wave * 32 + u * 4 + (lane >> 4);
             row = row < M ? row : M - 1;
-            __builtin_amdgcn_global_load_lds((gemm_gptr_t)(g.rope_csn + (size_t)row * 64 + (lane & 15) * 4), (gemm_lds_ptr_t)(lds_dynamic + (wave * 32 + u * 4) * 64), 16, 0, 0);
+            lds_dma16(g.rope_csn + (size_t)row * 64 + (lane & 15) * 4, lds_dynamic + (wave * 32 + u * 4) * 64);
         }
     }
     if (LNI) ln_tile();   // first tile: nothing to hide it under

@@ -15,15 +15,9 @@
 // fp16] = 64-byte rows of four 16-byte slots, slot s = 2 c + h stored at s ^ ((row >> 2) & 3) -- ds_read_b128 fragment reads and the
 // staging writes are bank-conflict free.  Epilogue (bias in the accumulator, alpha, residual, LayerNorm partials) as gemm.hip.
 #include "rfe_internal.h"
-#include "h2_split.h"
+#include "dev_prims.h"
 
 namespace rfe {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split2_f16(float x, float y, uint32_t& hi, uint32_t& lo) { h2_split2(x, y, hi, lo); }   // h2_split.h
 
 // fp32 [n] -> fp16 planes hi [n], lo [n] (n even)
 __global__ void split_f16_kernel(const float* __restrict__ x, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, size_t n) {
@@ -38,21 +32,11 @@ void launch_split_f16(hipStream_t s, const float* x, uint16_t* hi, uint16_t* lo,
     hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)((n / 2 + 256) / 256)), dim3(256), 0, s, x, hi, lo, n);
 }
 
-__device__ __forceinline__ float gelu_short_h2(float t) {   // = gemm.hip:gelu_short (Abramowitz-Stegun 7.1.26)
-    const float x = t * 0.70710678118654752f, ax = fabsf(x);
-    const float k = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    const float poly = fmaf(fmaf(fmaf(fmaf(1.061405429f, k, -1.453152027f), k, 1.421413741f), k, -0.284496736f), k, 0.254829592f) * k;
-    const float er = 1.0f - poly * __builtin_amdgcn_exp2f(-(ax * ax) * 1.44269504088896341f);
-    return 0.5f * t * (1.0f + copysignf(er, x));
-}
-
 // The weight planes never touch a register -- they are copied by global_load_lds_dwordx4 into a DOUBLE-buffered LDS tile (2 x 32 KB;
 // with the 16 KB A tile = 80 KB per workgroup: exactly two workgroups per CU, tools/kbench/lds_occupancy.hip), tile t + 1 requested
 // right after tile t is published, together with the A rows of tile t + 1 (16 registers); the 16-byte-slot swizzle is applied on the
 // SOURCE address (the LDS side of the copy is lane-linear: lane l of a wave instruction fills bytes 16 l .. of 1 KB = 16 rows).
 // Without it (register staging of all twelve loads of a tile at its top; measured and removed) both workgroups of a CU end up waiting for L2 / HBM together.
-typedef __attribute__((address_space(3))) void* h2_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* h2_gptr_t;
 template <bool RES, bool LNA>
 __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
     constexpr int BM = 128, BN = 256, BK = 32, MB = 2, NB = 4;
@@ -68,12 +52,13 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int i = lane & 31, h = lane >> 5;
-    // XCD-aware block order (blocks are dealt round-robin to the 8 XCDs): the N / 256 column tiles of one 128-row panel are consecutive
-    // workgroups of ONE XCD, so the panel's second (third) read of A hits that XCD's L2 instead of HBM -- at the f16 rate these
-    // kernels run within 1.5x of their HBM time, and A read once instead of N / 256 times is a third of the traffic
+    // the N / 256 column tiles of one 128-row panel are consecutive workgroups of ONE XCD, so the panel's second (third) read of A hits
+    // that XCD's L2 instead of HBM -- at the f16 rate these kernels run within 1.5x of their HBM time, and A read once instead of
+    // N / 256 times is a third of the traffic
     const int ncol = g.N / BN;
-    const int xb = blockIdx.x & 7, tb = blockIdx.x >> 3;
-    const int bx = tb % ncol, by = (tb / ncol) * 8 + xb;
+    const XcdBlock blk = xcd_decode(blockIdx.x, ncol);
+    const int bx = blk.inner, by = blk.unit;
+    __builtin_assume(bx >= 0);   // the block index is never negative: the column offsets n0 + ... stay zero-extended to 64 bits
     if (by * BM >= g.M) return;
     const int m0 = by * BM, n0 = bx * BN;
     const int M = g.M;
@@ -142,8 +127,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
             const int grp = wave * 4 + u;
             const size_t src = (size_t)(n0 + grp * 16 + (lane >> 2)) * g.ldb + k0 + 8 * ((lane & 3) ^ (lane >> 4));
             unsigned char* const dst = Bs + b * (2 * BPL) + grp * 1024;
-            __builtin_amdgcn_global_load_lds((h2_gptr_t)(g.Bh + src), (h2_lds_ptr_t)dst, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((h2_gptr_t)(g.Bl + src), (h2_lds_ptr_t)(dst + BPL), 16, 0, 0);
+            lds_dma16(g.Bh + src, dst);
+            lds_dma16(g.Bl + src, dst + BPL);
         }
     };
     auto stageA = [&](int k0) {   // [LayerNorm + GELU,] split, write the A planes
@@ -153,14 +138,14 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
         for (int it = 0; it < 4; ++it) {
             float4 v = fa[it];
             if (LNA) {   // same operation order as lg_ln_gelu / gemm.hip: ((a - mean) * rstd) * g + b, then GELU
-                v.x = gelu_short_h2((v.x - ln_mean[it]) * ln_rstd[it] * rg.x + rbeta.x);
-                v.y = gelu_short_h2((v.y - ln_mean[it]) * ln_rstd[it] * rg.y + rbeta.y);
-                v.z = gelu_short_h2((v.z - ln_mean[it]) * ln_rstd[it] * rg.z + rbeta.z);
-                v.w = gelu_short_h2((v.w - ln_mean[it]) * ln_rstd[it] * rg.w + rbeta.w);
+                v.x = gelu_short((v.x - ln_mean[it]) * ln_rstd[it] * rg.x + rbeta.x);
+                v.y = gelu_short((v.y - ln_mean[it]) * ln_rstd[it] * rg.y + rbeta.y);
+                v.z = gelu_short((v.z - ln_mean[it]) * ln_rstd[it] * rg.z + rbeta.z);
+                v.w = gelu_short((v.w - ln_mean[it]) * ln_rstd[it] * rg.w + rbeta.w);
             }
             uint32_t h0, l0, h1, l1;
-            split2_f16(v.x, v.y, h0, l0);
-            split2_f16(v.z, v.w, h1, l1);
+            h2_split2(v.x, v.y, h0, l0);
+            h2_split2(v.z, v.w, h1, l1);
             *reinterpret_cast<u32x2*>(As + adst[it]) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(As + BM * 64 + adst[it]) = u32x2{l0, l1};
         }
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_kernel(GemmArgs g) {
 // Called by launch_gemm_nt for the shapes it would give the 128 x 256 throughput tile (N % 256 == 0, K % 32 == 0, no batch / m_valid /
 // relu): returns the number of partial-statistics pairs per row it wrote (0 without stats_out), like launch_gemm_nt.
 int launch_gemm_h2(hipStream_t s, const GemmArgs& g) {
-    const int panels8 = (((g.M + 127) / 128) + 7) / 8 * 8;   // row panels padded to a multiple of 8: the block -> (panel, column tile) decode stays bijective
+    const int panels8 = xcd_padded((g.M + 127) / 128);   // row panels
     const dim3 grid((unsigned)(panels8 * (g.N / 256)));
     const bool res = g.R != nullptr, lna = g.stats_in != nullptr;
     constexpr int kDmaLds = 2 * 128 * 64 + 2 * 2 * 256 * 64;   // 80 KB

@@ -29,14 +29,9 @@
 //   the K loop runs at 43.
 // Roofline: fp32 MFMA peak 157.3 TFLOP/s, algorithmic 2 M N K FLOP.
 #include "rfe_internal.h"
-#include "h2_split.h"
+#include "dev_prims.h"
 
 namespace rfe {
-
-typedef _Float16 glat_f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t glat_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* glat_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glat_gptr_t;
 
 constexpr int LBK = 64;       // k per stage: LDS rows of 256 B
 
@@ -61,10 +56,10 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
     if (H2) h2_saturate_mode();                           // an activation past fp16's range saturates instead of turning its row into NaN (h2_split.h)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
-    // all column tiles of one activation panel on one XCD (blocks are dealt round-robin over the 8 XCDs)
+    // all column tiles of one activation panel on one XCD
     const int NT = g.N / BN;
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int nt = t_ % NT, mt = (t_ / NT) * 8 + xcd;
+    const XcdBlock blk = xcd_decode(blockIdx.x, NT);
+    const int nt = blk.inner, mt = blk.unit;
     if (mt >= MT) return;
     const int n0 = nt * BN, m0 = mt * BM;
     const int wn = wave % WGN, wm = wave / WGN;
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
         for (int u = 0; u < NDMA; ++u) {
             const bool wrow = H2 && (wave + NW * u) * 4 < BN;          // a weight-row group of the split form: fp16 planes, k0 halves
             const float* p = (second ? src2[u] : src[u]) + (wrow ? k0 / 2 : k0);
-            __builtin_amdgcn_global_load_lds((glat_gptr_t)p, (glat_lds_ptr_t)(lds + st * STAGE_F + (wave + NW * u) * 4 * LBK), 16, 0, 0);
+            lds_dma16(p, lds + st * STAGE_F + (wave + NW * u) * 4 * LBK);
         }
     };
 
@@ -146,11 +141,11 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
             // nothing: at 16 cycles per matrix instruction these kernels wait for the copies -- 8 MB per stage over the chip at ~10 TB/s.)
 #pragma unroll
             for (int g32 = 0; g32 < LBK / 32; ++g32) {
-                glat_f16x8 wh[WI], wl[WI], ah[WJ], al[WJ];
+                f16x8 wh[WI], wl[WI], ah[WJ], al[WJ];
 #pragma unroll
                 for (int i = 0; i < WI; ++i) {
-                    wh[i] = *reinterpret_cast<const glat_f16x8*>(ws + i * 16 * LBK + (((4 * g32 + q) ^ r) << 2));
-                    wl[i] = *reinterpret_cast<const glat_f16x8*>(ws + i * 16 * LBK + (((8 + 4 * g32 + q) ^ r) << 2));
+                    wh[i] = *reinterpret_cast<const f16x8*>(ws + i * 16 * LBK + (((4 * g32 + q) ^ r) << 2));
+                    wl[i] = *reinterpret_cast<const f16x8*>(ws + i * 16 * LBK + (((8 + 4 * g32 + q) ^ r) << 2));
                 }
 #pragma unroll
                 for (int j = 0; j < WJ; ++j) {
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(64 * WGN * WGM, 1) void gemm_lat_kernel(GemmArgs g,
                     uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
                     h2_split2(x0[0], x0[1], h0, l0); h2_split2(x0[2], x0[3], h1, l1);
                     h2_split2(x1[0], x1[1], h2, l2); h2_split2(x1[2], x1[3], h3, l3);
-                    ah[j] = __builtin_bit_cast(glat_f16x8, glat_u32x4{h0, h1, h2, h3}); al[j] = __builtin_bit_cast(glat_f16x8, glat_u32x4{l0, l1, l2, l3});
+                    ah[j] = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3}); al[j] = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
                 }
 #pragma unroll
                 for (int i = 0; i < WI; ++i)
@@ -258,7 +253,7 @@ bool launch_gemm_lat(hipStream_t s, const GemmArgs& g, const float* rope_csn, in
         const int MT = (g.M + BM_ - 1) / BM_;                                                                                    \
         auto kern = h2 ? gemm_lat_kernel<WI_, WJ_, WGN_, WGM_, LS_, RES_, ROPE_, true> : gemm_lat_kernel<WI_, WJ_, WGN_, WGM_, LS_, RES_, ROPE_, false>; \
         static bool ls_[2][64]; ensure_dynamic_lds((const void*)kern, BYTES_, ls_[h2 ? 1 : 0]);                                  \
-        hipLaunchKernelGGL(kern, dim3((g.N / BN_) * ((MT + 7) / 8 * 8), batch), dim3(64 * WGN_ * WGM_), BYTES_, s, g, rope_csn, rope_cols, MT);  \
+        hipLaunchKernelGGL(kern, dim3((g.N / BN_) * xcd_padded(MT), batch), dim3(64 * WGN_ * WGM_), BYTES_, s, g, rope_csn, rope_cols, MT);  \
         return true;                                                                                                             \
     } while (0)
     // ring depth: as many 64-k stages as the 160 KB of LDS hold, at most 6 (measured: 3 is as fast -- the kernel is bound by the matrix

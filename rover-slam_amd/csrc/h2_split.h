@@ -10,6 +10,7 @@
 namespace rfe {
 
 typedef _Float16 h2_f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h2_f16x8 __attribute__((ext_vector_type(8)));   // one fp16 operand register group of a v_mfma_f32_32x32x16_f16
 
 // (x, y) -> hi = (fp16 x, fp16 y) packed (x in the low half), lo = the packed residuals
 __device__ __forceinline__ void h2_split2(float x, float y, uint32_t& hi, uint32_t& lo) {
@@ -20,6 +21,15 @@ __device__ __forceinline__ void h2_split2(float x, float y, uint32_t& hi, uint32
         "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
         : "=&v"(l) : "v"(hi), "v"(x), "v"(y));
     lo = l;
+}
+
+// eight floats -> the fp16 hi / lo operand registers of a v_mfma_f32_32x32x16_f16
+__device__ __forceinline__ void h2_split8(const float* x, h2_f16x8& hi, h2_f16x8& lo) {
+    struct { uint32_t w[4]; } h, l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h2_split2(x[2 * e], x[2 * e + 1], h.w[e], l.w[e]);
+    hi = __builtin_bit_cast(h2_f16x8, h);
+    lo = __builtin_bit_cast(h2_f16x8, l);
 }
 
 // The same split, saturating in software (two v_med3_f32 more per float): x is clamped to +-131008 and its high part to +-65504, so both

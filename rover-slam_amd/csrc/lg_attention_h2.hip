@@ -28,50 +28,11 @@
 // Operands past fp16's range saturate instead of overflowing (MODE.FP16_OVFL, h2_split.h): finite results outside the option's domain.
 // Rotary (self blocks): applied to q and k with the same three fp32 operations as lg_attention_kernel, before the split.
 #include "rfe_internal.h"
-#include "h2_split.h"
+#include "dev_prims.h"
 
 namespace rfe {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int AH_K = 64;
-constexpr float AH_DEFER = 11.0f;   // log2 units: P <= 2^11 between two moves of the reference
-
-__device__ __forceinline__ void ah_split2(float x, float y, uint32_t& hi, uint32_t& lo) { h2_split2(x, y, hi, lo); }   // h2_split.h: 3 VALU per pair
-__device__ __forceinline__ void ah_split8(const float* x, f16x8& hi, f16x8& lo) {
-    u32x4 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { uint32_t a, b; ah_split2(x[2 * e], x[2 * e + 1], a, b); h[e] = a; l[e] = b; }
-    hi = __builtin_bit_cast(f16x8, h);
-    lo = __builtin_bit_cast(f16x8, l);
-}
-
-// online softmax step of one 32-key x 32-query block: lg_kernels.hip's at_softmax_step with this kernel's threshold
-__device__ __forceinline__ void ah_softmax_step(f32x16& st, bool first, float& m_run, float& l_run, f32x16& o0, f32x16& o1) {
-    float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
-#pragma unroll
-    for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
-    mx = fmaxf(mx, st[15]);
-    if (__any(first || mx > AH_DEFER)) {
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float ref = first ? 0.f : m_run;
-        const float m_new = fmaxf(m_run, mx + ref);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        const float d = ref - m_new;
-        l_run *= alpha;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st[r] += d; o0[r] *= alpha; o1[r] *= alpha; }
-    }
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { st[r] = __builtin_amdgcn_exp2f(st[r]); ps += st[r]; }
-    l_run += ps;
-}
 
 constexpr int AH_NQB = 2;   // 32-query blocks per wave (workgroup = 128 AH_NQB queries)
 template <bool ROPE>
@@ -83,9 +44,8 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
     constexpr int AH_Q = 128 * AH_NQB;
     h2_saturate_mode();
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 4 * AH_K * 128];
-    // XCD-aware decode as lg_attention_kernel: the query blocks of one (sequence, head) run on one XCD
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int qb = t_ % nqb, unit = (t_ / nqb) * 8 + xcd;
+    const XcdBlock blk = xcd_decode(blockIdx.x, nqb);   // the query blocks of one (sequence, head) run on one XCD
+    const int qb = blk.inner, unit = blk.unit;
     if (unit >= 4 * nseq_total) return;
     const int seq = unit >> 2, head = unit & 3;
     const int kvseq = kv_map ? kv_map[seq] : seq;
@@ -129,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] *= kScale;
-            ah_split8(t, qh[b][s], ql[b][s]);
+            h2_split8(t, qh[b][s], ql[b][s]);
         }
     }
 
@@ -184,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
             const int row = skey + 32 * it;
             const float t[8] = {rk[it][0].x, rk[it][0].y, rk[it][0].z, rk[it][0].w, rk[it][1].x, rk[it][1].y, rk[it][1].z, rk[it][1].w};
             f16x8 hi, lo;
-            ah_split8(t, hi, lo);
+            h2_split8(t, hi, lo);
             const int off = row * 128 + ((soct ^ ((row >> 1) & 7)) << 4);
             *reinterpret_cast<f16x8*>(Kh + off) = hi;
             *reinterpret_cast<f16x8*>(Kl + off) = lo;
@@ -200,8 +160,8 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
             const float x2 = c == 0 ? rv[2].x : c == 1 ? rv[2].y : c == 2 ? rv[2].z : rv[2].w;
             const float x3 = c == 0 ? rv[3].x : c == 1 ? rv[3].y : c == 2 ? rv[3].z : rv[3].w;
             uint32_t h0, l0, h1, l1;
-            ah_split2(x0, x1, h0, l0);
-            ah_split2(x2, x3, h1, l1);
+            h2_split2(x0, x1, h0, l0);
+            h2_split2(x2, x3, h1, l1);
             *reinterpret_cast<u32x2*>(Vh + off) = u32x2{h0, h1};
             *reinterpret_cast<u32x2*>(Vl + off) = u32x2{l0, l1};
         }
@@ -236,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
                 f32x16 st[AH_NQB];
 #pragma unroll
                 for (int b = 0; b < AH_NQB; ++b) {
-                    const float init = first ? 0.f : -m_run[b];
+                    const float init = softmax_init(first, m_run[b]);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) st[b][r] = init;
                 }
@@ -267,13 +227,13 @@ __global__ __launch_bounds__(256, 2) void lg_attention_h2_kernel(
                             if (key >= nk) st[b][r] = -INFINITY;
                         }
                     }
-                    ah_softmax_step(st[b], first, m_run[b], l_run[b], o[b][0], o[b][1]);
+                    softmax_step<SOFTMAX_DEFER_H2>(st[b], first, m_run[b], l_run[b], o[b][0], o[b][1]);
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         float t[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) t[e] = st[b][8 * s + e];
-                        ah_split8(t, ph[b][s], pl[b][s]);
+                        h2_split8(t, ph[b][s], pl[b][s]);
                     }
                 }
                 // ---- O^T[d][query] += sum_key V[key][d] P[key][query]
@@ -326,7 +286,7 @@ void launch_lg_attention_h2(hipStream_t s, const float* q, const float* k, const
                             const int* qlen, const int* klen, const int* kv_map, const float* rope_csn) {
     constexpr int AH_Q = 128 * AH_NQB;
     const int nqb = (Lq + AH_Q - 1) / AH_Q;
-    const int units8 = (4 * nseq + 7) / 8 * 8;
+    const int units8 = xcd_padded(4 * nseq);
     if (rope_csn)
         hipLaunchKernelGGL((lg_attention_h2_kernel<true>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, nseq, rope_csn);
     else

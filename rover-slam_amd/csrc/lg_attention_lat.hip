@@ -19,28 +19,13 @@
 // The rotary encoding is NOT applied here: the one-pair qkv projection (gemm_lat.hip, ROPE epilogue) has already rotated q and k.
 // Roofline: fp32 MFMA peak; algorithmic 4 heads * 4 * 64 * sum n_q n_k FLOP.
 #include "rfe_internal.h"
-#include "h2_split.h"
+#include "dev_prims.h"
 
 namespace rfe {
-
-typedef _Float16 alat_f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t alat_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* alat_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* alat_gptr_t;
 
 constexpr int AL_K = 32;                         // keys per tile
 constexpr int AL_TILE_F = AL_K * 64;             // floats of one K (or V) tile
 constexpr int AL_WAVE_F = 2 * AL_TILE_F;         // per wave: one K tile | one V tile
-constexpr float AL_DEFER = 16.0f;                // log2 units (lg_kernels.hip: AT_DEFER)
-constexpr float AL_DEFER_H2 = 11.0f;             // split form: P = 2^(S - ref) must stay below fp16's 65504 (lg_attention_h2.hip)
-
-// eight floats -> fp16 hi / lo operand registers of a v_mfma_f32_32x32x16_f16 (h2_split.h)
-__device__ __forceinline__ void alat_split8(const float (&t)[8], alat_f16x8& hi, alat_f16x8& lo) {
-    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
-    h2_split2(t[0], t[1], h0, l0); h2_split2(t[2], t[3], h1, l1); h2_split2(t[4], t[5], h2, l2); h2_split2(t[6], t[7], h3, l3);
-    hi = __builtin_bit_cast(alat_f16x8, alat_u32x4{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(alat_f16x8, alat_u32x4{l0, l1, l2, l3});
-}
 
 // H2 (RFE_OPT_LG_FP16X2, default off): both products of a tile as SPLIT products on the f16 matrix pipe -- K, Q, V and P = 2^(S - ref) as fp16
 // hi + lo (h2_split.h), three v_mfma_f32_32x32x16_f16 per 32 x 32 x 16 block: 24 matrix instructions of 32 cycles per 32-key tile instead of 64
@@ -54,8 +39,8 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];   // AL_NW waves x AL_WAVE_F floats (16 KB each); the merge needs AL_NW x 32 x 68 floats
     constexpr int NT_ = 64 * AL_NW;
     // all query blocks of one (sequence, head) on one XCD: its K / V (512 KB) is fetched into one L2
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int qb = t_ % nqb, unit = (t_ / nqb) * 8 + xcd;
+    const XcdBlock blk = xcd_decode(blockIdx.x, nqb);
+    const int qb = blk.inner, unit = blk.unit;
     if (unit >= 4 * nseq_total) return;
     const int seq = unit >> 2, head = unit & 3;
     const int kvseq = kv_map ? kv_map[seq] : seq;
@@ -75,7 +60,7 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
     const size_t qrow_c = (size_t)seq * Lq + (qrow < Lq ? qrow : Lq - 1);
     constexpr float kScale = 0.125f * 1.44269504088896341f;   // 1 / sqrt(64) * log2(e): softmax in base 2, folded into Q
     float qreg[32];   // qreg[4 g + e] = Q[query][8 g + 4 h + e] * scale  (the k order of the swizzled K image, lg_attention_dma_kernel)
-    alat_f16x8 qh[4], ql[4];   // H2: k-step s holds head dimensions 16 s + 8 h .. + 7 of this lane's query, as fp16 hi / lo
+    f16x8 qh[4], ql[4];   // H2: k-step s holds head dimensions 16 s + 8 h .. + 7 of this lane's query, as fp16 hi / lo
     if constexpr (H2) {
         h2_saturate_mode();
         const f32x4* qp4 = reinterpret_cast<const f32x4*>(q + qrow_c * ld + head * 64);
@@ -83,7 +68,7 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
         for (int s4 = 0; s4 < 4; ++s4) {
             const f32x4 t0 = qp4[4 * s4 + 2 * h], t1 = qp4[4 * s4 + 2 * h + 1];
             const float t[8] = {t0[0] * kScale, t0[1] * kScale, t0[2] * kScale, t0[3] * kScale, t1[0] * kScale, t1[1] * kScale, t1[2] * kScale, t1[3] * kScale};
-            alat_split8(t, qh[s4], ql[s4]);
+            h2_split8(t, qh[s4], ql[s4]);
         }
     } else {
         const f32x4* qp4 = reinterpret_cast<const f32x4*>(q + qrow_c * ld + head * 64) + h;
@@ -121,13 +106,13 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
         const float* base = kbase + (size_t)k0 * ld;
         if (k0 + AL_K <= nk) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) __builtin_amdgcn_global_load_lds((alat_gptr_t)(base + koff[u]), (alat_lds_ptr_t)(Kr + u * 256), 16, 0, 0);
+            for (int u = 0; u < 8; ++u) lds_dma16(base + koff[u], Kr + u * 256);
         } else {   // the sequence's last, partial tile: keys past the end read the last valid row (finite) and are masked in S
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int row = u * 4 + crow;
                 const int rc = k0 + row < nk ? row : nk - 1 - k0;
-                __builtin_amdgcn_global_load_lds((alat_gptr_t)(base + rc * ld + ((cslot ^ (row & 15)) << 2)), (alat_lds_ptr_t)(Kr + u * 256), 16, 0, 0);
+                lds_dma16(base + rc * ld + ((cslot ^ (row & 15)) << 2), Kr + u * 256);
             }
         }
     };
@@ -136,13 +121,13 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
         const float* base = vbase + (size_t)k0 * ld;
         if (k0 + AL_K <= nk) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) __builtin_amdgcn_global_load_lds((alat_gptr_t)(base + voff[u]), (alat_lds_ptr_t)(Vr + u * 256), 16, 0, 0);
+            for (int u = 0; u < 8; ++u) lds_dma16(base + voff[u], Vr + u * 256);
         } else {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int row = u * 4 + crow;
                 const int rc = k0 + row < nk ? row : nk - 1 - k0;
-                __builtin_amdgcn_global_load_lds((alat_gptr_t)(base + rc * ld + (cslot << 2)), (alat_lds_ptr_t)(Vr + u * 256), 16, 0, 0);
+                lds_dma16(base + rc * ld + (cslot << 2), Vr + u * 256);
             }
         }
     };
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
         f32x16 st;
         const bool first = t == 0;
         {
-            const float init = first ? 0.f : -m_run;
+            const float init = softmax_init(first, m_run);
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[r] = init;
         }
@@ -203,8 +188,8 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
                 const float t[8] = {kf[2 * s4][0], kf[2 * s4][1], kf[2 * s4][2], kf[2 * s4][3], kf[2 * s4 + 1][0], kf[2 * s4 + 1][1], kf[2 * s4 + 1][2], kf[2 * s4 + 1][3]};
-                alat_f16x8 kh, kl;
-                alat_split8(t, kh, kl);
+                f16x8 kh, kl;
+                h2_split8(t, kh, kl);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[s4], st, 0, 0, 0);   // small terms first
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[s4], st, 0, 0, 0);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[s4], st, 0, 0, 0);
@@ -224,13 +209,14 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
                 if (key >= nk) st[r] = -INFINITY;
             }
         }
-        // ---- online softmax over this lane's 16 keys (the other half-wave holds the other 16): lg_kernels.hip at_softmax_step
+        // ---- online softmax over this lane's 16 keys (the other half-wave holds the other 16): the statements of softmax_step (dev_prims.h),
+        // written out -- as a call the compiler arranges this loop body differently: profiles/dev_prims.md
         {
             float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
 #pragma unroll
             for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
             mx = fmaxf(mx, st[15]);
-            if (__any(first || mx > (H2 ? AL_DEFER_H2 : AL_DEFER))) {
+            if (__any(first || mx > (float)(H2 ? SOFTMAX_DEFER_H2 : SOFTMAX_DEFER_F32))) {
                 mx = fmaxf(mx, __shfl_xor(mx, 32));
                 const float ref = first ? 0.f : m_run;
                 const float m_new = fmaxf(m_run, mx + ref);
@@ -250,18 +236,18 @@ __global__ __launch_bounds__(64 * AL_NW, 1) void lg_attention_lat_kernel(
         if constexpr (H2) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {      // k-step s2: keys 16 s2 + 8 (e >> 2) + 4 h + (e & 3) = accumulator registers 8 s2 + e
-                alat_f16x8 ph, pl, v0h, v0l, v1h, v1l;
+                f16x8 ph, pl, v0h, v0l, v1h, v1l;
                 {
                     const float t[8] = {st[8 * s2], st[8 * s2 + 1], st[8 * s2 + 2], st[8 * s2 + 3], st[8 * s2 + 4], st[8 * s2 + 5], st[8 * s2 + 6], st[8 * s2 + 7]};
-                    alat_split8(t, ph, pl);
+                    h2_split8(t, ph, pl);
                 }
                 {
                     const float t[8] = {vf[8 * s2], vf[8 * s2 + 1], vf[8 * s2 + 2], vf[8 * s2 + 3], vf[8 * s2 + 4], vf[8 * s2 + 5], vf[8 * s2 + 6], vf[8 * s2 + 7]};
-                    alat_split8(t, v0h, v0l);
+                    h2_split8(t, v0h, v0l);
                 }
                 {
                     const float t[8] = {vf[16 + 8 * s2], vf[17 + 8 * s2], vf[18 + 8 * s2], vf[19 + 8 * s2], vf[20 + 8 * s2], vf[21 + 8 * s2], vf[22 + 8 * s2], vf[23 + 8 * s2]};
-                    alat_split8(t, v1h, v1l);
+                    h2_split8(t, v1h, v1l);
                 }
                 o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0l, ph, o0, 0, 0, 0);
                 o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1l, ph, o1, 0, 0, 0);
@@ -328,7 +314,7 @@ bool launch_lg_attention_lat(hipStream_t s, const float* q, const float* k, cons
                              const int* qlen, const int* klen, const int* kv_map, bool h2) {
     if ((size_t)nseq * Lq > 8192 || (ld % 4) || Lq < 1 || Lk < 1) return false;
     const int nqb = (Lq + 31) / 32;
-    const int units8 = (4 * nseq + 7) / 8 * 8;    // (sequence, head) units padded to a multiple of 8: the block decode stays bijective
+    const int units8 = xcd_padded(4 * nseq);      // (sequence, head) units
     constexpr int bytes = (AL_NW * AL_WAVE_F > AL_NW * 32 * 68 ? AL_NW * AL_WAVE_F : AL_NW * 32 * 68) * 4;   // tiles, later the merge
 #define RFE_ALAT_GO(H2_)                                                                                                                  \
     do {                                                                                                                                  \

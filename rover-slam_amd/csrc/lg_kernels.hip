@@ -6,6 +6,7 @@
 // fp32 throughout (descriptor tolerance 1e-4 of the north star rules out bf16 operands).
 #include <stdlib.h>
 #include "rfe_internal.h"
+#include "dev_prims.h"
 
 namespace rfe {
 
@@ -31,43 +32,8 @@ void launch_lg_posenc(hipStream_t s, const float* kn, const float* wr, int rows,
 //         order of the reduction is permuted to the D-layout order, so P never moves).
 // 64 MFMA (32x32x2 f32) per 32x32 tile, no wasted FLOPs: 4*L*L*64 per head.
 constexpr int AT_Q = 128, AT_K = 64, AT_LDK = 65;
-constexpr float AT_DEFER = 16.0f;   // log2 units
 constexpr int AT_SPLIT_MAX = 8;               // key ranges of the split variant
 constexpr size_t AT_SPLIT_MAX_ROWS = 8192;    // only problems this small are latency-bound enough to split
-
-// Online softmax step on one 32-key x 32-query S^T block, trimmed for VALU count: on gfx950 the fp32 MFMA runs at the vector rate
-// (64 FLOP / clk / SIMD) and every VALU instruction of ANY wave of the SIMD measurably costs matrix-pipe time (the softmax removed:
-// +12 % with the staging gone, profiles/r01_pmc.md; LayerNorm + GELU on ffn.3's operand path: its full VALU time), so the steady
-// state does as little as it can:
-//   * the reference maximum is subtracted INSIDE the accumulation -- the accumulator starts at -m_run instead of 0 (at_softmax_init) --
-//     so no subtraction per element;
-//   * the tile maximum is a v_max3 tree per lane, compared against the deferred-rescale threshold WITHOUT combining the two half-waves
-//     (__any covers both); only the rare branch (always the first tile) combines them, moves the reference and shifts the block;
-//   * the row sum stays a per-half-wave partial; the halves are added once after the last tile (at_softmax_finish).
-// st: in = S^T block relative to the reference, out = P^T block.  first: wave-uniform, the first tile of this wave's key range.
-__device__ __forceinline__ float at_softmax_init(bool first, float m_run) { return first ? 0.f : -m_run; }
-__device__ __forceinline__ void at_softmax_step(f32x16& st, bool first, float& m_run, float& l_run, f32x16& o0, f32x16& o1) {
-    float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
-#pragma unroll
-    for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
-    mx = fmaxf(mx, st[15]);
-    if (__any(first || mx > AT_DEFER)) {
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float ref = first ? 0.f : m_run;            // what the accumulator already subtracted
-        const float m_new = fmaxf(m_run, mx + ref);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // m_run = -inf on the first tile -> 0
-        const float d = ref - m_new;
-        l_run *= alpha;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st[r] += d; o0[r] *= alpha; o1[r] *= alpha; }
-    }
-    float ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { st[r] = __builtin_amdgcn_exp2f(st[r]); ps += st[r]; }
-    l_run += ps;
-}
-__device__ __forceinline__ float at_softmax_finish(float l_run) { return l_run + __shfl_xor(l_run, 32); }
 
 // SPLIT: split-key variant for latency-bound problems (one pair = 64 (sequence, head, query block) units for 256 CUs and
 // a 2048-MFMA serial chain per wave): blockIdx.y selects one of gridDim.y key ranges, the workgroup writes its
@@ -93,11 +59,10 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
     constexpr bool DBUF = false;   // (the double-buffered variant measured 4 % slower; kept out of the build)
     __shared__ float Ks[1][AT_K * AT_LDK];
     __shared__ float Vs[1][AT_K * 64];
-    // XCD-aware decode (blocks are dealt round-robin to the 8 XCDs): all query blocks of one
-    // (sequence, head) run on the same XCD so its K/V (512 KB) is fetched into one L2 only.
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int qb = t_ % nqb, unit = (t_ / nqb) * 8 + xcd;
-    if (unit >= 4 * nseq_total) return;   // the grid is padded to a multiple of 8 (sequence, head) units so that the decode stays bijective
+    // all query blocks of one (sequence, head) run on the same XCD so its K/V (512 KB) is fetched into one L2 only
+    const XcdBlock blk = xcd_decode(blockIdx.x, nqb);
+    const int qb = blk.inner, unit = blk.unit;
+    if (unit >= 4 * nseq_total) return;
     const int seq = unit >> 2, head = unit & 3;
     const int kvseq = kv_map ? kv_map[seq] : seq;
     const int nq = qlen ? qlen[seq] : Lq;
@@ -200,11 +165,11 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
 #pragma unroll
         for (int sub = 0; sub < AT_K / 32; ++sub) {
             if (k0 + sub * 32 >= nk) break;
-            // ---- S^T[key][query] = sum_d K[key][d] * Q[query][d] (relative to the running reference maximum: at_softmax_step)
+            // ---- S^T[key][query] = sum_d K[key][d] * Q[query][d] (relative to the running reference maximum: softmax_step)
             f32x16 st;
             const bool first = k0 == kbeg && sub == 0;
             {
-                const float init = at_softmax_init(first, m_run);
+                const float init = softmax_init(first, m_run);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) st[r] = init;
             }
@@ -222,7 +187,7 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
                     if (key >= nk) st[r] = -INFINITY;
                 }
             }
-            at_softmax_step(st, first, m_run, l_run, o0, o1);
+            softmax_step<SOFTMAX_DEFER_F32>(st, first, m_run, l_run, o0, o1);
             // ---- O^T[d][query] += sum_key V[key][d] * P[key][query]; k-step r uses key(r,h)
             const float* va = Vs[buf] + (sub * 32 + 4 * h) * 64 + j;
             if (prio) __builtin_amdgcn_s_setprio(1);
@@ -240,7 +205,7 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
             buf ^= 1;
         }
     }
-    l_run = at_softmax_finish(l_run);
+    l_run = softmax_finish(l_run);
     if (SPLIT) {
         if (qrow < Lq) {
             const size_t prow = ((size_t)blockIdx.y * nseq_total + seq) * Lq + qrow;
@@ -282,8 +247,6 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
 // therefore multiplies k = 8 g + e and 8 g + 4 + e: the sum over the head dimension runs in a permuted order (tolerance-checked
 // like every LightGlue kernel), Q is loaded in that order with eight float4 loads.  V image: plain [key][64].  Keys past the
 // sequence length are read from the last valid row (finite) and masked in S.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
 constexpr int AD_K = 32;
 __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld, float* __restrict__ out,
@@ -296,8 +259,8 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     extern __shared__ __attribute__((aligned(16))) float ad_lds[];
     float (*Kd)[AD_K * 64] = reinterpret_cast<float (*)[AD_K * 64]>(ad_lds);
     float (*Vd)[AD_K * 64] = reinterpret_cast<float (*)[AD_K * 64]>(ad_lds + 2 * AD_K * 64);
-    const int Lb = blockIdx.x, xcd = Lb & 7, t_ = Lb >> 3;
-    const int qb = t_ % nqb, unit = (t_ / nqb) * 8 + xcd;
+    const XcdBlock blk = xcd_decode(blockIdx.x, nqb);
+    const int qb = blk.inner, unit = blk.unit;
     if (unit >= 4 * nseq_total) return;
     const int seq = unit >> 2, head = unit & 3;
     const int kvseq = kv_map ? kv_map[seq] : seq;
@@ -343,8 +306,8 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
             int key = k0 + row; key = key < nk ? key : nk - 1;
             const float* ksrc = kbase + (size_t)key * ld + ((cslot ^ (row & 15)) << 2);
             const float* vsrc = vbase + (size_t)key * ld + (cslot << 2);
-            __builtin_amdgcn_global_load_lds((gptr_t)ksrc, (lds_ptr_t)(Kd[buf] + (wave * 8 + u * 4) * 64), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)vsrc, (lds_ptr_t)(Vd[buf] + (wave * 8 + u * 4) * 64), 16, 0, 0);
+            lds_dma16(ksrc, Kd[buf] + (wave * 8 + u * 4) * 64);
+            lds_dma16(vsrc, Vd[buf] + (wave * 8 + u * 4) * 64);
         }
     };
     if (nk > 0) issue(0, 0);
@@ -357,7 +320,7 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
         f32x16 st;
         const bool first = k0 == 0;
         {
-            const float init = at_softmax_init(first, m_run);
+            const float init = softmax_init(first, m_run);
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[r] = init;
         }
@@ -377,7 +340,7 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
                 if (key >= nk) st[r] = -INFINITY;
             }
         }
-        at_softmax_step(st, first, m_run, l_run, o0, o1);
+        softmax_step<SOFTMAX_DEFER_F32>(st, first, m_run, l_run, o0, o1);
         const float* va = Vd[buf] + (4 * h) * 64 + j;
         if (prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -389,7 +352,7 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
         if (prio) __builtin_amdgcn_s_setprio(0);
         buf ^= 1;
     }
-    l_run = at_softmax_finish(l_run);
+    l_run = softmax_finish(l_run);
     if (qrow < Lq) {
         const float inv = (qrow < nq && l_run > 0.f) ? 1.0f / l_run : 0.f;
         float* op = out + ((size_t)seq * Lq + qrow) * 256 + head * 64;
@@ -450,10 +413,8 @@ void launch_lg_attention(hipStream_t s, const float* q, const float* k, const fl
     // in-workgroup key split (lg_attention_lat.hip) -- no partial sums in HBM, no combine launch
     if (!rope_csn && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS && launch_lg_attention_lat(s, q, k, v, ld, out, nseq, Lq, Lk, qlen, klen, kv_map, fp16x2)) return;
     const int nqb = (Lq + AT_Q - 1) / AT_Q;
-    // (sequence, head) units, padded to a multiple of 8: the kernels deal their blocks round-robin over the 8 XCDs and map
-    // block -> (unit, query block) by unit = (t / nqb) * 8 + xcd, which is a bijection only for a multiple of 8 units
-    // (2P sequences always are; the per-frame self block of the stream mode runs on B sequences, e.g. 33)
-    const int units8 = (4 * nseq + 7) / 8 * 8;
+    // (sequence, head) units (2P sequences always are a multiple of 8; the per-frame self block of the stream mode runs on B sequences, e.g. 33)
+    const int units8 = xcd_padded(4 * nseq);
     const bool rope = rope_csn != nullptr;
     // latency shapes the kernel above does not serve: fewer (sequence, head, query block) units than CUs -> split the keys until the chip is covered
     if (part && (size_t)nseq * Lq <= AT_SPLIT_MAX_ROWS) {
@@ -486,13 +447,6 @@ void launch_lg_attention(hipStream_t s, const float* q, const float* k, const fl
 // dropped: every 16-row wave tile re-evaluates the GELU of its whole 16 x 512 activation panel, 8 column workgroups per panel = 8 x the
 // transcendentals, and a wave alone on its SIMD cannot hide 3200 VALU instructions behind 256 matrix instructions: 17.6 us against
 // 4.5 + 7 us for this pass + the plain GEMM, profiles/r04_ab_notes.md)
-__device__ __forceinline__ float gelu_short_(float t) {   // Abramowitz-Stegun 7.1.26 erf, |error| <= 1.5e-7 (== gemm.hip gelu_short)
-    const float x = t * 0.70710678118654752f, ax = fabsf(x);
-    const float k = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    const float poly = fmaf(fmaf(fmaf(fmaf(1.061405429f, k, -1.453152027f), k, 1.421413741f), k, -0.284496736f), k, 0.254829592f) * k;
-    const float er = 1.0f - poly * __builtin_amdgcn_exp2f(-(ax * ax) * 1.44269504088896341f);
-    return 0.5f * t * (1.0f + copysignf(er, x));
-}
 __global__ __launch_bounds__(256) void lg_ln_gelu_kernel(float* __restrict__ hbuf, const float* __restrict__ g,
                                                          const float* __restrict__ b, int64_t rows) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -518,7 +472,7 @@ __global__ __launch_bounds__(256) void lg_ln_gelu_kernel(float* __restrict__ hbu
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float vv = x[e] * rs * gg[e] + bb[e];
-        x[e] = gelu_short_(vv);     // the GELU of the fused throughput path (gemm.hip gelu_short): one arithmetic for every LightGlue tiling
+        x[e] = gelu_short(vv);
     }
     p[0] = make_float4(x[0], x[1], x[2], x[3]);
     p[1] = make_float4(x[4], x[5], x[6], x[7]);
@@ -733,8 +687,6 @@ __global__ __launch_bounds__(CW * RG) void lg_col_kernel(const float* __restrict
 // 32 columns x m rows ONCE, by global_load_lds_dwordx4 (a wave instruction moves eight 128-byte row segments = 1 KB, which is also
 // 1 KB of the [row][32] LDS image: a linear copy, no VGPRs), and walks LDS three times.  One workgroup per CU (128 KB + 8 KB of LDS).
 // Reduction tree: 32 row groups per column (rows rg, rg + 32, ...), combined in ascending group order.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
 __global__ __launch_bounds__(1024) void lg_col_lds_kernel(const float* __restrict__ sim, const float* __restrict__ z0,
                                                           const float* __restrict__ z1, const float* __restrict__ rowlse, int L,
                                                           const int* __restrict__ m, const int* __restrict__ n,
@@ -754,7 +706,7 @@ __global__ __launch_bounds__(1024) void lg_col_lds_kernel(const float* __restric
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const float* src = base + (size_t)(lane >> 3) * L + (lane & 7) * 4;
         for (int q = wave; q * 8 < mm; q += 16)      // rows 8 q .. 8 q + 7 (rows up to L - 1 exist: L % 8 == 0)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)q * 8 * L), (lds_ptr_t)(stripe + q * 8 * CW), 16, 0, 0);
+            lds_dma16(src + (size_t)q * 8 * L, stripe + q * 8 * CW);
     }
     __syncthreads();                            // every wave's copies have landed (vmcnt(0) in front of the barrier)
     const float* col = stripe + c;

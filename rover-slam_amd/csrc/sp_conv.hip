@@ -17,6 +17,7 @@
 // Roofline: compute bound on the fp32 MFMA peak (157.3 TFLOP/s); algorithmic 2*9*Cin*Cout FLOP/px.
 #include <stdlib.h>
 #include "rfe_internal.h"
+#include "dev_prims.h"
 
 namespace rfe {
 
@@ -141,20 +142,19 @@ __device__ __forceinline__ void conv_store(const f32x16 (&acc)[2][2], float* __r
     }
 }
 
-// XCD-aware block decode (1-D grid): blocks are dealt round-robin to the 8 XCDs, each with its own L2.  The nct output-channel
-// tiles of one pixel tile read the same input tile: they are made consecutive on ONE XCD (linear = ((u / 8) * nct + ct) * 8 + u % 8
-// for pixel tile u), so the haloed input tile is fetched into one L2 instead of nct of them (conv3b: 2, the 256-channel heads: 4).
+// Block decode (1-D grid, xcd_decode).  The nct output-channel tiles of one pixel tile read the same input tile: they run on ONE XCD,
+// so the haloed input tile is fetched into one L2 instead of nct of them (conv3b: 2, the 256-channel heads: 4).
 struct ConvBlock { int b, bx, by, ct; bool valid; };
 __device__ __forceinline__ ConvBlock conv_decode(int nct, int gx, int gy, int ntiles) {
-    const int L = blockIdx.x, xcd = L & 7, t = L >> 3;
+    const XcdBlock x = xcd_decode(blockIdx.x, nct);
     ConvBlock k;
-    k.ct = t % nct;
-    const int u = (t / nct) * 8 + xcd;
+    k.ct = x.inner;
+    const int u = x.unit;
     k.valid = u < ntiles;
     k.bx = u % gx; k.by = (u / gx) % gy; k.b = u / (gx * gy);
     return k;
 }
-static inline unsigned conv_grid(int gx, int gy, int B, int nct) { return (unsigned)(((gx * gy * B + 7) / 8) * 8 * nct); }
+static inline unsigned conv_grid(int gx, int gy, int B, int nct) { return (unsigned)(xcd_padded(gx * gy * B) * nct); }
 
 // TAG only gives each SuperPoint layer its own kernel symbol (per-layer rows in rocprofv3 --stats)
 template <int CIN, bool POOL, bool RELU, int TAG>
@@ -374,8 +374,6 @@ constexpr int T16_H = 4, T16_W = 16, T16_IH = T16_H + 2, T16_IW = T16_W + 2, T16
 //     16 pixels); granule g of pixel p is stored at g ^ ((p >> 2) & 3) -- swizzle on the source address -- so that the B-operand read of the
 //     16 x-consecutive pixels of a lane group (word p * 16 + ...) is conflict-free; pixels outside the image read a zero line;
 //   * every wave issues the same number of copies per stage (5 + 2; surplus slots re-copy a valid line into padding).
-typedef __attribute__((address_space(3))) void* conv_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* conv_gptr_t;
 constexpr int T16D_WROWS = 144, T16D_PIX = 128;    // ring-stage capacities: weight rows (18 copy slots of 8), pixels (108 used: 8 slots of 16); 3 x 26 KB = 78 KB
 __device__ __attribute__((aligned(64))) float t16d_zero_line[16];   // zero-initialised: the source of every out-of-image pixel
 
@@ -452,10 +450,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_t16d_kernel(
         float* idst = lin + (st % 3) * IST_W;
 #pragma unroll
         for (int u = 0; u < WCP; ++u)
-            __builtin_amdgcn_global_load_lds((conv_gptr_t)(w_src[u] + (size_t)st * BLK_W), (conv_lds_ptr_t)(wdst + w_slot[u] * 256), 16, 0, 0);
+            lds_dma16(w_src[u] + (size_t)st * BLK_W, wdst + w_slot[u] * 256);
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            __builtin_amdgcn_global_load_lds((conv_gptr_t)(i_src[u] + (i_img[u] ? st * T16_CK : 0)), (conv_lds_ptr_t)(idst + (wave + 4 * u) * 256), 16, 0, 0);
+            lds_dma16(i_src[u] + (i_img[u] ? st * T16_CK : 0), idst + (wave + 4 * u) * 256);
     };
     issue(0);
     if (NST > 1) issue(1);

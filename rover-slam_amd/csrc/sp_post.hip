@@ -6,6 +6,7 @@
 // All kernels here are HBM/latency bound (a few MB per frame); arithmetic orders are the canonical
 // ones of oracle/rfe_oracle.c so that scores / keypoints / descriptors are bit-exact.
 #include "rfe_internal.h"
+#include "dev_prims.h"
 
 namespace rfe {
 
@@ -529,7 +530,6 @@ __global__ __launch_bounds__(256) void select_rank_kernel(const unsigned long lo
     const unsigned long long key = keys[t];
     int rank = 0;
     // part p scans the key pairs p, p + 4, ... (16-byte LDS reads, eight in flight: one dependent 8-byte read per iteration was 17 us)
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const u64x2* kp = reinterpret_cast<const u64x2*>(keys);
     const int npair = nsel >> 1;
 #pragma unroll 8
@@ -593,7 +593,6 @@ __global__ __launch_bounds__(256) void select_rankall_kernel(const float* __rest
         }
         const bool live = t < count;
         const unsigned long long key = live ? make_key(cs[t], ci[t]) : ~0ull;
-        typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
         const u64x2* kp = reinterpret_cast<const u64x2*>(keys);
         int rank = 0;
         for (int w = 0; w < nwin; ++w) {
@@ -807,7 +806,6 @@ __global__ __launch_bounds__(256) void select_rankall_keys_kernel(const unsigned
                                                                   int32_t* __restrict__ kxy, float* __restrict__ score) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const int b = blockIdx.y, tid = threadIdx.x;
     const int count = cand_cnt[2 * b];
     const unsigned long long* ck = cand_keys + (size_t)b * HW;
