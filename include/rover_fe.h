@@ -524,6 +524,13 @@ int rfe_k_linear(rfe_ctx* ctx, const float* a_dev, int M, int K, const float* w_
 int rfe_k_scoremap(rfe_ctx* ctx, const uint8_t* img_dev, int H, int W, int stride, int B,
                    float* scoremap_dev /*[B,Hs,Ws] pre-NMS, Hs = 8*(H/8), Ws = 8*(W/8)*/,
                    float* nms_dev /*[B,Hs,Ws] post-NMS+border*/, float* descmap_dev /*[B,H/8,W/8,256]*/);
+/* The sparse descriptor head of calls with more than four frames (descriptor stages only on the cells that keypoints sample), alone and through the
+ * forward's own code, behind the backbone of B frames and for caller-provided keypoints n_dev [B], kxy_dev [B,Kmax,2].  poison != 0: its workspace is
+ * filled with NaN words first.  Outputs (each may be NULL): cell_row_dev [B,(H/8)*(W/8)] row of a cell within its frame or -1, count_dev [B] live rows
+ * per frame, rows_dev [B*cap,256] with cap = min(4*Kmax, (H/8)*(W/8)): the normalised descriptor rows, frame after frame without gaps, ascending cell order
+ * inside a frame (sum(count) rows are written), desc_dev [B,Kmax,256] sampled through cell_row. */
+int rfe_k_sparse_desc(rfe_ctx* ctx, const uint8_t* img_dev, int H, int W, int stride, int B, int Kmax, const int32_t* n_dev, const int32_t* kxy_dev,
+                      int poison, int32_t* cell_row_dev, int32_t* count_dev, float* rows_dev, float* desc_dev);
 /* keypoint selection alone on a post-NMS map (H, W multiples of 8 as the score-map frame always is): n [B], kxy [B,Kmax,2], score [B,Kmax] */
 int rfe_k_select(rfe_ctx* ctx, const float* nms_dev /*[B,H,W]*/, int B, int H, int W, int Kmax, float thr, int topk_always,
                  int32_t* n_dev, int32_t* kxy_dev, float* score_dev);

@@ -20,6 +20,9 @@ static void sp_layout(Bump& a, int B, int H, int W, SpBuffers& b) {   // ws_sp
     b.mask = a.take<uint8_t>(hw); b.supp = a.take<uint8_t>(hw);
     b.cand_score = a.take<float>(hw); b.cand_idx = a.take<int32_t>(hw);
     b.sel_keys = a.take<unsigned long long>((size_t)B * 4096); b.sel_n = a.take<int32_t>(B);   // Kmax <= 4096
+    // sparse descriptor head: cell_cnt = [B] rows per frame, [B + 1] their prefix sums; the patches lie over p1 | a2 (see SpBuffers)
+    b.cell_row = a.take<int32_t>(cells); b.row_cell = a.take<int32_t>(cells); b.cell_cnt = a.take<int32_t>(2 * (size_t)B + 1);
+    b.patch = b.p1;
 }
 size_t sp_ws_bytes(int B, int H, int W) { SpBuffers b; return layout_bytes([&](Bump& a) { sp_layout(a, B, H, W, b); }); }
 int sp_carve(rfe_ctx* c, int B, int H, int W, SpBuffers& b) {
@@ -42,11 +45,12 @@ int sp_check(rfe_ctx* c, int H, int W, int B, int Kmax) {
     return RFE_OK;
 }
 
-// backbone + heads up to the NMS'ed score map and the normalised descriptor map
+// backbone + heads up to the NMS'ed score map and the normalised descriptor map (dense_head = false: no descriptor head at all -- the caller runs
+// sp_desc_rows behind its keypoint selection; nothing is forked then)
 // join = false: the caller still has detector-only work to enqueue and joins the descriptor stream itself
 // (hipStreamWaitEvent(c->stream, c->ev_join)) when `forked` comes back true
 int sp_forward_maps(rfe_ctx* c, const void* img, int H, int W, int stride, int B, SpBuffers& b, bool join, bool& forked, bool img_f32, long long frame_step,
-                    float thr, bool want_maps) {
+                    float thr, bool want_maps, bool dense_head) {
     forked = false;
     int rc = sp_carve(c, B, H, W, b);
     if (rc) return rc;
@@ -68,12 +72,14 @@ int sp_forward_maps(rfe_ctx* c, const void* img, int H, int W, int stride, int B
     // side stream while the detector head continues on the main one with its tail of small bandwidth / latency-bound
     // kernels (convPb, softmax, 5 NMS passes, selection), which would otherwise leave most of the chip idle.
     // With events around every stage (full profiling pass) the heads stay serial so that the stage times are clean.
-    const bool fork = !(c->prof && c->prof_filter.empty());
+    const bool fork = dense_head && !(c->prof && c->prof_filter.empty());
     hipStream_t sd = fork ? c->side_stream : s;
     if (fork) { RFE_HIP(c, hipEventRecord(c->ev_fork, s)); RFE_HIP(c, hipStreamWaitEvent(sd, c->ev_fork, 0)); }
-    { ProfScope p(c, "convDa", sd); launch_conv3x3(sd, b.f4, B, Hc, Wc, 128, w.packed[L_DA], w.bias[L_DA], 256, true, kSpLayers[L_DA].pool, b.da, L_DA); }
-    { ProfScope p(c, "convDb", sd); launch_gemm_nt(sd, gemm_plain(b.da, 256, w.packed[L_DB], 256, w.bias[L_DB], b.dmap, 256, cells, 256, 256)); }
-    { ProfScope p(c, "sp_post", sd); launch_descmap_norm(sd, b.dmap, cells); }
+    if (dense_head) {
+        { ProfScope p(c, "convDa", sd); launch_conv3x3(sd, b.f4, B, Hc, Wc, 128, w.packed[L_DA], w.bias[L_DA], 256, true, kSpLayers[L_DA].pool, b.da, L_DA); }
+        { ProfScope p(c, "convDb", sd); launch_gemm_nt(sd, gemm_plain(b.da, 256, w.packed[L_DB], 256, w.bias[L_DB], b.dmap, 256, cells, 256, 256)); }
+        { ProfScope p(c, "sp_post", sd); launch_descmap_norm(sd, b.dmap, cells); }
+    }
     if (fork) RFE_HIP(c, hipEventRecord(c->ev_join, sd));
     { ProfScope p(c, "convPa"); launch_conv3x3(s, b.f4, B, Hc, Wc, 128, w.packed[L_PA], w.bias[L_PA], 256, true, kSpLayers[L_PA].pool, b.pa, L_PA); }
     { ProfScope p(c, "convPb"); launch_gemm_nt(s, gemm_plain(b.pa, 256, w.packed[L_PB], 256, w.bias[L_PB], b.logits, 65, cells, 65, 256)); }
@@ -96,11 +102,41 @@ int sp_forward_maps(rfe_ctx* c, const void* img, int H, int W, int stride, int B
     return RFE_OK;
 }
 
+// The descriptor head on the cells the keypoints sample, for calls of more than four frames (the regime split of the detector tail).  desc_sample_kernel
+// reads the <= 4 cells around each of <= Kmax keypoints and nothing else of the map -- 30 % of a VGA frame's 4800 cells at Kmax = 1024 -- so the two
+// matrix stages run on those cells only, as rows of two plain GEMMs, on the main stream behind the selection:
+//   cell list (ascending cell order per frame, no atomics; the frames' rows packed back to back) -> patch [rows, 1152] = each cell's 3x3x128 neighbourhood of f4 in the conv's reduction order,
+//   +0.0f outside the map -> convDa as relu(bias + patch . W^T) with W = the OIHW weight [256][1152] -> convDb -> L2 norm, every stage on the live rows
+//   (launches sized for B cap rows, the count read on the device: workgroups past it return at once; no host synchronisation).
+// The plain GEMM path is the k-ascending chain from the bias that the conv kernels run per output, and it does not care which matrix
+// row a cell sits in: the rows equal the dense map's cells bit for bit (tests/test_gpu_sparse_desc.py).  Leaves b.dmap = rows [row_base[B], 256].
+int sp_desc_rows(rfe_ctx* c, SpBuffers& b, int B, int Hc, int Wc, int Kmax, const int32_t* n, const int32_t* kxy) {
+    hipStream_t s = c->stream;
+    const SpWeightsDev& w = c->sp;
+    const int cap = sp_desc_cap(Kmax, Hc, Wc);
+    int32_t* const row_base = b.cell_cnt + B;
+    { ProfScope p(c, "sp_desc_cells");
+      launch_desc_cells(s, B, Hc, Wc, 8 * Hc, 8 * Wc, n, kxy, Kmax, cap, b.cell_row, b.row_cell, b.cell_cnt, row_base);
+      launch_desc_gather(s, b.f4, B, Hc, Wc, cap, b.row_cell, b.cell_cnt, row_base, b.patch); }
+    { ProfScope p(c, "convDa_rows");
+      GemmArgs g = gemm_plain(b.patch, 1152, w.da_rows, 1152, w.bias[L_DA], b.da, 256, B * cap, 256, 1152);
+      g.relu = 1; g.m_valid = row_base + B;
+      launch_gemm_nt(s, g); }
+    { ProfScope p(c, "convDb_rows");
+      GemmArgs g = gemm_plain(b.da, 256, w.packed[L_DB], 256, w.bias[L_DB], b.dmap, 256, B * cap, 256, 256);
+      g.m_valid = row_base + B;
+      launch_gemm_nt(s, g); }
+    { ProfScope p(c, "sp_desc_norm"); launch_descrows_norm(s, b.dmap, B, cap, b.cell_cnt, row_base); }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
 int sp_forward(rfe_ctx* c, const void* img, int H, int W, int stride, int B, int Kmax, float thr,
                int32_t* n, int32_t* kxy, float* score, float* desc, uint8_t* desc_bin, bool img_f32, long long frame_step) {
     SpBuffers b;
     bool forked;
-    int rc = sp_forward_maps(c, img, H, W, stride, B, b, false, forked, img_f32, frame_step, thr);
+    const bool sparse = B > 4;   // up to four frames the dense head on the side stream hides under the detector tail and wins
+    int rc = sp_forward_maps(c, img, H, W, stride, B, b, false, forked, img_f32, frame_step, thr, false, !sparse);
     if (rc) return rc;
     const int Hc = H / 2 / 2 / 2, Wc = W / 2 / 2 / 2, Hs = 8 * Hc, Ws = 8 * Wc;   // score-map frame, see sp_forward_maps
     { ProfScope p(c, "sp_select");
@@ -110,7 +146,12 @@ int sp_forward(rfe_ctx* c, const void* img, int H, int W, int stride, int B, int
       } else
       launch_select(c->stream, b.nmap, B, Hs, Ws, Kmax, thr, b.cand_score, b.cand_idx, n, kxy, score, (int32_t*)b.ss /*NMS scratch, free by now*/, c->hp.sp_topk_always != 0, b.sel_keys, b.sel_n);
       if (forked) RFE_HIP(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));   // descriptor map ready
-      launch_desc_sample(c->stream, b.dmap, B, Hc, Wc, Hs, Ws, n, kxy, Kmax, desc, desc_bin); }
+      if (!sparse) launch_desc_sample(c->stream, b.dmap, B, Hc, Wc, Hs, Ws, n, kxy, Kmax, desc, desc_bin); }
+    if (sparse) {
+        if ((rc = sp_desc_rows(c, b, B, Hc, Wc, Kmax, n, kxy))) return rc;
+        ProfScope p(c, "sp_desc_sample");
+        launch_desc_sample(c->stream, b.dmap, B, Hc, Wc, Hs, Ws, n, kxy, Kmax, desc, desc_bin, b.cell_row, b.cell_cnt + B);
+    }
     RFE_HIP(c, hipGetLastError());
     return RFE_OK;
 }

@@ -60,6 +60,39 @@ extern "C" int rfe_k_scoremap(rfe_ctx* c, const uint8_t* img, int H, int W, int 
     return RFE_OK;
 }
 
+// The sparse descriptor head (sp_desc_rows, the forward's own: cell list, row gather, convDa and convDb on rows, L2 norm) behind the backbone of B frames,
+// for CALLER-PROVIDED keypoints n [B], kxy [B,Kmax,2] (device) -- so the tests place footprints on the map's edges and beyond them, whatever B.  poison != 0
+// fills the patch buffer, both activation buffers and the row tables with 0xFFFFFFFF words (NaN) between the backbone and the head: nothing past the live
+// rows may reach a result.  Outputs (device, each may be null): cell_row [B,Hc*Wc] (row within the frame or -1), count [B], rows [B*cap,256] with
+// cap = min(4 Kmax, Hc Wc): the frames' live rows back to back (frame b's from row count[0] + .. + count[b-1] on; only those sum(count) rows are
+// meaningful), desc [B,Kmax,256] = desc_sample_kernel through cell_row.
+extern "C" int rfe_k_sparse_desc(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B, int Kmax, const int32_t* n, const int32_t* kxy, int poison,
+                                 int32_t* cell_row, int32_t* count, float* rows, float* desc) {
+    int rc = sp_check(c, H, W, B, Kmax);
+    if (rc) return rc;
+    if (!img || !n || !kxy || stride < W) return fail(c, RFE_ERR_INVALID, "k_sparse_desc: null pointer or stride < W");
+    RFE_HIP(c, hipSetDevice(c->device));
+    SpBuffers b;
+    bool forked;
+    if ((rc = sp_forward_maps(c, img, H, W, stride, B, b, true, forked, false, 0, 0.0005f, false, false))) return rc;   // sp_cnt stays dirty: zeroed before the next forward
+    const int Hc = H / 8, Wc = W / 8, cap = sp_desc_cap(Kmax, Hc, Wc);
+    const size_t cells = (size_t)B * Hc * Wc, live = (size_t)B * cap;
+    hipStream_t s = c->stream;
+    if (poison) {
+        const struct { void* p; size_t words; } fill[] = {{b.patch, live * 1152}, {b.da, cells * 256}, {b.dmap, cells * 256}, {b.cell_row, cells},
+                                                          {b.row_cell, cells}, {b.cell_cnt, (size_t)2 * B + 1}};
+        for (const auto& f : fill) RFE_HIP(c, hipMemsetD32Async((hipDeviceptr_t)f.p, -1, f.words, s));
+    }
+    if ((rc = sp_desc_rows(c, b, B, Hc, Wc, Kmax, n, kxy))) return rc;
+    if (desc) launch_desc_sample(s, b.dmap, B, Hc, Wc, 8 * Hc, 8 * Wc, n, kxy, Kmax, desc, nullptr, b.cell_row, b.cell_cnt + B);
+    RFE_HIP(c, hipGetLastError());
+    if (cell_row) RFE_HIP(c, hipMemcpyAsync(cell_row, b.cell_row, cells * 4, hipMemcpyDeviceToDevice, s));
+    if (count) RFE_HIP(c, hipMemcpyAsync(count, b.cell_cnt, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    if (rows) RFE_HIP(c, hipMemcpyAsync(rows, b.dmap, live * 256 * 4, hipMemcpyDeviceToDevice, s));
+    RFE_HIP(c, hipStreamSynchronize(s));
+    return RFE_OK;
+}
+
 // keypoint selection alone on a caller-provided post-NMS map [B,H,W] (device): candidates > thr, the top Kmax by (score descending, pixel
 // index ascending) or row-major order, through the forward's own launch_select -- so B selects the form (rank-all up to 4 frames, radix
 // select + rank sort above).  Lets the tests drive candidate counts and tie patterns no network output produces.

@@ -133,13 +133,21 @@ struct SpBuffers {
     float* cand_score; int32_t* cand_idx;
     unsigned long long* sel_keys; int32_t* sel_n;     // selected (score, pixel) keys between select_kernel and select_rank_kernel
     bool tail_fused = false;                          // sp_tail_lat_kernel ran: candidates are 64-bit keys at cand_score (cand_score | cand_idx = 8 B per pixel)
+    // sparse descriptor head (sp_desc_rows): cell -> row within its frame, row -> cell, cell_cnt = [B] rows per frame then [B + 1] their prefix sums;
+    // patch = the gathered conv input [rows, 1152], rows <= B cap, which ALIASES p1 | a2 (dead once conv2b has run; B cap 1152 <= B (HW / 64) 1152 =
+    // 18 HW floats of the 32 HW the two hold)
+    int32_t *cell_row, *row_cell, *cell_cnt; float* patch;
 };
+// rows per frame the sparse descriptor head can need: four cells per keypoint, every cell of the map at most
+inline int sp_desc_cap(int Kmax, int Hc, int Wc) { return std::min(4 * Kmax, Hc * Wc); }
 size_t sp_ws_bytes(int B, int H, int W);
 int sp_carve(rfe_ctx* c, int B, int H, int W, SpBuffers& b);    // grows ws_sp to its layout and carves it
 int sp_check(rfe_ctx* c, int H, int W, int B, int Kmax);
 int sp_forward_maps(rfe_ctx* c, const void* img, int H, int W, int stride, int B, SpBuffers& b, bool join, bool& forked, bool img_f32 = false,
                     long long frame_step = 0 /*pixels from frame b to b + 1; 0 = stride * H*/, float thr = 0.0005f /*candidate threshold of the fused tail*/,
-                    bool want_maps = false /*test hook: the fused tail also writes the score map and the NMS'ed map*/);
+                    bool want_maps = false /*test hook: the fused tail also writes the score map and the NMS'ed map*/,
+                    bool dense_head = true /*false: no descriptor head; the caller runs sp_desc_rows behind its selection*/);
+int sp_desc_rows(rfe_ctx* c, SpBuffers& b, int B, int Hc, int Wc, int Kmax, const int32_t* n, const int32_t* kxy);   // sparse descriptor head: b.dmap = the frames' rows back to back
 int sp_forward(rfe_ctx* c, const void* img, int H, int W, int stride, int B, int Kmax, float thr,
                int32_t* n, int32_t* kxy, float* score, float* desc, uint8_t* desc_bin = nullptr, bool img_f32 = false, long long frame_step = 0);
 

@@ -27,6 +27,7 @@ struct SpShared {
     ~SpShared() {
         (void)hipSetDevice(device);
         if (w.conv1a_w) (void)hipFree(w.conv1a_w);
+        if (w.da_rows) (void)hipFree(w.da_rows);
         for (int l = 0; l < 12; ++l) { if (w.packed[l]) (void)hipFree(w.packed[l]); if (w.bias[l]) (void)hipFree(w.bias[l]); }
     }
 };
@@ -103,6 +104,7 @@ static int set_sp_upload(rfe_ctx* c, const float* blob) {
             std::vector<float> t;
             pack_conv3x3_weights(w, L.cin, L.cout, L.pool, t);
             if ((rc = upload(c, &c->sp.packed[l], t.data(), t.size()))) return rc;
+            if (l == L_DA && (rc = upload(c, &c->sp.da_rows, w, wn))) return rc;   // [256][1152] as-is, for the sparse descriptor head
         } else {
             if ((rc = upload(c, &c->sp.packed[l], w, wn))) return rc;  // [N][K] as-is
         }

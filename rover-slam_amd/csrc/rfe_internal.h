@@ -36,6 +36,7 @@ struct SpWeightsDev {
     float* conv1a_w = nullptr;           // [9][64]   (kappa-major)
     float* packed[12] = {nullptr};       // 3x3 layers: [Cout/64][Cin/16][144][64]; 1x1: [N][K] as-is
     float* bias[12] = {nullptr};
+    float* da_rows = nullptr;            // convDa's weight as it comes, OIHW = [256][1152] with k = ci*9 + ky*3 + kx: the B operand of the sparse descriptor head's GEMM
 };
 
 struct LgLayerDev {
@@ -234,7 +235,17 @@ void launch_select_keys(hipStream_t s, const unsigned long long* cand_keys, int3
 void launch_keys_from_map(hipStream_t s, const float* nms, int B, int HW, float thr, unsigned long long* cand_keys, int32_t* cand_cnt);   // test hook
 void launch_descmap_norm(hipStream_t s, float* dmap, int64_t cells);
 void launch_desc_sample(hipStream_t s, const float* dmap, int B, int Hc, int Wc, int H, int W,
-                        const int32_t* n, const int32_t* kxy, int Kmax, float* desc, uint8_t* desc_bin /*optional u8 [B,Kmax,256] = desc > 0*/);
+                        const int32_t* n, const int32_t* kxy, int Kmax, float* desc, uint8_t* desc_bin /*optional u8 [B,Kmax,256] = desc > 0*/,
+                        const int32_t* cell_row = nullptr /*sparse head: dmap is packed rows, cell_row [B,Hc*Wc] the row of a cell within its frame*/,
+                        const int32_t* row_base = nullptr /*sparse head: [B] first row of every frame*/);
+// sparse descriptor head: the cells the keypoints' bilinear footprints touch, in ascending cell order per frame (cell_row [B,Hc*Wc] = row within the frame
+// or -1, row_cell [B,cap], count [B]) and the frames' rows packed back to back (row_base [B+1], exclusive prefix of count; [B] = rows of the call); their
+// 3x3x128 patches of f4 in the conv's reduction order (patch [rows,1152]); the L2 norm of the live rows
+void launch_desc_cells(hipStream_t s, int B, int Hc, int Wc, int H, int W, const int32_t* n, const int32_t* kxy, int Kmax, int cap, int32_t* cell_row,
+                       int32_t* row_cell, int32_t* count, int32_t* row_base);
+void launch_desc_gather(hipStream_t s, const float* f4, int B, int Hc, int Wc, int cap, const int32_t* row_cell, const int32_t* count, const int32_t* row_base,
+                        float* patch);
+void launch_descrows_norm(hipStream_t s, float* rows, int B, int cap, const int32_t* count, const int32_t* row_base);
 // lg_kernels.hip
 void launch_lg_posenc(hipStream_t s, const float* kn, const float* wr, int rows, float* csn /*[rows,32] (cos, sin) pairs*/);
 void launch_lg_attention(hipStream_t s, const float* q, const float* k, const float* v, int ld /*row stride of q,k,v*/,

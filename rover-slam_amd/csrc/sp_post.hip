@@ -948,11 +948,31 @@ void launch_descmap_norm(hipStream_t s, float* dmap, int64_t cells) {
     hipLaunchKernelGGL(descmap_norm_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, dmap, cells);
 }
 
+// the bilinear footprint of keypoint (x, y) on the Hc x Wc descriptor map, grid_sample(align_corners=True) at ((x-3.5)/(W-4.5), (y-3.5)/(H-4.5)):
+// continuous cell coordinates (ix, iy) and their floors.  ONE definition for the sampling kernel and for the cell list of the sparse head, which
+// must name exactly the cells the sampling reads.
+struct DescFoot { float ix, iy, fx0, fy0; int x0, y0, x1, y1; bool vx0, vx1, vy0, vy1; };
+__device__ __forceinline__ DescFoot desc_footprint(int x, int y, int H, int W, int Hc, int Wc) {
+    DescFoot f;
+    const float gx = (((float)x - 3.5f) / ((float)W - 4.5f)) * 2.0f - 1.0f;
+    const float gy = (((float)y - 3.5f) / ((float)H - 4.5f)) * 2.0f - 1.0f;
+    f.ix = ((gx + 1.0f) * 0.5f) * (float)(Wc - 1);
+    f.iy = ((gy + 1.0f) * 0.5f) * (float)(Hc - 1);
+    f.fx0 = floorf(f.ix); f.fy0 = floorf(f.iy);
+    f.x0 = (int)f.fx0; f.y0 = (int)f.fy0; f.x1 = f.x0 + 1; f.y1 = f.y0 + 1;
+    f.vx0 = f.x0 >= 0 && f.x0 < Wc; f.vx1 = f.x1 >= 0 && f.x1 < Wc; f.vy0 = f.y0 >= 0 && f.y0 < Hc; f.vy1 = f.y1 >= 0 && f.y1 < Hc;
+    return f;
+}
+
 // one wave per keypoint: bilinear grid_sample(align_corners=True, zero padding) of the normalised
 // descriptor map at ((x-3.5)/(W-4.5), (y-3.5)/(H-4.5)), then L2 normalise.
+// cell_row == null: dmap is the dense map [B, Hc, Wc, 256].  Otherwise (sparse head) dmap holds the rows of all frames back to back, frame b's from row
+// row_base[b] on, and cell_row [B, Hc * Wc] names the row within the frame of every cell a keypoint reads (desc_cells_kernel marks exactly the in-range
+// corners below, so every row looked up here is >= 0).
 __global__ __launch_bounds__(256) void desc_sample_kernel(const float* __restrict__ dmap, int Hc, int Wc, int H, int W,
                                                           const int32_t* __restrict__ n, const int32_t* __restrict__ kxy,
-                                                          int Kmax, float* __restrict__ desc, uint8_t* __restrict__ desc_bin) {
+                                                          int Kmax, float* __restrict__ desc, uint8_t* __restrict__ desc_bin,
+                                                          const int32_t* __restrict__ cell_row, const int32_t* __restrict__ row_base) {
     const int b = blockIdx.y;
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= Kmax) return;
@@ -963,21 +983,24 @@ __global__ __launch_bounds__(256) void desc_sample_kernel(const float* __restric
     uchar4* ob = desc_bin ? reinterpret_cast<uchar4*>(desc_bin + ((size_t)b * Kmax + k) * 256) + lane : nullptr;
     if (k >= n[b]) { *o = make_float4(0.f, 0.f, 0.f, 0.f); if (ob) *ob = make_uchar4(0, 0, 0, 0); return; }
     const int x = kxy[((size_t)b * Kmax + k) * 2], y = kxy[((size_t)b * Kmax + k) * 2 + 1];
-    const float gx = (((float)x - 3.5f) / ((float)W - 4.5f)) * 2.0f - 1.0f;
-    const float gy = (((float)y - 3.5f) / ((float)H - 4.5f)) * 2.0f - 1.0f;
-    const float ix = ((gx + 1.0f) * 0.5f) * (float)(Wc - 1);
-    const float iy = ((gy + 1.0f) * 0.5f) * (float)(Hc - 1);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+    const DescFoot f = desc_footprint(x, y, H, W, Hc, Wc);
+    const float ix = f.ix, iy = f.iy, fx0 = f.fx0, fy0 = f.fy0;
     const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.0f) - ix, wy0 = (fy0 + 1.0f) - iy;
     const float wnw = wx0 * wy0, wne = wx1 * wy0, wsw = wx0 * wy1, wse = wx1 * wy1;
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* mb = dmap + (size_t)b * Hc * Wc * 256;
-    const bool vx0 = x0 >= 0 && x0 < Wc, vx1 = x1 >= 0 && x1 < Wc, vy0 = y0 >= 0 && y0 < Hc, vy1 = y1 >= 0 && y1 < Hc;
-    const float4 nw = (vx0 && vy0) ? reinterpret_cast<const float4*>(mb + ((size_t)y0 * Wc + x0) * 256)[lane] : z;
-    const float4 ne = (vx1 && vy0) ? reinterpret_cast<const float4*>(mb + ((size_t)y0 * Wc + x1) * 256)[lane] : z;
-    const float4 sw = (vx0 && vy1) ? reinterpret_cast<const float4*>(mb + ((size_t)y1 * Wc + x0) * 256)[lane] : z;
-    const float4 se = (vx1 && vy1) ? reinterpret_cast<const float4*>(mb + ((size_t)y1 * Wc + x1) * 256)[lane] : z;
+    const float* mb = cell_row ? dmap + (size_t)row_base[b] * 256 : dmap + (size_t)b * Hc * Wc * 256;
+    const int32_t* cr = cell_row ? cell_row + (size_t)b * Hc * Wc : nullptr;
+    // a corner's 256 floats: the cell itself in the dense map, the cell's row in the sparse one (a row < 0 cannot happen, see above; it reads as zero)
+    auto corner = [&](bool valid, int yy, int xx) {
+        if (!valid) return z;
+        int r = yy * Wc + xx;
+        if (cr) { r = cr[r]; if (r < 0) return z; }
+        return reinterpret_cast<const float4*>(mb + (size_t)r * 256)[lane];
+    };
+    const float4 nw = corner(f.vx0 && f.vy0, f.y0, f.x0);
+    const float4 ne = corner(f.vx1 && f.vy0, f.y0, f.x1);
+    const float4 sw = corner(f.vx0 && f.vy1, f.y1, f.x0);
+    const float4 se = corner(f.vx1 && f.vy1, f.y1, f.x1);
     float4 v;
     v.x = fmaf(se.x, wse, fmaf(sw.x, wsw, fmaf(ne.x, wne, nw.x * wnw)));
     v.y = fmaf(se.y, wse, fmaf(sw.y, wsw, fmaf(ne.y, wne, nw.y * wnw)));
@@ -989,8 +1012,121 @@ __global__ __launch_bounds__(256) void desc_sample_kernel(const float* __restric
     if (ob) *ob = make_uchar4(v.x > 0.f, v.y > 0.f, v.z > 0.f, v.w > 0.f);
 }
 void launch_desc_sample(hipStream_t s, const float* dmap, int B, int Hc, int Wc, int H, int W, const int32_t* n,
-                        const int32_t* kxy, int Kmax, float* desc, uint8_t* desc_bin) {
-    hipLaunchKernelGGL(desc_sample_kernel, dim3((Kmax + 3) / 4, B), dim3(256), 0, s, dmap, Hc, Wc, H, W, n, kxy, Kmax, desc, desc_bin);
+                        const int32_t* kxy, int Kmax, float* desc, uint8_t* desc_bin, const int32_t* cell_row, const int32_t* row_base) {
+    hipLaunchKernelGGL(desc_sample_kernel, dim3((Kmax + 3) / 4, B), dim3(256), 0, s, dmap, Hc, Wc, H, W, n, kxy, Kmax, desc, desc_bin, cell_row, row_base);
+}
+
+// ---------------------------------------------------------------- sparse descriptor head (more than four frames per call; api_extract.hip: sp_desc_rows)
+// The descriptor map is only ever read at the <= 4 cells around each keypoint, so the head runs on those cells alone, as GEMM rows.
+// Cell list: one workgroup per frame.  (1) clear the frame's cell_row, (2) every keypoint k < n[b] marks its in-range corners (desc_footprint: the
+// sampling kernel's own arithmetic), (3) the marks are compacted in ASCENDING CELL ORDER by a block scan over 256 cells at a time -- no atomics, so
+// the row of a cell does not depend on the run.  cell_row [B, Hc * Wc] = row within the frame or -1, row_cell [B, cap] = cell of every live row, count [B].
+// cap >= min(4 Kmax, Hc Wc) bounds the rows of a frame.  desc_row_base_kernel then packs the frames' rows back to back: row_base [B + 1] = exclusive
+// prefix sums of count, row_base[B] the rows of the call (the GEMMs' m_valid).  Packed per frame instead ([B, cap] rows, batched GEMMs) the live tiles of
+// a frame are the first few of every 32 workgroup ids, which the round-robin dispatch piles onto half of the XCDs: convDa on rows 0.69 ms against 0.28 (profiles/sparse_desc_head.md).
+__global__ __launch_bounds__(256) void desc_cells_kernel(int Hc, int Wc, int H, int W, const int32_t* __restrict__ n, const int32_t* __restrict__ kxy, int Kmax,
+                                                         int cap, int32_t* __restrict__ cell_row, int32_t* __restrict__ row_cell, int32_t* __restrict__ count) {
+    __shared__ int wsum[4];
+    __shared__ int base_s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cells = Hc * Wc;
+    int32_t* cr = cell_row + (size_t)b * cells;
+    int32_t* rc = row_cell + (size_t)b * cap;
+    for (int c = tid; c < cells; c += 256) cr[c] = 0;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    int nk = n[b]; nk = nk < Kmax ? nk : Kmax;
+    for (int k = tid; k < nk; k += 256) {
+        const DescFoot f = desc_footprint(kxy[((size_t)b * Kmax + k) * 2], kxy[((size_t)b * Kmax + k) * 2 + 1], H, W, Hc, Wc);
+        if (f.vx0 && f.vy0) cr[f.y0 * Wc + f.x0] = 1;      // several keypoints may mark one cell: every writer stores the same word
+        if (f.vx1 && f.vy0) cr[f.y0 * Wc + f.x1] = 1;
+        if (f.vx0 && f.vy1) cr[f.y1 * Wc + f.x0] = 1;
+        if (f.vx1 && f.vy1) cr[f.y1 * Wc + f.x1] = 1;
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < cells; c0 += 256) {
+        const int c = c0 + tid;
+        const bool m = c < cells && cr[c] != 0;
+        const unsigned long long bal = __ballot(m);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base_s;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (c < cells) {
+            const int r = off + before;
+            const bool live = m && r < cap;                 // r < cap always (at most 4 marks per keypoint, at most Hc Wc cells); never write past the rows
+            cr[c] = live ? r : -1;
+            if (live) rc[r] = c;
+        }
+        __syncthreads();
+        if (tid == 0) base_s += total;
+    }
+    __syncthreads();
+    if (tid == 0) count[b] = base_s < cap ? base_s : cap;
+}
+__global__ __launch_bounds__(64) void desc_row_base_kernel(const int32_t* __restrict__ count, int B, int32_t* __restrict__ row_base) {
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int j0 = 0; j0 < B; j0 += 64) {       // one wave: 64 counts at a time, inclusive scan by shuffles
+        const int j = j0 + lane, v = j < B ? count[j] : 0;
+        int sum = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(sum, o); if (lane >= o) sum += t; }
+        if (j < B) row_base[j] = carry + sum - v;
+        carry += __shfl(sum, 63);
+    }
+    if (lane == 0) row_base[B] = carry;
+}
+void launch_desc_cells(hipStream_t s, int B, int Hc, int Wc, int H, int W, const int32_t* n, const int32_t* kxy, int Kmax, int cap, int32_t* cell_row,
+                       int32_t* row_cell, int32_t* count, int32_t* row_base) {
+    hipLaunchKernelGGL(desc_cells_kernel, dim3(B), dim3(256), 0, s, Hc, Wc, H, W, n, kxy, Kmax, cap, cell_row, row_cell, count);
+    hipLaunchKernelGGL(desc_row_base_kernel, dim3(1), dim3(64), 0, s, count, B, row_base);
+}
+
+// Row gather: patch [rows, 1152] = for every live row the 3 x 3 x 128 neighbourhood of its cell in f4 [B, Hc, Wc, 128], in the conv's reduction order
+// kappa = ci * 9 + ky * 3 + kx (the OIHW weight row), +0.0f for taps outside the map (the canonical arithmetic multiplies the padding, it does not skip it).
+// One thread per four consecutive kappa (one 16-byte store); the four loads of a thread hit at most two channels of up to four taps, a wave's 256 kappa
+// about 29 channels of the 9 tap pixels (nine 116-byte runs, L2 / L1 resident: f4 was just written).
+__global__ __launch_bounds__(256) void desc_gather_kernel(const float* __restrict__ f4, int Hc, int Wc, int cap, const int32_t* __restrict__ row_cell,
+                                                          const int32_t* __restrict__ count, const int32_t* __restrict__ row_base, float* __restrict__ patch) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;          // (row, quad) of frame b: 288 quads per row
+    const int r = t / 288, q = t - r * 288;
+    if (r >= count[b]) return;
+    const int cell = row_cell[(size_t)b * cap + r];
+    const int y = cell / Wc, x = cell - y * Wc;
+    const float* fb = f4 + (size_t)b * Hc * Wc * 128;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int kappa = q * 4 + e, ci = kappa / 9, tap = kappa - ci * 9, ky = tap / 3, kx = tap - ky * 3;
+        const int yy = y + ky - 1, xx = x + kx - 1;
+        v[e] = (yy >= 0 && yy < Hc && xx >= 0 && xx < Wc) ? fb[((size_t)yy * Wc + xx) * 128 + ci] : 0.0f;
+    }
+    *reinterpret_cast<float4*>(patch + ((size_t)row_base[b] + r) * 1152 + q * 4) = make_float4(v[0], v[1], v[2], v[3]);
+}
+void launch_desc_gather(hipStream_t s, const float* f4, int B, int Hc, int Wc, int cap, const int32_t* row_cell, const int32_t* count, const int32_t* row_base,
+                        float* patch) {
+    hipLaunchKernelGGL(desc_gather_kernel, dim3((unsigned)(((long long)cap * 288 + 255) / 256), B), dim3(256), 0, s, f4, Hc, Wc, cap, row_cell, count, row_base,
+                       patch);
+}
+
+// descmap_norm_kernel's arithmetic on the live rows of every frame (count [B], row_base [B] on the device)
+__global__ __launch_bounds__(256) void descrows_norm_kernel(float* __restrict__ rows, const int32_t* __restrict__ count, const int32_t* __restrict__ row_base) {
+    const int b = blockIdx.y;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= count[b]) return;
+    const int lane = threadIdx.x & 63;
+    float4* p = reinterpret_cast<float4*>(rows + ((size_t)row_base[b] + r) * 256) + lane;
+    float4 v = *p;
+    const float d = fmaxf(sqrtf(wave_sumsq256(v)), 1e-12f);
+    v.x = v.x / d; v.y = v.y / d; v.z = v.z / d; v.w = v.w / d;
+    *p = v;
+}
+void launch_descrows_norm(hipStream_t s, float* rows, int B, int cap, const int32_t* count, const int32_t* row_base) {
+    hipLaunchKernelGGL(descrows_norm_kernel, dim3((cap + 3) / 4, B), dim3(256), 0, s, rows, count, row_base);
 }
 
 }  // namespace rfe
