@@ -551,6 +551,12 @@ int rfe_k_lightglue_ffn(rfe_ctx* ctx, int layer, int cross, const float* x_dev, 
  * the forward's launcher, so nseq * Lq and RFE_OPT_LG_FP16X2 select the kernel exactly as inside a match call. */
 int rfe_k_attention(rfe_ctx* ctx, const float* q_dev, const float* k_dev, const float* v_dev, int ld, float* out_dev, int nseq, int Lq, int Lk,
                     const int32_t* qlen_dev, const int32_t* klen_dev, const int32_t* kv_map_dev, const float* rope_dev);
+/* Both directions of one LightGlue cross block, through the forward's own code: qk_v_dev [2*P*L, ld] rows [qk (256) | v (256) | ...] in the side-major
+ * layout (sequence p < P is side 0 of pair p and attends to sequence p + P, and back), lens_dev [2*P] valid rows, out_dev [2*P*L, 256]; ld >= 512,
+ * ld % 4 == 0, L % 4 == 0, 4 <= L <= 4096.  form 0: the form a match call would choose at (P, L); 1: the shared-logit form (side 0 writes each pair's
+ * logits out, side 1 reads them back) at any shape; 2: the generic form (every direction forms its own logits).  The LightGlue workspace, logit scratch included, is filled
+ * with NaN before the launches.  A ctx is enough, no weights. */
+int rfe_k_cross_attention(rfe_ctx* ctx, const float* qk_v_dev, int ld, float* out_dev, int P, int L, const int32_t* lens_dev, int form);
 /* Projection + attention of one self block with the loaded weights, through the forward's own code: x_dev [nseq*L, 256] token rows, csn_dev [nseq*L, 32]
  * (cos, sin) rotary pairs, lens_dev [nseq] valid rows; qkv_out_dev [nseq*L, 768] = [q | k | v] as the attention reads them, ctx_out_dev [nseq*L, 256]
  * (either may be NULL).  nseq * L selects the path as inside a match call: throughput shapes rotate q | k in the projection's epilogue (gemm.hip) and run

@@ -28,7 +28,7 @@ EXPORTS = [
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
-    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert",
+    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_cross_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -163,6 +163,7 @@ lib.rfe_k_lightglue_self_attention.argtypes = [C.c_void_p, C.c_int, _fp, _fp, C.
 lib.rfe_k_lightglue_assign.argtypes = [C.c_void_p, _fp, _fp, _fp, _fp, _ip, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int32,
                                        _fp, _fp, _fp, _fp, _ip, _ip, _ip, _ip, _fp, _fp]
 lib.rfe_k_attention.argtypes = [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _fp]
+lib.rfe_k_cross_attention.argtypes = [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int, _ip, C.c_int]
 
 
 POOL_AUTO, POOL_RCCL, POOL_COPY = 0, 1, 2

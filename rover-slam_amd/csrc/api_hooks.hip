@@ -169,6 +169,31 @@ extern "C" int rfe_k_attention(rfe_ctx* c, const float* q, const float* k, const
     return RFE_OK;
 }
 
+// Both directions of one cross block, through the forward's own lg_cross_attention, on caller-provided [qk | v] rows in the side-major layout.  form 0: what
+// the forward would choose at (P, L); 1: the shared-logit form at any shape; 2: the generic form.  The whole LightGlue workspace, the logit scratch included, is filled
+// with 0xFFFFFFFF words (NaN) before the launches: nothing but what a call writes itself may reach its result.
+extern "C" int rfe_k_cross_attention(rfe_ctx* c, const float* qk_v, int ld, float* out, int P, int L, const int32_t* lens, int form) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!qk_v || !out || !lens || P <= 0 || L < 4 || L > 4096 || (L % 4) || ld < 512 || (ld % 4) || form < 0 || form > 2)
+        return fail(c, RFE_ERR_INVALID, "k_cross_attention: null pointer, P <= 0, L not a multiple of 4 in [4, 4096], ld < 512 or not a multiple of 4, or form outside 0..2");
+    RFE_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> hl((size_t)2 * P), map((size_t)2 * P);   // the kernels trust the lengths (lg_stage clamps them for the forward)
+    RFE_HIP(c, hipMemcpy(hl.data(), lens, hl.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : hl) if (v < 0 || v > L) return fail(c, RFE_ERR_INVALID, "k_cross_attention: a length outside [0, L]");
+    for (int i = 0; i < 2 * P; ++i) map[i] = i < P ? i + P : i - P;
+    LgBuffers b;
+    int rc = lg_carve_as(c, P, L, b, form == 1 || (form == 0 && lg_cross_shared(c, P, L)), [](Bump&) {});
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    RFE_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->ws_lg, -1, c->ws_lg_bytes / 4, s));   // the whole LightGlue workspace, the logit scratch included
+    RFE_HIP(c, hipMemcpyAsync(b.lens, lens, (size_t)2 * P * 4, hipMemcpyDeviceToDevice, s));
+    RFE_HIP(c, hipMemcpyAsync(b.kvmap, map.data(), (size_t)2 * P * 4, hipMemcpyHostToDevice, s));
+    lg_cross_attention(c, b, qk_v, ld, out, P, L);
+    RFE_HIP(c, hipGetLastError());
+    RFE_HIP(c, hipStreamSynchronize(s));
+    return RFE_OK;
+}
+
 extern "C" int rfe_k_set_lightglue_tap(rfe_ctx* c, int pair, float* x0, float* x1, float* scores) {
     if (!c) return RFE_ERR_INVALID;
     if (pair < 0) { c->tap.armed = false; return RFE_OK; }

@@ -166,18 +166,24 @@ int pyr_forward(rfe_ctx* c, const uint8_t* img, int H, int W, int stride, int B,
 // ---------------------------------------------------------------- LightGlue pipeline (api_match.hip)
 struct LgBuffers {
     float *x, *kn, *csn, *lnstat, *qkv, *ctx, *msg, *h, *md, *z, *sim, *rowlse, *collse, *mx0, *apart;
+    float* slog;   // cross blocks' shared logits (lg_cross_slog_floats), or null: the generic form.  sim is its first quarter (dead until the assignment)
     int32_t *a0, *a1, *lens, *kvmap;
 };
-void lg_layout(Bump& a, int P, int L, LgBuffers& b);             // ws_lg
-inline size_t lg_ws_bytes(int P, int L) { LgBuffers b; return layout_bytes([&](Bump& a) { lg_layout(a, P, L, b); }); }
+// whether a forward on P pairs of L runs its cross blocks in the shared-logit form -- and therefore whether the workspace holds slog
+inline bool lg_cross_shared(const rfe_ctx* c, int P, int L) { return !c->opt_lg_fp16x2 && lg_cross_shared_ok(P, L); }
+void lg_layout(Bump& a, int P, int L, LgBuffers& b, bool shared);             // ws_lg
+inline size_t lg_ws_bytes(const rfe_ctx* c, int P, int L) { LgBuffers b; return layout_bytes([&](Bump& a) { lg_layout(a, P, L, b, lg_cross_shared(c, P, L)); }); }
 // grows ws_lg and carves it: the fixed buffers, then whatever `extra` takes from the same Bump (a caller's own scratch)
-template <typename X> int lg_carve(rfe_ctx* c, int P, int L, LgBuffers& b, X&& extra) {
-    return ws_carve(c, &c->ws_lg, &c->ws_lg_bytes, [&](Bump& a) { lg_layout(a, P, L, b); extra(a); });
+template <typename X> int lg_carve_as(rfe_ctx* c, int P, int L, LgBuffers& b, bool shared, X&& extra) {
+    return ws_carve(c, &c->ws_lg, &c->ws_lg_bytes, [&](Bump& a) { lg_layout(a, P, L, b, shared); extra(a); });
 }
+template <typename X> int lg_carve(rfe_ctx* c, int P, int L, LgBuffers& b, X&& extra) { return lg_carve_as(c, P, L, b, lg_cross_shared(c, P, L), extra); }
 inline int lg_carve(rfe_ctx* c, int P, int L, LgBuffers& b) { return lg_carve(c, P, L, b, [](Bump&) {}); }
 int lg_check(rfe_ctx* c, int P, int Mmax, int Nmax);
 void lg_ffn(rfe_ctx* c, LgBuffers& b, float* x, const float* second, int rows, const float* w1, const float* b1, const float* g,
             const float* be, const float* w2, const float* b2);
+// both directions of a cross block on [qk | v] rows of stride ld in the side-major layout -> out [2 P L, 256]: the shared-logit form when b.slog was carved
+void lg_cross_attention(rfe_ctx* c, LgBuffers& b, const float* qk_v, int ld, float* out, int P, int L);
 bool lg_self_qkv_attention(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, const float* x, const float* csn, const int32_t* lens, int nseq, int L);
 void lg_self_block(rfe_ctx* c, LgBuffers& b, const LgLayerDev& Lw, float* x, const float* csn, const int32_t* lens, int nseq, int L);
 int lg_forward(rfe_ctx* c, LgBuffers& b, int P, int L, float thr, int cap, int32_t* S, int32_t* pairs, float* ms,

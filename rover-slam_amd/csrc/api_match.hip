@@ -29,13 +29,14 @@ GemmArgs gemm_lgw(const rfe_ctx* c, const float* A, int lda, const float* Bw, in
     return g;
 }
 
-void lg_layout(Bump& a, int P, int L, LgBuffers& b) {
+void lg_layout(Bump& a, int P, int L, LgBuffers& b, bool shared) {
     const size_t rows = (size_t)2 * P * L;
     b.x = a.take<float>(rows * 256); b.ctx = a.take<float>(rows * 256); b.msg = a.take<float>(rows * 256);
     b.md = a.take<float>(rows * 256);
     b.kn = a.take<float>(rows * 2); b.csn = a.take<float>(rows * 64); b.lnstat = a.take<float>(rows * 32);   // <= 16 partial pairs per row
     b.qkv = a.take<float>(rows * 768); b.h = a.take<float>(rows * 512); b.z = a.take<float>(rows);
-    b.sim = a.take<float>((size_t)P * L * L);
+    b.slog = shared ? a.take<float>(lg_cross_slog_floats(P, L)) : nullptr;
+    b.sim = shared ? b.slog : a.take<float>((size_t)P * L * L);
     b.rowlse = a.take<float>((size_t)P * L); b.collse = a.take<float>((size_t)P * L); b.mx0 = a.take<float>((size_t)P * L);
     b.a0 = a.take<int32_t>((size_t)P * L); b.a1 = a.take<int32_t>((size_t)P * L);
     b.lens = a.take<int32_t>((size_t)2 * P); b.kvmap = a.take<int32_t>((size_t)2 * P);
@@ -46,6 +47,11 @@ void lg_layout(Bump& a, int P, int L, LgBuffers& b) {
 // block) may use it whenever its own requirement fits
 static float* lg_part(const LgBuffers& b, int nseq, int L) { return (b.apart && lg_attention_part_bytes(nseq, L) > 0) ? b.apart : nullptr; }
 
+
+void lg_cross_attention(rfe_ctx* c, LgBuffers& b, const float* qk_v, int ld, float* out, int P, int L) {
+    if (b.slog) launch_lg_cross_shared(c->stream, qk_v, ld, out, P, L, b.lens, b.slog);
+    else launch_lg_attention(c->stream, qk_v, qk_v, qk_v + 256, ld, out, 2 * P, L, L, b.lens, b.lens, b.kvmap, lg_part(b, 2 * P, L), nullptr, c->opt_lg_fp16x2);
+}
 
 // x + ffn([x | msg]) in place on x
 void lg_ffn(rfe_ctx* c, LgBuffers& b, float* x, const float* second, int rows, const float* w1, const float* b1, const float* g,
@@ -137,7 +143,7 @@ int lg_forward(rfe_ctx* c, LgBuffers& b, int P, int L, float thr, int cap, int32
         if (l > 0 || !first_self_done) lg_self_block(c, b, Lw, b.x, b.csn, b.lens, nseq, L);
         // ---- cross block
         { ProfScope p(c, "lg_cross_qkv"); launch_gemm_nt(s, gemm_lgw(c, b.x, 256, Lw.cwqkv, 256, Lw.cbqkv, b.qkv, 512, rows, 512, 256)); }
-        { ProfScope p(c, "lg_attention"); launch_lg_attention(s, b.qkv, b.qkv, b.qkv + 256, 512, b.ctx, nseq, L, L, b.lens, b.lens, b.kvmap, lg_part(b, nseq, L), nullptr, c->opt_lg_fp16x2); }
+        { ProfScope p(c, "lg_attention"); lg_cross_attention(c, b, b.qkv, 512, b.ctx, P, L); }
         if (c->opt_lg_fold) {
             lg_ffn(c, b, b.x, b.ctx, rows, Lw.cw1f, Lw.cb1f, Lw.clng, Lw.clnb, Lw.cw2, Lw.cb2);
         } else {
@@ -264,7 +270,7 @@ extern "C" int rfe_match(rfe_ctx* c, const float* k0n, const float* k1n, const f
     io.out(dS, S, P); io.out(dp, pairs, P * cap * 2); io.out(dms, ms, P * cap);
     if ((rc = io.upload())) return rc;
     const int L = ((std::max(Mmax, Nmax) + 3) / 4) * 4;
-    if ((rc = ensure_ws(c, &c->ws_lg, &c->ws_lg_bytes, lg_ws_bytes(P, L)))) return rc;   // before the key is formed: a capture must not allocate
+    if ((rc = ensure_ws(c, &c->ws_lg, &c->ws_lg_bytes, lg_ws_bytes(c, P, L)))) return rc;   // before the key is formed: a capture must not allocate
     int thr_bits; memcpy(&thr_bits, &thr, 4);
     if ((rc = run_host_graph(c, c->g_match, host_graph_key(c, "m", {P, Mmax, Nmax, thr_bits}),
                              [&] { return rfe_match_dev(c, dk0, dk1, dd0, dd1, dm, dn, P, Mmax, Nmax, thr, dS, dp, dms); }))) return rc;

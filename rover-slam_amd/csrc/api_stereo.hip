@@ -293,7 +293,7 @@ extern "C" int rfe_stereo_frame_pyramid_dev(rfe_ctx* c, const uint8_t* imgL, con
     // every allocation before the first kernel of the call (ensure_ws synchronises the ctx stream only; the side stream is idle between calls)
     StState st;
     if ((rc = st_carve(c, K, st))) return rc;
-    if ((rc = ensure_ws(c, &c->ws_lg, &c->ws_lg_bytes, lg_ws_bytes(1, ((K + 3) / 4) * 4)))) return rc;
+    if ((rc = ensure_ws(c, &c->ws_lg, &c->ws_lg_bytes, lg_ws_bytes(c, 1, ((K + 3) / 4) * 4)))) return rc;
     if ((rc = pyr_prepare(c, H, W, 2, scale_factor, P, true))) return rc;
     if (fresh || reset) { c->st_have_prev = false; c->st_H = H; c->st_W = W; c->st_K = K; c->st_pyr_key = key; }
     // both views as one batch of 2, read where the caller has them (frame distance imgR - imgL); every level image, level 0 included, is

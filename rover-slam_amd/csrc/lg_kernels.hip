@@ -247,11 +247,21 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 4) void lg_attention_kernel(   // 
 // therefore multiplies k = 8 g + e and 8 g + 4 + e: the sum over the head dimension runs in a permuted order (tolerance-checked
 // like every LightGlue kernel), Q is loaded in that order with eight float4 loads.  V image: plain [key][64].  Keys past the
 // sequence length are read from the last valid row (finite) and masked in S.
+// SLOG (cross blocks, shared-logit form: launch_lg_cross_shared below): the nseq_total sequences are side 0 of as many pairs and attend to sequence
+// seq + nseq_total (the forward's side-major layout, no kv_map); next to its normal work the kernel leaves every live logit of S^T behind in
+// slog[((pair * 4 + head) * Lk + key) * (Lq + SLOG_PAD) + query] -- absolute, in the scaled base-2 domain -- for lg_cross_slog_kernel, which runs the other direction
+// of the pair on the same matrix without forming it again.  Per 32-key tile: 16 additions (the accumulator holds S relative to the reference) and 16
+// dword stores per lane, a half-wave's 32 queries = one 128-byte line per key; the addresses are a wave-uniform row base plus a loop-invariant lane offset.
 constexpr int AD_K = 32;
+// Rows of a logit image are SLOG_PAD floats longer than Lq.  At Lq = 1024 an unpadded row is 4 KB, and the 16 rows a wave stores per tile here -- and
+// the 32 rows a wave's load instruction touches in lg_cross_slog_kernel -- would all start at the same offset modulo 4 KB, i.e. on the same memory
+// channels; 256 B more per row walk them through the channels (side 1: 181 -> 157 us per launch in the bench step, profiles/cross_shared_logits.md).
+constexpr int SLOG_PAD = 64;
+template <bool SLOG = false>
 __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld, float* __restrict__ out,
     int Lq, int Lk, int nqb, const int* __restrict__ qlen, const int* __restrict__ klen, const int* __restrict__ kv_map,
-    int prio, int nseq_total) {
+    int prio, int nseq_total, float* __restrict__ slog) {
     // Dynamic LDS on purpose: with static `__shared__ float Kd[2][..]` tiles the compiler's wait-count pass cannot tell buffer buf from
     // buf ^ 1 and puts an s_waitcnt vmcnt(0) in front of the first ds_read of tile t -- i.e. AFTER tile t + 1 has just been requested, so
     // every wave sat out that round trip and nothing overlapped (round-3 advisor finding, visible in the ISA).  With one dynamic array and
@@ -263,7 +273,7 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     const int qb = blk.inner, unit = blk.unit;
     if (unit >= 4 * nseq_total) return;
     const int seq = unit >> 2, head = unit & 3;
-    const int kvseq = kv_map ? kv_map[seq] : seq;
+    const int kvseq = SLOG ? seq + nseq_total : kv_map ? kv_map[seq] : seq;
     const int nq = qlen ? qlen[seq] : Lq;
     const int nk = klen ? klen[kvseq] : Lk;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -313,6 +323,11 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
     if (nk > 0) issue(0, 0);
     int buf = 0;
     const int jsw = j & 15;
+    // SLOG: the buffer resource is this (pair, head)'s logit image; the scalar offset of a store selects the row `key` (wave-uniform), the lane's own
+    // offset adds its half-wave's 4 rows and its query
+    // (a buffer store: resource = the image, scalar offset = the row, vector offset = the lane's -- no address arithmetic on the VALU)
+    __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(SLOG ? slog + (size_t)unit * Lk * (Lq + SLOG_PAD) : nullptr, 0, SLOG ? Lk * (Lq + SLOG_PAD) * 4 : 0, 0x00027000);
+    const int slane = (4 * h * (Lq + SLOG_PAD) + qrow) * 4;
     for (int k0 = 0; k0 < nk; k0 += AD_K) {
         // tile k0 has landed (this wave's copies: the wait; everybody's: the barrier) and the other buffer is no longer read
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -333,6 +348,20 @@ __global__ __launch_bounds__(256, 4) void lg_attention_dma_kernel(
             for (int e = 0; e < 4; ++e) st = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], qreg[4 * g + e], st, 0, 0, 0);
         }
         if (prio) __builtin_amdgcn_s_setprio(0);
+        if constexpr (SLOG) {
+            if (qrow < nq) {   // only the live nq x nk block is written (and read back)
+                const float ref = first ? 0.f : m_run;
+                if (k0 + AD_K <= nk) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(st[r] + ref), srsrc, slane, (k0 + (r & 3) + 8 * (r >> 2)) * (Lq + SLOG_PAD) * 4, 0);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (k0 + (r & 3) + 8 * (r >> 2) + 4 * h < nk)
+                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(st[r] + ref), srsrc, slane, (k0 + (r & 3) + 8 * (r >> 2)) * (Lq + SLOG_PAD) * 4, 0);
+                }
+            }
+        }
         if (k0 + AD_K > nk) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -435,11 +464,120 @@ void launch_lg_attention(hipStream_t s, const float* q, const float* k, const fl
     }
     // throughput shapes: K / V tiles by LDS-DMA when q | k arrive rotated (self blocks behind the rotary epilogue, cross blocks); rotary on load otherwise
     if (!rope && (ld % 4) == 0)
-        hipLaunchKernelGGL(lg_attention_dma_kernel, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nseq);
+        hipLaunchKernelGGL(lg_attention_dma_kernel<false>, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nseq, nullptr);
     else if (rope)
         hipLaunchKernelGGL((lg_attention_kernel<false, true>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nullptr, nseq, rope_csn);
     else
         hipLaunchKernelGGL((lg_attention_kernel<false, false>), dim3(nqb * units8), dim3(256), 0, s, q, k, v, ld, out, Lq, Lk, nqb, qlen, klen, kv_map, AT_PRIO, nullptr, nseq, rope_csn);
+}
+
+// ---- cross blocks, shared-logit form.  LightGlue's cross blocks share ONE projection for queries and keys, so for pair p and head h both directions
+// attend through the same matrix S = qk0 . qk1^T: side 0 takes the softmax over its rows and multiplies by v1, side 1 over its columns and multiplies by
+// v0.  The generic launch over 2P sequences forms every element of S twice.  Here lg_attention_dma_kernel<true> runs side 0 and writes S out (slog, see
+// there), and this kernel runs side 1 from it: workgroup = 128 queries j of side 1, wave = 32, lane (j, hh) owns a query and per 32-key tile of side 0
+// loads ITS row of the image -- register r = key (r & 3) + 8 (r >> 2) + 4 hh, the S^T accumulator layout, as four 16-byte loads (the two half-waves
+// together consume whole 128-byte lines) -- one tile ahead, into registers.  No K tile, no Q fragment, no S product: the softmax step and the 32 PV
+// matrix instructions of the generic kernel on V tiles copied by LDS-DMA (2 x 8 KB).  Keys at or past lens[p] are masked by a select (the image is not
+// initialised outside the live block; a tile's loads may run up to 28 floats past a row's end, which lg_cross_slog_floats pads for); query lanes past
+// lens[p + P] read the last live row.  Without Q the kernel takes 96 VGPRs: 5 workgroups per CU cover the load latency (a bound of 6 spills 14 registers and
+// measured no faster).  The (pair, head) units are walked in the REVERSE of the order the side-0 kernel wrote them in, so that the most recently written
+// logits are the first ones read; the same order measured the same (profiles/cross_shared_logits.md, with the crossover and the HBM bytes).
+size_t lg_cross_slog_floats(int P, int L) { return (size_t)4 * P * L * (L + SLOG_PAD) + 64; }
+constexpr size_t CROSS_SLOG_CAP_BYTES = (size_t)4 << 30;   // of logits (16 P L^2, row padding not counted); above this the workspace growth is not worth it: the generic form
+constexpr int CROSS_SHARED_MIN_PAIRS = 8;   // L = 1024: 147 against 156 us at 8 pairs, 265 / 302 at 16, 536 / 595 at 32; 4 pairs belong to the latency kernel
+// (the crossover was measured at L = 1024 only; calls of many short sequences, e.g. 100 pairs of 128, pass the same test unmeasured, and a call just past
+// the cap -- more than 256 pairs of 1024 -- steps back to the generic form's time)
+bool lg_cross_shared_ok(int P, int L) {
+    return P >= CROSS_SHARED_MIN_PAIRS && (L % 4) == 0 && (size_t)2 * P * L > AT_SPLIT_MAX_ROWS && (size_t)16 * P * L * L <= CROSS_SLOG_CAP_BYTES;
+}
+__global__ __launch_bounds__(256, 5) void lg_cross_slog_kernel(const float* __restrict__ slog, const float* __restrict__ v, int ld, float* __restrict__ out,
+                                                               int L, int nqb, const int* __restrict__ lens, int P, int prio) {
+    extern __shared__ __attribute__((aligned(16))) float ad_lds[];   // dynamic for the reason given in lg_attention_dma_kernel
+    float (*Vd)[AD_K * 64] = reinterpret_cast<float (*)[AD_K * 64]>(ad_lds);
+    const XcdBlock blk = xcd_decode(blockIdx.x, nqb);
+    const int qb = blk.inner;
+    if (blk.unit >= 4 * P) return;
+    const int unit = 4 * P - 1 - blk.unit;
+    const int p = unit >> 2, head = unit & 3, seq = p + P;
+    const int nq = lens[seq], nk = lens[p];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (qb * AT_Q >= nq) {
+        for (int e = tid; e < AT_Q * 64; e += 256) {
+            const int row = qb * AT_Q + (e >> 6);
+            if (row < L) out[((size_t)seq * L + row) * 256 + head * 64 + (e & 63)] = 0.f;
+        }
+        return;
+    }
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int qrow = qb * AT_Q + wave * 32 + j;
+    const f32x4* lp = reinterpret_cast<const f32x4*>(slog + ((size_t)unit * L + (qrow < nq ? qrow : nq - 1)) * (L + SLOG_PAD) + 4 * h);
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m_run = -INFINITY, l_run = 0.f;
+    const float* vbase = v + (size_t)p * L * ld + head * 64;
+    const int crow = lane >> 4, cslot = lane & 15;
+    f32x4 nx[4];
+    auto issue = [&](int k0, int buf) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            int key = k0 + wave * 8 + u * 4 + crow; key = key < nk ? key : nk - 1;
+            lds_dma16(vbase + (size_t)key * ld + (cslot << 2), Vd[buf] + (wave * 8 + u * 4) * 64);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) nx[g] = lp[(k0 >> 2) + 2 * g];
+    };
+    if (nk > 0) issue(0, 0);
+    int buf = 0;
+    for (int k0 = 0; k0 < nk; k0 += AD_K) {
+        // tile k0 has landed -- the V copies and this lane's logits (this wave's: the wait; everybody's: the barrier) -- and the other buffer is no longer read
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const bool first = k0 == 0;
+        f32x16 st;
+        {
+            const float ref = first ? 0.f : m_run;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[r] = nx[r >> 2][r & 3] - ref;
+        }
+        if (k0 + AD_K < nk) issue(k0 + AD_K, buf ^ 1);
+        if (k0 + AD_K > nk) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                st[r] = key < nk ? st[r] : -INFINITY;
+            }
+        }
+        softmax_step<SOFTMAX_DEFER_F32>(st, first, m_run, l_run, o0, o1);
+        const float* va = Vd[buf] + (4 * h) * 64 + j;
+        if (prio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kr = (r & 3) + 8 * (r >> 2);
+            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(va[kr * 64], st[r], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(va[kr * 64 + 32], st[r], o1, 0, 0, 0);
+        }
+        if (prio) __builtin_amdgcn_s_setprio(0);
+        buf ^= 1;
+    }
+    l_run = softmax_finish(l_run);
+    if (qrow < L) {
+        const float inv = (qrow < nq && l_run > 0.f) ? 1.0f / l_run : 0.f;
+        float* op = out + ((size_t)seq * L + qrow) * 256 + head * 64;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int d = (r & 3) + 8 * (r >> 2) + 4 * h;
+            op[d] = o0[r] * inv;
+            op[d + 32] = o1[r] * inv;
+        }
+    }
+}
+// both directions of a cross block on [qk | v] rows (row stride ld, ld % 4 == 0) in the side-major layout: out [2 P L, 256], lens [2 P], slog lg_cross_slog_floats(P, L)
+void launch_lg_cross_shared(hipStream_t s, const float* qk_v, int ld, float* out, int P, int L, const int* lens, float* slog) {
+    const int nqb = (L + AT_Q - 1) / AT_Q, units8 = xcd_padded(4 * P);
+    hipLaunchKernelGGL(lg_attention_dma_kernel<true>, dim3(nqb * units8), dim3(256), 4 * AD_K * 64 * sizeof(float), s, qk_v, qk_v, qk_v + 256, ld, out, L, L, nqb,
+                       lens, lens, nullptr, AT_PRIO, P, slog);
+    hipLaunchKernelGGL(lg_cross_slog_kernel, dim3(nqb * units8), dim3(256), 2 * AD_K * 64 * sizeof(float), s, slog, qk_v + 256, ld, out, L, nqb, lens, P, AT_PRIO);
 }
 
 // ---------------------------------------------------------------- LayerNorm(512) + GELU(erf), in place

@@ -257,6 +257,11 @@ void launch_lg_attention(hipStream_t s, const float* q, const float* k, const fl
 void launch_lg_attention_h2(hipStream_t s, const float* q, const float* k, const float* v, int ld, float* out, int nseq, int Lq, int Lk,
                             const int* qlen, const int* klen, const int* kv_map, const float* rope_csn);   // lg_attention_h2.hip
 size_t lg_attention_part_bytes(int nseq, int Lq);
+// cross blocks, shared-logit form (lg_kernels.hip): side 0 writes each pair's logits to slog while it runs, side 1 reads them back instead of forming them again
+bool lg_cross_shared_ok(int P, int L);        // the default fp32 path takes the form at this shape (throughput shapes from the measured crossover up, slog under its cap)
+size_t lg_cross_slog_floats(int P, int L);    // 4 P L^2 logits + the padding a tile's loads may run into
+void launch_lg_cross_shared(hipStream_t s, const float* qk_v, int ld /*row stride of the [qk | v] rows, % 4 == 0*/, float* out /*[2 P L, 256]*/, int P, int L,
+                            const int* lens /*[2 P], side-major*/, float* slog);
 void launch_lg_ln_gelu(hipStream_t s, float* h, const float* g, const float* b, int64_t rows);
 void launch_lg_assign(hipStream_t s, const float* sim, const float* z0, const float* z1, int P, int L,
                       int cap, const int* m, const int* n, float thr, float* scores_opt, float* rowlse,
