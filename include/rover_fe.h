@@ -468,6 +468,74 @@ int rfe_search_by_projection_sim3(rfe_ctx* ctx, const rfe_sim3_params* params, c
                                   int32_t* matched, int32_t* best_idx, float* best_dist, float* second_dist, float* proj, float* radius,
                                   int32_t* level, int32_t* reject, int32_t* stats);
 
+/* ---- steps 2 and 3 of Tracking::SearchLocalPoints as one call ----
+ * Frame::isInFrustum(pMP, 0.5) for every local map point (src/Tracking.cc:4124-4147, src/Frame.cc:711-794, one pinhole camera) and
+ * SPmatcher::SearchByProjection1 over the points that passed (src/Matchers/SPmatcher.cc:1178-1283): the front (transform, projection, the
+ * gates, MapPoint::PredictScale, RadiusByViewingCos, the far-point gate) in one kernel, then the grid, candidate lists, scan and sequential
+ * assignment of rfe_search_by_projection, unchanged.  All arithmetic is fp32 in this order, one rounding per operation, no contraction:
+ *   x = ((r00 px + r01 py) + r02 pz) + tx (y, z alike; rcw row-major), depth = sqrtf((x x + y y) + z z), invz = 1 / z;
+ *   u = (fx x) / z + cx, v = (fy y) / z + cy; PO = P - ow, dist = sqrtf((POx POx + POy POy) + POz POz);
+ *   viewCos = ((POx nx + POy ny) + POz nz) / dist; predicted level = ceilf(logf(scale_dist / dist) / log_scale_factor) clamped as a float to
+ *   0..nlevels-1 (NaN = 0); radius = ((viewCos > 0.998 (the double literal) ? 2.5f : 4.0f) * th) * scale_factors[L].
+ * reject [Np], the first gate that failed: 1 = invalid, 2 = z < 0 (z == +-0 passes), 3 = u < min_x || u > max_x || v < min_y || v > max_y
+ *   (closed: u == max_x passes; a NaN u or v passes too, as in the reference, and is searched with an empty candidate list), 4 = dist <
+ *   min_dist || dist > max_dist, 5 = viewCos < view_cos_limit, 6 = in the frustum but far_points && depth > th_far (not searched),
+ *   0 = searched.
+ *   rfe_frustum_params: rcw = mRcw (row-major), tcw = mtcw, ow = mOw; fx, fy, cx, cy, mbf; the frame's mnMinX, mnMinY, mnMaxX, mnMaxY;
+ *   view_cos_limit (0.5 in SearchLocalPoints); th (a float in SearchByProjection1); far_points / th_far = bFarPoints / thFarPoints;
+ *   nlevels = mnScaleLevels (1..RFE_MAX_LEVELS), log_scale_factor = mfLogScaleFactor, scale_factors = mvScaleFactors; level_mode:
+ *   RFE_LEVEL_ZERO (the reference as written, :1193 nPredictedLevel = 0: L = 0 and the octave gate of the search is that of level 0) or
+ *   RFE_LEVEL_PREDICTED (ORB-SLAM3's form: L = the predicted level, which is also the pred_level of the search).
+ *   q [Np,256], pw [Np,3] GetWorldPos, normal [Np,3] GetNormal, min_dist / max_dist [Np] Get{Min,Max}DistanceInvariance, scale_dist [Np] the
+ *   bare mfMaxDistance (as rfe_search_by_projection_sim3), valid [Np] or NULL = all 1 (mnLastFrameSeen != F.mnId && !isBad()), observed [Np]
+ *   or NULL = all 1; f, kpts / kxy (exactly one), octave, skip, Nf, nf_dev, th_high, cand_cap, assign, best_idx, best_dist, second_dist and
+ *   stats[0..3] exactly as rfe_search_by_projection[_dev].
+ *   What isInFrustum leaves in the map point, per reject code (each array may be NULL):
+ *     proj [Np,2] = (mTrackProjX, mTrackProjY): (0, 0) for 1, (-1, -1) for 2 and 3, (u, v) for 4, 5, 6 and 0;
+ *     proj_xr [Np] = u - mbf * invz, depth [Np] = mTrackDepth, view_cos [Np]: for 0 and 6, else 0;
+ *     level [Np] = mnTrackScaleLevel, the PREDICTED level in both level modes: for 0 and 6, else -1.
+ *   stats [8]: 0..3 as rfe_search_by_projection, 4 = points in the frustum (codes 0 and 6: the reference's nToMatch, the IncreaseVisible
+ *   calls), 5 = points searched (code 0), 6..7 = 0.
+ * The _dev form takes DEVICE pointers and is asynchronous on the ctx stream (no host synchronisation, no host read of device data once
+ * the workspace has its size; cand_cap and overflow as rfe_search_by_projection_dev -- the front's outputs and stats[4..5] do not depend
+ * on the slots; stats is required).  The host form sizes the slots itself and returns stats[0] >= 0.
+ * Refused (RFE_ERR_INVALID): Np outside 0..16384; Nf outside 0..4096; empty bounds; nlevels outside 1..RFE_MAX_LEVELS; log_scale_factor
+ *   <= 0 when nlevels > 1; an unknown level_mode; cand_cap < 0; both or neither of kpts / kxy; a NULL required pointer; host form only: a
+ *   non-finite pose, intrinsic, bound, th, th_high, view_cos_limit, th_far, scale factor, log_scale_factor or keypoint.  The per-point
+ *   arrays are not checked in either form.
+ * Out of scope: two-camera frames (Nleft != -1: isInFrustumChecks and the right-camera branch) and KannalaBrandt8 -- the caller keeps the
+ * reference's loops. */
+#define RFE_LEVEL_ZERO 0
+#define RFE_LEVEL_PREDICTED 1
+typedef struct rfe_frustum_params {
+    float rcw[9];                  /* row-major */
+    float tcw[3];
+    float ow[3];
+    float fx, fy, cx, cy, mbf;
+    float min_x, min_y, max_x, max_y;
+    float view_cos_limit;
+    float th;
+    int32_t far_points;
+    float th_far;
+    int32_t nlevels;
+    float log_scale_factor;
+    float scale_factors[RFE_MAX_LEVELS];
+    int32_t level_mode;
+} rfe_frustum_params;
+int rfe_search_local_points_dev(rfe_ctx* ctx, const rfe_frustum_params* params, const float* q_dev, const float* pw_dev,
+                                const float* normal_dev, const float* min_dist_dev, const float* max_dist_dev, const float* scale_dist_dev,
+                                const uint8_t* valid_dev, const uint8_t* observed_dev, int Np, const float* f_dev, const float* kpts_dev,
+                                const int32_t* kxy_dev, const int32_t* octave_dev, const uint8_t* skip_dev, int Nf, const int32_t* nf_dev,
+                                float th_high, int cand_cap, int32_t* assign_dev, int32_t* best_idx_dev, float* best_dist_dev,
+                                float* second_dist_dev, float* proj_dev, float* proj_xr_dev, float* depth_dev, float* view_cos_dev,
+                                int32_t* level_dev, int32_t* reject_dev, int32_t* stats_dev);
+int rfe_search_local_points(rfe_ctx* ctx, const rfe_frustum_params* params, const float* q, const float* pw, const float* normal,
+                            const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid,
+                            const uint8_t* observed, int Np, const float* f, const float* kpts, const int32_t* kxy, const int32_t* octave,
+                            const uint8_t* skip, int Nf, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist,
+                            float* second_dist, float* proj, float* proj_xr, float* depth, float* view_cos, int32_t* level, int32_t* reject,
+                            int32_t* stats);
+
 /* ---- multi-device pool (BASELINE configs[3] for a C / C++ host) ----
  * The reference runs on ONE device (device_id = 0, src/Extractors/superpoint_onnx.cc:19, src/Matchers/lightglue_onnx.cpp:24) and
  * is a C++ program (src/Tracking.cc:645-651); a pool gives such a host the frame sharding of rover-slam_amd/sharding.py without

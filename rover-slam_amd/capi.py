@@ -25,6 +25,7 @@ EXPORTS = [
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
+    "rfe_search_local_points", "rfe_search_local_points_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
@@ -146,6 +147,39 @@ _s3q = [C.c_void_p, C.POINTER(Sim3Params), _fp, _fp, _fp, _fp, _fp, _fp, _u8p, C
 _s3o = [_ip, _ip, _fp, _fp, _fp, _fp, _ip, _ip, _ip]
 lib.rfe_search_by_projection_sim3.argtypes = _s3q + [C.c_float] + _s3o
 lib.rfe_search_by_projection_sim3_dev.argtypes = _s3q + [_ip, C.c_float, C.c_int] + _s3o
+
+LEVEL_ZERO, LEVEL_PREDICTED = 0, 1                                # RFE_LEVEL_*
+
+
+class FrustumParams(C.Structure):
+    """include/rover_fe.h: rfe_frustum_params -- pose, intrinsics, bounds, gates and scale pyramid of one SearchLocalPoints call."""
+    _fields_ = [("rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("mbf", C.c_float), ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float),
+                ("view_cos_limit", C.c_float), ("th", C.c_float), ("far_points", C.c_int32), ("th_far", C.c_float), ("nlevels", C.c_int32),
+                ("log_scale_factor", C.c_float), ("scale_factors", C.c_float * MAX_LEVELS), ("level_mode", C.c_int32)]
+
+
+def frustum_params(rcw, tcw, ow, intrinsics, mbf, bounds, th, far_points=False, th_far=0.0, scale_factors=(1.0,), log_scale_factor=0.0,
+                   level_mode=LEVEL_ZERO, view_cos_limit=0.5, nlevels=None):
+    """rfe_frustum_params from plain values: rcw [3,3] row-major, intrinsics (fx, fy, cx, cy), bounds (min_x, min_y, max_x, max_y)"""
+    p = FrustumParams()
+    p.rcw[:] = [float(v) for v in np.asarray(rcw, np.float32).reshape(-1)]
+    p.tcw[:] = [float(v) for v in tcw]; p.ow[:] = [float(v) for v in ow]
+    p.fx, p.fy, p.cx, p.cy = (float(v) for v in intrinsics)
+    p.mbf = float(mbf)
+    p.min_x, p.min_y, p.max_x, p.max_y = (float(v) for v in bounds)
+    p.view_cos_limit, p.th, p.far_points, p.th_far = float(view_cos_limit), float(th), int(bool(far_points)), float(th_far)
+    p.nlevels, p.log_scale_factor = len(scale_factors) if nlevels is None else int(nlevels), float(log_scale_factor)
+    for l, v in enumerate(list(scale_factors)[:MAX_LEVELS]):
+        p.scale_factors[l] = float(v)
+    p.level_mode = int(level_mode)
+    return p
+
+
+_lpq = [C.c_void_p, C.POINTER(FrustumParams), _fp, _fp, _fp, _fp, _fp, _fp, _u8p, _u8p, C.c_int, _fp, _fp, _ip, _ip, _u8p, C.c_int]
+_lpo = [_ip, _ip, _fp, _fp, _fp, _fp, _fp, _fp, _ip, _ip, _ip]
+lib.rfe_search_local_points.argtypes = _lpq + [C.c_float] + _lpo
+lib.rfe_search_local_points_dev.argtypes = _lpq + [_ip, C.c_float, C.c_int] + _lpo
 lib.rfe_profile_enable.argtypes = [C.c_void_p, C.c_int]
 lib.rfe_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
 lib.rfe_profile_reset.argtypes = [C.c_void_p]
@@ -692,6 +726,44 @@ class Context:
                                                         a(f), a(kpts), a(kxy), a(matched_in), Nf, a(nf_dev), float(th_accept), cand_cap,
                                                         a(matched), a(best_idx), a(best_dist), a(second_dist), a(proj), a(radius), a(level),
                                                         a(reject), a(stats)))
+
+    def search_local_points(self, params, q, pw, normal, min_dist, max_dist, scale_dist, f, valid=None, observed=None, kpts=None, kxy=None,
+                            octave=None, skip=None, th_high=1.4):
+        """Steps 2 and 3 of Tracking::SearchLocalPoints as one call (rfe_search_local_points, host arrays; DESIGN.md 6f).  params: a
+        FrustumParams (frustum_params()); scale_dist [Np] is the bare mfMaxDistance of PredictScale; exactly one of kpts [Nf,2] f32 and kxy
+        [Nf,2] i32.  Returns a dict: assign [Nf], best_idx / best_dist / second_dist / proj_xr / depth / view_cos / level / reject [Np],
+        proj [Np,2], nmatches, stats [8]."""
+        f32 = lambda a, w: np.ascontiguousarray(a, np.float32).reshape(-1, w)   # noqa: E731
+        qa, fa, pa, na = f32(q, 256), f32(f, 256), f32(pw, 3), f32(normal, 3)
+        mn, mx, sc = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (min_dist, max_dist, scale_dist))
+        Np, Nf = qa.shape[0], fa.shape[0]
+        assert pa.shape[0] == Np and na.shape[0] == Np and mn.shape[0] == Np and mx.shape[0] == Np and sc.shape[0] == Np
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
+        va, ob, ka, xa = opt(valid, np.uint8), opt(observed, np.uint8), opt(kpts, np.float32), opt(kxy, np.int32)
+        oc, sk = opt(octave, np.int32), opt(skip, np.uint8)
+        n1, f1 = max(Np, 1), max(Nf, 1)
+        o = {"assign": np.full((f1,), -1, np.int32), "best_idx": np.full((n1,), -1, np.int32), "best_dist": np.full((n1,), 256, np.float32),
+             "second_dist": np.full((n1,), 256, np.float32), "proj": np.zeros((n1, 2), np.float32), "proj_xr": np.zeros((n1,), np.float32),
+             "depth": np.zeros((n1,), np.float32), "view_cos": np.zeros((n1,), np.float32), "level": np.full((n1,), -1, np.int32),
+             "reject": np.ones((n1,), np.int32)}
+        st = np.zeros((8,), np.int32)
+        n = self._chk(lib.rfe_search_local_points(self.h, C.byref(params), qa.ctypes.data, pa.ctypes.data, na.ctypes.data, mn.ctypes.data,
+                                                  mx.ctypes.data, sc.ctypes.data, _addr(va), _addr(ob), Np, fa.ctypes.data, _addr(ka), _addr(xa),
+                                                  _addr(oc), _addr(sk), Nf, float(th_high), *[o[k].ctypes.data for k in o], st.ctypes.data))
+        out = {k: (v[:Nf] if k == "assign" else v[:Np]) for k, v in o.items()}
+        out.update(nmatches=n, stats=st)
+        return out
+
+    def search_local_points_dev(self, params, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, Nf, cand_cap, assign, stats, valid=None,
+                                observed=None, kpts=None, kxy=None, octave=None, skip=None, nf_dev=None, th_high=1.4, best_idx=None,
+                                best_dist=None, second_dist=None, proj=None, proj_xr=None, depth=None, view_cos=None, level=None, reject=None):
+        """rfe_search_local_points_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
+        outputs land in assign [Nf], stats [8] and the optional per-map-point arrays."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_search_local_points_dev(self.h, C.byref(params), a(q), a(pw), a(normal), a(min_dist), a(max_dist), a(scale_dist), a(valid),
+                                                  a(observed), Np, a(f), a(kpts), a(kxy), a(octave), a(skip), Nf, a(nf_dev), float(th_high),
+                                                  cand_cap, a(assign), a(best_idx), a(best_dist), a(second_dist), a(proj), a(proj_xr), a(depth),
+                                                  a(view_cos), a(level), a(reject), a(stats)))
 
     def distinctive_descriptors(self, desc, offsets):
         """MapPoint::ComputeDistinctiveDescriptors for many map points (MapPoint.cc:438-530)."""

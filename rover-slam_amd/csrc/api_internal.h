@@ -63,7 +63,7 @@ struct HostIo {
 
 private:
     struct Item { void** dev; void* host; char* p; size_t bytes, row_bytes, pitch; bool carve, cut, to_caller; };
-    static constexpr int MAX_ITEMS = 12;
+    static constexpr int MAX_ITEMS = 16;               // rfe_search_local_points stages 13 inputs
     void add(Item* v, int& n, void** dev, const void* host, size_t bytes, bool carve) {
         if (n >= MAX_ITEMS) abort();
         v[n++] = Item{dev, const_cast<void*>(host), nullptr, bytes, 0, 0, carve, false, false};

@@ -1,5 +1,5 @@
 // api_search.hip -- C ABI of librover_fe.so: the descriptor helpers of the callers' classic searches (L2 matrix, binarisation, candidate
-// scan, SearchByProjection1, the Sim3 SearchByProjection overloads, distinctive descriptors).
+// scan, SearchByProjection1, the Sim3 SearchByProjection overloads, SearchLocalPoints, distinctive descriptors).
 #include <string.h>
 #include <algorithm>
 #include "api_internal.h"
@@ -305,6 +305,118 @@ extern "C" int rfe_search_by_projection_sim3(rfe_ctx* c, const rfe_sim3_params* 
         cap = st[1];
     }
     if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection_sim3: candidate lists still overflow");
+    c->ps_cap = std::max(c->ps_cap, cap);
+    if ((rc = io.download())) return rc;
+    if (stats) memcpy(stats, st, 32);
+    return st[0];
+}
+
+// Steps 2 and 3 of Tracking::SearchLocalPoints (src/Tracking.cc:4124-4180): frustum_project_kernel (proj_frustum.hip) writes
+// proj / radius / level into ws_ps, behind the layout of rfe_search_by_projection_dev, and what else isInFrustum leaves in a map point
+// straight into the caller's arrays; the grid, count, fill and resolve kernels of 6d run on them as they are.
+static int lp_check(rfe_ctx* c, const rfe_frustum_params* P, const void* q, const void* pw, const void* normal, const void* min_dist,
+                    const void* max_dist, const void* scale_dist, int Np, const void* f, const void* kpts, const void* kxy, int Nf, int cand_cap,
+                    const void* assign) {
+    if (!P) return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
+    if (Np < 0 || Np > 16384) return fail(c, RFE_ERR_INVALID, "search_local_points: Np outside 0..16384");
+    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_local_points: Nf outside 0..4096");
+    if (!(P->max_x > P->min_x) || !(P->max_y > P->min_y)) return fail(c, RFE_ERR_INVALID, "search_local_points: empty image bounds");
+    if (P->nlevels < 1 || P->nlevels > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, "search_local_points: nlevels outside 1..16");
+    if (P->nlevels > 1 && !(P->log_scale_factor > 0.f)) return fail(c, RFE_ERR_INVALID, "search_local_points: log_scale_factor must be positive");
+    if (P->level_mode != RFE_LEVEL_ZERO && P->level_mode != RFE_LEVEL_PREDICTED) return fail(c, RFE_ERR_INVALID, "search_local_points: unknown level_mode");
+    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_local_points: negative cand_cap");
+    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_local_points: pass exactly one of kpts and kxy");
+    if ((Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !assign)))
+        return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_local_points_dev(rfe_ctx* c, const rfe_frustum_params* P, const float* q, const float* pw, const float* normal,
+                                           const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid,
+                                           const uint8_t* observed, int Np, const float* f, const float* kpts, const int32_t* kxy,
+                                           const int32_t* octave, const uint8_t* skip, int Nf, const int32_t* nf_dev, float th_high, int cand_cap,
+                                           int32_t* assign, int32_t* best_idx, float* best_dist, float* second_dist, float* proj, float* proj_xr,
+                                           float* depth, float* view_cos, int32_t* level, int32_t* reject, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = lp_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, cand_cap, assign);
+    if (rc) return rc;
+    if (!stats) return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
+    RFE_HIP(c, hipSetDevice(c->device));
+    PsBuffers b; float *wproj, *wradius; int32_t* wlevel;
+    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
+        ps_layout(a, Np, Nf, cand_cap, b);
+        const size_t np1 = (size_t)std::max(Np, 1);
+        wproj = a.take<float>(np1 * 2); wradius = a.take<float>(np1); wlevel = a.take<int32_t>(np1);
+    });
+    if (rc) return rc;
+    const float inv_w = 32.f / (P->max_x - P->min_x), inv_h = 24.f / (P->max_y - P->min_y);   // Frame::mfGridElementWidthInv / HeightInv
+    // a rejected point has level -1 and radius 0: an empty list either way
+    const int32_t* pred_level = P->level_mode == RFE_LEVEL_PREDICTED ? wlevel : nullptr;
+    hipStream_t s = c->stream;
+    RFE_HIP(c, hipMemsetAsync(stats + 4, 0, 16, s));
+    { ProfScope ps(c, "lp_frustum");
+      launch_frustum_project(s, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, proj_xr, depth, view_cos, reject,
+                             stats); }
+    { ProfScope ps(c, "ps_grid");
+      launch_proj_grid(s, kpts, kxy, Nf, nf_dev, P->min_x, P->min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
+    { ProfScope ps(c, "ps_count");
+      launch_proj_count(s, wproj, wradius, pred_level, Np, b.cell_start, b.cell_items, b.fxy, octave, P->min_x, P->min_y, inv_w, inv_h, cand_cap,
+                        b.seg_off, b.cand_idx, stats); }
+    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Np, f, Nf, b.seg_off, b.cand_idx, skip, b.cand_dist); }
+    { ProfScope ps(c, "ps_resolve");
+      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, observed, Np, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
+    if (Np > 0) {
+        if (proj) RFE_HIP(c, hipMemcpyAsync(proj, wproj, (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
+        if (level) RFE_HIP(c, hipMemcpyAsync(level, wlevel, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
+    }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+extern "C" int rfe_search_local_points(rfe_ctx* c, const rfe_frustum_params* P, const float* q, const float* pw, const float* normal,
+                                       const float* min_dist, const float* max_dist, const float* scale_dist, const uint8_t* valid,
+                                       const uint8_t* observed, int Np, const float* f, const float* kpts, const int32_t* kxy,
+                                       const int32_t* octave, const uint8_t* skip, int Nf, float th_high, int32_t* assign, int32_t* best_idx,
+                                       float* best_dist, float* second_dist, float* proj, float* proj_xr, float* depth, float* view_cos,
+                                       int32_t* level, int32_t* reject, int32_t* stats) {
+    if (!c) return RFE_ERR_INVALID;
+    int rc = lp_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, 0, assign);
+    if (rc) return rc;
+    auto fin = [](float v) { return v - v == 0.f; };
+    bool ok = fin(th_high) && fin(P->log_scale_factor) && fin(P->th) && fin(P->view_cos_limit) && (!P->far_points || fin(P->th_far));
+    for (float v : P->rcw) ok = ok && fin(v);
+    for (float v : P->tcw) ok = ok && fin(v);
+    for (float v : P->ow) ok = ok && fin(v);
+    for (float v : {P->fx, P->fy, P->cx, P->cy, P->mbf, P->min_x, P->min_y, P->max_x, P->max_y}) ok = ok && fin(v);
+    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->scale_factors[l]);
+    if (!ok) return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite argument");
+    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite keypoint");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dq, *dpw, *dn, *dmin, *dmax, *dsc, *df, *dkp, *dbd, *dsd, *dproj, *dxr, *ddep, *dvc; int32_t *dkx, *doct, *dasg, *dbi, *dlev, *drej, *dst;
+    uint8_t *dval, *dobs, *dsk;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dq, q, (size_t)Np * 256); io.in(dpw, pw, (size_t)Np * 3); io.in(dn, normal, (size_t)Np * 3); io.in(dmin, min_dist, Np);
+    io.in(dmax, max_dist, Np); io.in(dsc, scale_dist, Np); io.in_opt(dval, valid, Np); io.in_opt(dobs, observed, Np);
+    io.in(df, f, (size_t)Nf * 256); io.in_opt(dkp, kpts, (size_t)Nf * 2); io.in_opt(dkx, kxy, (size_t)Nf * 2); io.in_opt(doct, octave, Nf);
+    io.in_opt(dsk, skip, Nf);
+    io.out(dasg, assign, Nf); io.out_opt(dbi, best_idx, Np); io.out_opt(dbd, best_dist, Np); io.out_opt(dsd, second_dist, Np);
+    io.out_opt(dproj, proj, (size_t)Np * 2); io.out_opt(dxr, proj_xr, Np); io.out_opt(ddep, depth, Np); io.out_opt(dvc, view_cos, Np);
+    io.out_opt(dlev, level, Np); io.out_opt(drej, reject, Np);
+    io.scratch(dst, 8);
+    if ((rc = io.upload())) return rc;
+    hipStream_t s = c->stream;
+    // the slots: as rfe_search_by_projection -- the largest count used so far (at least 16 per map point), then once more with what is needed
+    int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Np, 1)), (long long)Np * Nf);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = rfe_search_local_points_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, dobs, Np, df, dkp, dkx, doct, dsk, Nf, nullptr, th_high, cap,
+                                              dasg, dbi, dbd, dsd, dproj, dxr, ddep, dvc, dlev, drej, dst))) return rc;
+        RFE_HIP(c, hipMemcpyAsync(st, dst, 32, hipMemcpyDeviceToHost, s));
+        RFE_HIP(c, hipStreamSynchronize(s));
+        if (!st[3]) break;
+        cap = st[1];
+    }
+    if (st[3]) return fail(c, RFE_ERR_HIP, "search_local_points: candidate lists still overflow");
     c->ps_cap = std::max(c->ps_cap, cap);
     if ((rc = io.download())) return rc;
     if (stats) memcpy(stats, st, 32);

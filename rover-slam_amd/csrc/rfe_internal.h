@@ -355,4 +355,10 @@ void launch_sim3_project(hipStream_t s, const rfe_sim3_params& P, const float* p
                          const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np, float* proj, float* radius,
                          int32_t* level, int32_t* reject, int32_t* stats);
 
+// proj_frustum.hip: Frame::isInFrustum and the head of SearchByProjection1 for every local map point; adds the points in
+// the frustum to stats[4] and the searched ones to stats[5].  proj_xr / depth / view_cos / reject may be NULL
+void launch_frustum_project(hipStream_t s, const rfe_frustum_params& P, const float* pw, const float* normal, const float* min_dist,
+                            const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np, float* proj, float* radius,
+                            int32_t* level, float* proj_xr, float* depth, float* view_cos, int32_t* reject, int32_t* stats);
+
 }  // namespace rfe
