@@ -536,6 +536,92 @@ int rfe_search_local_points(rfe_ctx* ctx, const rfe_frustum_params* params, cons
                             float* second_dist, float* proj, float* proj_xr, float* depth, float* view_cos, int32_t* level, int32_t* reject,
                             int32_t* stats);
 
+/* ---- LocalMapping::CreateNewMapPoints behind the matcher, for all neighbours in one call ----
+ * The filter of SPmatcher::SearchForTriangulation (src/Matchers/SPmatcher.cc:1376-1393) and the geometry loop of
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:662-943) over the matches rfe_match_dev left on the device for P = Nn pairs
+ * (current keyframe, neighbour n): S [Nn] and pairs [Nn,Kmax,2] exactly as it writes them, side 0 the current keyframe, i ascending, every
+ * i and every j at most once per neighbour.  One pinhole camera per keyframe (NLeft == -1, no mpCamera2), mono and rectified stereo /
+ * RGB-D.  The neighbours must be DISTINCT keyframes (has_mp2 of neighbour n is never changed by another neighbour).
+ *   rfe_tri_params: inertial = mbInertial (parallax bound 0.9996, else 0.9998); far_points / th_far = mbFarPoints / mThFarPoints;
+ *   ratio_factor = 1.5f * mfScaleFactor; nlevels (1..RFE_MAX_LEVELS), scale_factors = mvScaleFactors, level_sigma2 = mvLevelSigma2: ONE
+ *   set for the whole call -- all keyframes of a map come from one extractor.  An octave outside 0..RFE_MAX_LEVELS-1 reads level 0.
+ *   rfe_tri_view: rcw (row-major), tcw = GetPose(), ow = GetCameraCenter(); fx, fy, cx, cy, invfx, invfy, mb, mbf of the keyframe.
+ *   view1 (HOST pointer in both forms) and kpts1 [N1,2] = mvKeysUn, kpts1_raw [N1,2] = mvKeys or NULL = kpts1 (KeyFrame::UnprojectStereo
+ *   reads mvKeys), octave1, uright1 = mvuRight, depth1 = mvDepth, has_mp1 [N1] u8 = GetMapPoint(i) != NULL; per neighbour views2 [Nn],
+ *   kpts2 / kpts2_raw [Nn,N2max,2], octave2, uright2, depth2, has_mp2 [Nn,N2max], n2 [Nn] (features of neighbour n, <= N2max),
+ *   neighbour_valid [Nn] u8 or NULL = all 1: the baseline test of :600-620, which the caller makes (ComputeSceneMedianDepth included).
+ * Per slot (n, k < S[n]) the statements run in the reference's order; code [Nn,Kmax] is the first `continue` taken:
+ *    0 created                      1 neighbour skipped (neighbour_valid)   2 i outside 0..N1-1 or j outside 0..n2[n]-1 (nothing is read)
+ *    3 existing map point (has_mp1[i] || has_mp2[n,j])                      4 Triangulate: x3Dh.w == 0 (:797)
+ *    5 no stereo and low parallax (:815)    6 UnprojectStereo: depth <= 0 (:823)    7 z1 <= 0    8 z2 <= 0
+ *    9 / 10 reprojection in view 1, mono (5.991) / stereo (7.8)            11 / 12 the same in view 2
+ *   13 dist1 == 0 || dist2 == 0    14 far point    15 scale consistency    16 passed every gate, claimed by an earlier neighbour
+ *   -1 for k >= S[n] (S[n] is clamped to 0..Kmax).
+ * fp32, one rounding per operation, no contraction, plain / and sqrtf; dot and norm as ((a0 b0 + a1 b1) + a2 b2) and sqrtf of it:
+ *   xn = ((kp.x - cx) / fx, (kp.y - cy) / fy, 1); ray = Rcw^T xn, ray[a] = (r0a xn.x + r1a xn.y) + r2a;
+ *   cosParallaxRays = dot(ray1, ray2) / (norm(ray1) * norm(ray2)); z1 = ((r20 X + r21 Y) + r22 Z) + tz, x1 and y1 alike;
+ *   mono: ((fx x1) / z1 + cx) - kp.x (Pinhole::project); stereo: u = (fx x1) invz + cx, u_r = u - mbf invz, three-term sum left to right;
+ *   UnprojectStereo: x = ((u - cx) z) invfx, y alike, x3D[a] = ((r0a x + r1a y) + r2a z) + ow[a];
+ *   dist = norm(x3D - ow); ratioDist = dist2 / dist1; ratioOctave = scale_factors[octave1] / scale_factors[octave2].
+ *   In double, as the reference writes them: invz = (float)(1.0 / z); err > 5.991 * sigma2 and err > 7.8 * sigma2 (double products);
+ *   cosParallaxRays < 0.9998 / < 0.9996 against the double literals (as float comparisons: < 0x1.ffe5cap-1f / < 0x1.ffcb94p-1f).
+ * Reproduced as written: `else if (bStereo2)` -- the neighbour's stereo parallax is only computed when the current keyframe's feature is
+ *   not stereo (:767-775); u2_r uses the CURRENT keyframe's mbf (:886); UnprojectStereo tests z > 0 again; a NaN passes every < / > gate,
+ *   so a NaN point can be created (stats[5] counts them: drop them if you must); bOnlyStereo and bCoarse change nothing.
+ * Two departures, which ARE this contract (the reference's own build may round differently):
+ *   (a) the stereo parallax cos(2 atan2(mb / 2, depth)) is (d d - h h) / (d d + h h), h = mb / 2, in fp32;
+ *   (b) Triangulate: A as at GeometricTools.cc:73-76; the null vector by a one-sided (Hestenes) Jacobi iteration on the columns of A that
+ *       accumulates V: 6 sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); per pair alpha = |a_p|^2, beta = |a_q|^2, gamma = a_p . a_q
+ *       as left-associated 4-term sums; no rotation when gamma == 0, else zeta = (beta - alpha) / (2 gamma), t = (zeta >= 0 ? 1 : -1) /
+ *       (|zeta| + sqrtf(1 + zeta zeta)), c = 1 / sqrtf(1 + t t), s = c t, (a_p, a_q) <- (c a_p - s a_q, s a_p + c a_q), V alike; x3Dh = the
+ *       column of V whose column of A has the smallest squared norm (the first minimum); w == 0 fails the slot, else x3D = xyz / w.
+ * Across neighbours: the reference adds the point to the current keyframe at once (:930), so a later neighbour skips that feature --
+ *   for every i the slot of the LOWEST n that passes every gate creates the point, the other passing slots get code 16.
+ * Outputs (device pointers in the _dev form; every one but stats may be NULL): code [Nn,Kmax]; x3d [Nn,Kmax,3], the point of every slot
+ *   that got as far as the depth tests (codes 0 and 7..16), else 0; point_stereo [Nn,Kmax] u8 = bPointStereo (1 for code 6 too); the
+ *   points created in creation order (n ascending, then k): out_n, out_idx1, out_idx2 (i32), out_x3d [.,3], out_stereo (u8), each with
+ *   room for N1 entries (a feature is created once; entries past N1, which only input outside the contract can cause, are not written);
+ *   matches [Nn] = S[n] for a valid neighbour, else 0 (their sum is the reference's matchsum).
+ *   stats [8]: 0 points created, 1 slots examined (the S[n] of valid neighbours), 2 slots dropped for an existing map point (code 3),
+ *   3 countStereo, 4 countStereoAttempt (slots whose feature an earlier neighbour took are not counted: the reference never sees them),
+ *   5 created points with a non-finite coordinate, 6..7 = 0.
+ * The _dev form is asynchronous on the ctx stream: no host synchronisation and no host read of device data once the workspace has its
+ * size.  The host form stages its arrays and returns stats[0] >= 0.
+ * Refused (RFE_ERR_INVALID): Nn outside 0..64; N1, N2max or Kmax outside 0..4096; nlevels outside 1..RFE_MAX_LEVELS; a NULL required
+ *   pointer; host form only: a non-finite pose, intrinsic, mb, mbf, th_far, ratio_factor, scale factor or sigma2.  The per-feature arrays
+ *   are not checked in either form.
+ * Out of scope: KannalaBrandt8 and two-camera rigs -- the caller keeps the reference's loop. */
+typedef struct rfe_tri_params {
+    int32_t inertial;
+    int32_t far_points;
+    float th_far;
+    float ratio_factor;
+    int32_t nlevels;
+    float scale_factors[RFE_MAX_LEVELS];
+    float level_sigma2[RFE_MAX_LEVELS];
+} rfe_tri_params;
+typedef struct rfe_tri_view {
+    float rcw[9];                  /* row-major */
+    float tcw[3];
+    float ow[3];
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+} rfe_tri_view;
+int rfe_triangulate_neighbours_dev(rfe_ctx* ctx, const rfe_tri_params* params, const rfe_tri_view* view1, const float* kpts1_dev,
+                                   const float* kpts1_raw_dev, const int32_t* octave1_dev, const float* uright1_dev, const float* depth1_dev,
+                                   const uint8_t* has_mp1_dev, int N1, const rfe_tri_view* views2_dev, const float* kpts2_dev,
+                                   const float* kpts2_raw_dev, const int32_t* octave2_dev, const float* uright2_dev, const float* depth2_dev,
+                                   const uint8_t* has_mp2_dev, const int32_t* n2_dev, const uint8_t* neighbour_valid_dev, int Nn, int N2max,
+                                   const int32_t* S_dev, const int32_t* pairs_dev, int Kmax, int32_t* code_dev, float* x3d_dev,
+                                   uint8_t* point_stereo_dev, int32_t* out_n_dev, int32_t* out_idx1_dev, int32_t* out_idx2_dev,
+                                   float* out_x3d_dev, uint8_t* out_stereo_dev, int32_t* matches_dev, int32_t* stats_dev);
+int rfe_triangulate_neighbours(rfe_ctx* ctx, const rfe_tri_params* params, const rfe_tri_view* view1, const float* kpts1,
+                               const float* kpts1_raw, const int32_t* octave1, const float* uright1, const float* depth1,
+                               const uint8_t* has_mp1, int N1, const rfe_tri_view* views2, const float* kpts2, const float* kpts2_raw,
+                               const int32_t* octave2, const float* uright2, const float* depth2, const uint8_t* has_mp2, const int32_t* n2,
+                               const uint8_t* neighbour_valid, int Nn, int N2max, const int32_t* S, const int32_t* pairs, int Kmax,
+                               int32_t* code, float* x3d, uint8_t* point_stereo, int32_t* out_n, int32_t* out_idx1, int32_t* out_idx2,
+                               float* out_x3d, uint8_t* out_stereo, int32_t* matches, int32_t* stats);
+
 /* ---- multi-device pool (BASELINE configs[3] for a C / C++ host) ----
  * The reference runs on ONE device (device_id = 0, src/Extractors/superpoint_onnx.cc:19, src/Matchers/lightglue_onnx.cpp:24) and
  * is a C++ program (src/Tracking.cc:645-651); a pool gives such a host the frame sharding of rover-slam_amd/sharding.py without

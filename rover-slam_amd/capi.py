@@ -25,7 +25,7 @@ EXPORTS = [
     "rfe_search_candidates", "rfe_distinctive_descriptors",
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
-    "rfe_search_local_points", "rfe_search_local_points_dev",
+    "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
@@ -180,6 +180,44 @@ _lpq = [C.c_void_p, C.POINTER(FrustumParams), _fp, _fp, _fp, _fp, _fp, _fp, _u8p
 _lpo = [_ip, _ip, _fp, _fp, _fp, _fp, _fp, _fp, _ip, _ip, _ip]
 lib.rfe_search_local_points.argtypes = _lpq + [C.c_float] + _lpo
 lib.rfe_search_local_points_dev.argtypes = _lpq + [_ip, C.c_float, C.c_int] + _lpo
+class TriParams(C.Structure):
+    """include/rover_fe.h: rfe_tri_params -- the switches, gates and scale pyramid of one CreateNewMapPoints call."""
+    _fields_ = [("inertial", C.c_int32), ("far_points", C.c_int32), ("th_far", C.c_float), ("ratio_factor", C.c_float), ("nlevels", C.c_int32),
+                ("scale_factors", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
+
+
+class TriView(C.Structure):
+    """include/rover_fe.h: rfe_tri_view -- pose, camera centre, intrinsics and stereo baseline of one keyframe."""
+    _fields_ = [("rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float)]
+
+
+def tri_params(inertial, far_points, th_far, ratio_factor, scale_factors, level_sigma2, nlevels=None):
+    """rfe_tri_params from plain values (ratio_factor = 1.5f * mfScaleFactor)"""
+    p = TriParams()
+    p.inertial, p.far_points, p.th_far, p.ratio_factor = int(bool(inertial)), int(bool(far_points)), float(th_far), float(ratio_factor)
+    p.nlevels = len(scale_factors) if nlevels is None else int(nlevels)
+    for l, v in enumerate(list(scale_factors)[:MAX_LEVELS]):
+        p.scale_factors[l] = float(v)
+    for l, v in enumerate(list(level_sigma2)[:MAX_LEVELS]):
+        p.level_sigma2[l] = float(v)
+    return p
+
+
+def tri_view(rcw, tcw, ow, fx, fy, cx, cy, invfx, invfy, mb, mbf):
+    """rfe_tri_view from plain values: rcw [3,3] row-major"""
+    v = TriView()
+    v.rcw[:] = [float(x) for x in np.asarray(rcw, np.float32).reshape(-1)]
+    v.tcw[:] = [float(x) for x in tcw]; v.ow[:] = [float(x) for x in ow]
+    v.fx, v.fy, v.cx, v.cy, v.invfx, v.invfy, v.mb, v.mbf = (float(x) for x in (fx, fy, cx, cy, invfx, invfy, mb, mbf))
+    return v
+
+
+TRI_OUTPUTS = ("code", "x3d", "point_stereo", "out_n", "out_idx1", "out_idx2", "out_x3d", "out_stereo", "matches")
+_tri = [C.c_void_p, C.POINTER(TriParams), C.POINTER(TriView), _fp, _fp, _ip, _fp, _fp, _u8p, C.c_int, C.c_void_p, _fp, _fp, _ip, _fp, _fp, _u8p, _ip,
+        _u8p, C.c_int, C.c_int, _ip, _ip, C.c_int, _ip, _fp, _u8p, _ip, _ip, _ip, _fp, _u8p, _ip, _ip]
+lib.rfe_triangulate_neighbours.argtypes = _tri
+lib.rfe_triangulate_neighbours_dev.argtypes = _tri
 lib.rfe_profile_enable.argtypes = [C.c_void_p, C.c_int]
 lib.rfe_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
 lib.rfe_profile_reset.argtypes = [C.c_void_p]
@@ -764,6 +802,59 @@ class Context:
                                                   a(observed), Np, a(f), a(kpts), a(kxy), a(octave), a(skip), Nf, a(nf_dev), float(th_high),
                                                   cand_cap, a(assign), a(best_idx), a(best_dist), a(second_dist), a(proj), a(proj_xr), a(depth),
                                                   a(view_cos), a(level), a(reject), a(stats)))
+
+    def triangulate_neighbours(self, params, view1, kpts1, octave1, uright1, depth1, has_mp1, views2, kpts2, octave2, uright2, depth2, has_mp2,
+                               n2, S, pairs, kpts1_raw=None, kpts2_raw=None, neighbour_valid=None, outputs=TRI_OUTPUTS):
+        """LocalMapping::CreateNewMapPoints behind the matcher for all neighbours (rfe_triangulate_neighbours, host arrays; DESIGN.md 6g).
+        params: a TriParams (tri_params()); view1: a TriView, views2: a sequence of Nn of them; kpts2 [Nn,N2max,2] and the other neighbour
+        arrays [Nn,N2max]; S [Nn], pairs [Nn,Kmax,2] as rfe_match_dev writes them.  outputs: the arrays to ask for (the others are passed
+        as NULL).  Returns a dict: code [Nn,Kmax], x3d [Nn,Kmax,3], point_stereo [Nn,Kmax], the created points in creation order (out_n,
+        out_idx1, out_idx2, out_x3d [created,3], out_stereo), matches [Nn], created, stats [8]."""
+        pr = np.ascontiguousarray(pairs, np.int32)
+        Nn, Kmax = pr.shape[0], pr.shape[1]
+        k1 = np.ascontiguousarray(kpts1, np.float32).reshape(-1, 2)
+        N1 = k1.shape[0]
+        k2 = np.ascontiguousarray(kpts2, np.float32).reshape(Nn, -1, 2) if Nn else np.zeros((0, 0, 2), np.float32)
+        N2max = k2.shape[1]
+        v2 = (TriView * max(Nn, 1))(*views2)
+        flat = lambda a, dt, n: np.ascontiguousarray(a, dt).reshape(-1)[:n] if n else np.zeros((0,), dt)   # noqa: E731
+        opt = lambda a, n: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1)           # noqa: E731
+        o1, u1, d1, m1 = flat(octave1, np.int32, N1), flat(uright1, np.float32, N1), flat(depth1, np.float32, N1), flat(has_mp1, np.uint8, N1)
+        f2 = Nn * N2max
+        o2, u2, d2, m2 = flat(octave2, np.int32, f2), flat(uright2, np.float32, f2), flat(depth2, np.float32, f2), flat(has_mp2, np.uint8, f2)
+        assert len(o1) == N1 and len(m1) == N1 and len(o2) == f2 and len(m2) == f2
+        nn2, Sa = flat(n2, np.int32, Nn), flat(S, np.int32, Nn)
+        r1, r2 = opt(kpts1_raw, N1), opt(kpts2_raw, f2)
+        nv = None if neighbour_valid is None else np.ascontiguousarray(neighbour_valid, np.uint8).reshape(-1)
+        n1, s1 = max(N1, 1), max(Nn * Kmax, 1)
+        o = {"code": np.full((s1,), -1, np.int32), "x3d": np.zeros((s1, 3), np.float32), "point_stereo": np.zeros((s1,), np.uint8),
+             "out_n": np.zeros((n1,), np.int32), "out_idx1": np.zeros((n1,), np.int32), "out_idx2": np.zeros((n1,), np.int32),
+             "out_x3d": np.zeros((n1, 3), np.float32), "out_stereo": np.zeros((n1,), np.uint8), "matches": np.zeros((max(Nn, 1),), np.int32)}
+        assert tuple(o) == TRI_OUTPUTS
+        st = np.zeros((8,), np.int32)
+        n = self._chk(lib.rfe_triangulate_neighbours(self.h, C.byref(params), C.byref(view1), _addr(k1), _addr(r1), _addr(o1), _addr(u1), _addr(d1),
+                                                     _addr(m1), N1, C.cast(v2, C.c_void_p), _addr(k2), _addr(r2), _addr(o2), _addr(u2), _addr(d2),
+                                                     _addr(m2), _addr(nn2), _addr(nv), Nn, N2max, _addr(Sa), _addr(pr), Kmax,
+                                                     *[o[k].ctypes.data if k in outputs else None for k in o], st.ctypes.data))
+        out = {"code": o["code"][:Nn * Kmax].reshape(Nn, Kmax), "x3d": o["x3d"][:Nn * Kmax].reshape(Nn, Kmax, 3),
+               "point_stereo": o["point_stereo"][:Nn * Kmax].reshape(Nn, Kmax), "matches": o["matches"][:Nn]}
+        out.update({k: o[k][:n] for k in ("out_n", "out_idx1", "out_idx2", "out_x3d", "out_stereo")})
+        out = {k: v for k, v in out.items() if k in outputs}
+        out.update(created=n, stats=st)
+        return out
+
+    def triangulate_neighbours_dev(self, params, view1, kpts1, octave1, uright1, depth1, has_mp1, N1, views2, kpts2, octave2, uright2, depth2,
+                                   has_mp2, n2, Nn, N2max, S, pairs, Kmax, stats, kpts1_raw=None, kpts2_raw=None, neighbour_valid=None, code=None,
+                                   x3d=None, point_stereo=None, out_n=None, out_idx1=None, out_idx2=None, out_x3d=None, out_stereo=None,
+                                   matches=None):
+        """rfe_triangulate_neighbours_dev: params and view1 are host structures, every array (views2 [Nn] included) a DevBuf (or a raw
+        device address / torch tensor); asynchronous on the ctx stream.  The out_* arrays need room for N1 entries."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_triangulate_neighbours_dev(self.h, C.byref(params), C.byref(view1), a(kpts1), a(kpts1_raw), a(octave1), a(uright1),
+                                                     a(depth1), a(has_mp1), N1, a(views2), a(kpts2), a(kpts2_raw), a(octave2), a(uright2),
+                                                     a(depth2), a(has_mp2), a(n2), a(neighbour_valid), Nn, N2max, a(S), a(pairs), Kmax, a(code),
+                                                     a(x3d), a(point_stereo), a(out_n), a(out_idx1), a(out_idx2), a(out_x3d), a(out_stereo),
+                                                     a(matches), a(stats)))
 
     def distinctive_descriptors(self, desc, offsets):
         """MapPoint::ComputeDistinctiveDescriptors for many map points (MapPoint.cc:438-530)."""

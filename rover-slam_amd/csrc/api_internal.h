@@ -63,7 +63,7 @@ struct HostIo {
 
 private:
     struct Item { void** dev; void* host; char* p; size_t bytes, row_bytes, pitch; bool carve, cut, to_caller; };
-    static constexpr int MAX_ITEMS = 16;               // rfe_search_local_points stages 13 inputs
+    static constexpr int MAX_ITEMS = 20;               // rfe_triangulate_neighbours stages 17 inputs
     void add(Item* v, int& n, void** dev, const void* host, size_t bytes, bool carve) {
         if (n >= MAX_ITEMS) abort();
         v[n++] = Item{dev, const_cast<void*>(host), nullptr, bytes, 0, 0, carve, false, false};
@@ -120,6 +120,15 @@ int run_host_graph(rfe_ctx* c, rfe_ctx::HostGraph& g, const std::string& key, F&
     return RFE_OK;
 }
 std::string host_graph_key(const rfe_ctx* c, const char* kind, std::initializer_list<long long> v);
+
+// ---------------------------------------------------------------- rfe_triangulate_neighbours* (api_triangulate.hip)
+// ws_tri: per slot the code, the point and bPointStereo between the kernels; claim [N1] and count [64], which every call presets
+struct TriBuffers { int32_t *code, *claim, *count; float* x3d; uint8_t* stereo; };
+inline void tri_layout(Bump& a, int N1, int Nn, int Kmax, TriBuffers& b) {
+    const size_t slots = std::max<size_t>((size_t)Nn * Kmax, 1);
+    b.claim = a.take<int32_t>(std::max(N1, 1)); b.count = a.take<int32_t>(64);
+    b.code = a.take<int32_t>(slots); b.x3d = a.take<float>(slots * 3); b.stereo = a.take<uint8_t>(slots);
+}
 
 // ---------------------------------------------------------------- GEMM argument builders (api_extract.hip, api_match.hip)
 GemmArgs gemm_plain(const float* A, int lda, const float* Bw, int ldb, const float* bias, float* C, int ldc, int M, int N, int K);

@@ -137,6 +137,7 @@ struct rfe_ctx {
     bool sp_cnt_dirty = false;           // the tail ran and its ranking kernel was not enqueued behind it (an error in between): zeroed before the next use
     void* ws_ps = nullptr; size_t ws_ps_bytes = 0;   // rfe_search_by_projection*: grid, segment offsets, (index, distance) slots
     int ps_cap = 0;                                  // rfe_search_by_projection (host form): most slots any call has needed
+    void* ws_tri = nullptr; size_t ws_tri_bytes = 0; // rfe_triangulate_neighbours*: per-slot results, claims, per-neighbour counts
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -360,5 +361,18 @@ void launch_sim3_project(hipStream_t s, const rfe_sim3_params& P, const float* p
 void launch_frustum_project(hipStream_t s, const rfe_frustum_params& P, const float* pw, const float* normal, const float* min_dist,
                             const float* max_dist, const float* scale_dist, const uint8_t* valid, int Np, float* proj, float* radius,
                             int32_t* level, float* proj_xr, float* depth, float* view_cos, int32_t* reject, int32_t* stats);
+// triangulate.hip: CreateNewMapPoints behind the matcher for every match slot of every neighbour.  launch_tri_eval leaves
+// code (0 = passed every gate) / x3d / bPointStereo per slot in the workspace and atomicMin's claim [N1] (preset to a value above 63);
+// launch_tri_resolve gives the losers code 16, writes the per-slot outputs, the list in creation order (room for N1 entries), matches and
+// stats (preset to 0; count [64] too).  Every output but stats may be NULL
+void launch_tri_eval(hipStream_t s, const rfe_tri_params& P, const rfe_tri_view& V1, const float* kpts1, const float* kraw1, const int32_t* oct1,
+                     const float* ur1, const float* dep1, const uint8_t* mp1, int N1, const rfe_tri_view* views2, const float* kpts2,
+                     const float* kraw2, const int32_t* oct2, const float* ur2, const float* dep2, const uint8_t* mp2, const int32_t* n2,
+                     const uint8_t* nvalid, int Nn, int N2max, const int32_t* S, const int32_t* pairs, int Kmax, int32_t* wcode, float* wx3d,
+                     uint8_t* wstereo, int32_t* claim);
+void launch_tri_resolve(hipStream_t s, const int32_t* S, const uint8_t* nvalid, const int32_t* pairs, int N1, int Nn, int Kmax, int32_t* wcode,
+                        const float* wx3d, const uint8_t* wstereo, const int32_t* claim, int32_t* count, int32_t* code, float* x3d,
+                        uint8_t* point_stereo, int32_t* out_n, int32_t* out_idx1, int32_t* out_idx2, float* out_x3d, uint8_t* out_stereo,
+                        int32_t* matches, int32_t* stats);
 
 }  // namespace rfe
