@@ -622,6 +622,85 @@ int rfe_triangulate_neighbours(rfe_ctx* ctx, const rfe_tri_params* params, const
                                int32_t* code, float* x3d, uint8_t* point_stereo, int32_t* out_n, int32_t* out_idx1, int32_t* out_idx2,
                                float* out_x3d, uint8_t* out_stereo, int32_t* matches, int32_t* stats);
 
+/* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
+ * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
+ * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates
+ * (src/KeyFrameDatabase.cc:660-740, :1045-1100) up to and including the L1 scores.
+ *
+ * A vocabulary is a tree in flat host arrays (rfe_bow_vocab_desc): node 0 is the root, children [child_offsets[i], child_offsets[i + 1])
+ * are node i's children in their stored order, desc [n_nodes, D] u8 the node descriptors (row 0 is ignored), weight [n_nodes] f64,
+ * word_id [n_nodes] (-1 for inner nodes), parent [n_nodes] (the root's entry is ignored).  weighting / scoring carry DBoW3's enum values.
+ * Leaves may lie at different depths.  Refused (RFE_ERR_INVALID, rfe_last_error): n_nodes outside 1..2^24; D not a multiple of 8 or
+ * outside 8..256; scoring != RFE_BOW_L1_NORM; weighting outside 0..3; child_offsets not ascending from 0 to n_nodes - 1; a child index
+ * out of range or the root; a node with two parents; parent[] disagreeing with children[]; a node the root does not reach; a childless
+ * node without a word id.
+ * rfe_bow_vocab_load reads DBoW3's UNCOMPRESSED binary stream (Vocabulary::toStream(.., false)): u64 88877711233, u8 compressed, u32
+ * nnodes, i32 k, L, scoring, weighting, then per node but the root u32 id, u32 parent, f64 weight, i32 cols, rows, type and cols bytes,
+ * then u32 nwords and (u32 word, u32 node) pairs; children in the order of the file.  RFE_ERR_IO: the file cannot be read, is not such
+ * a stream, is compressed (re-save it uncompressed; there is no quicklz here), holds a descriptor that is not one CV_8U row of one common
+ * width, or a count, id or length the file's size does not bear out.  Then rfe_bow_vocab_create's checks. */
+#define RFE_BOW_TF_IDF 0
+#define RFE_BOW_TF 1
+#define RFE_BOW_IDF 2
+#define RFE_BOW_BINARY 3
+#define RFE_BOW_L1_NORM 0
+typedef struct rfe_bow_vocab rfe_bow_vocab;
+typedef struct rfe_bow_db rfe_bow_db;
+typedef struct rfe_bow_vocab_desc {
+    int32_t k, L, weighting, scoring;
+    int32_t n_nodes, D;
+    const int32_t* parent;
+    const int32_t* child_offsets;
+    const int32_t* children;
+    const uint8_t* desc;
+    const double* weight;
+    const int32_t* word_id;
+} rfe_bow_vocab_desc;
+int rfe_bow_vocab_create(rfe_ctx* ctx, const rfe_bow_vocab_desc* desc, rfe_bow_vocab** out);
+int rfe_bow_vocab_load(rfe_ctx* ctx, const char* path, rfe_bow_vocab** out);
+void rfe_bow_vocab_destroy(rfe_bow_vocab* vocab);
+/* info [8]: k, L, n_nodes, n_words (childless nodes), D, weighting, scoring, depth of the deepest leaf */
+int rfe_bow_vocab_info(const rfe_bow_vocab* vocab, int32_t* info);
+/* Vocabulary::transform(features, v, fv, levelsup) of N features: desc_f32 [N,256] floats, binarised as rfe_binarize_descriptors does
+ * (byte = value > 0, NaN -> 0; the vocabulary's D must be 256), or desc_u8 [N,D] bytes as they are -- exactly one of the two non-NULL.
+ * Per feature the descent: from the root, at every node the child with the smallest distance (popcount of the xor over the D bytes),
+ * the first of equal ones, until a childless node: word [N] = its word id, weight [N] = its weight, node [N] = the node passed at depth
+ * L - levelsup (the root when that is <= 0; the leaf's own node id when the leaf is shallower -- the reference leaves *nid unwritten
+ * there).  Features with weight > 0 enter the results: bow_word ascending with bow_value = the weights of the word's features summed in
+ * feature order (TF_IDF, TF) or the first one (IDF, BINARY), then every value divided by their sum taken in word order (when > 0), all
+ * in IEEE double, one rounding per operation; fv_node ascending, node i's features fv_feat[fv_offsets[i] .. fv_offsets[i + 1]) ascending.
+ * word / node / weight may be NULL; the others need room for N (fv_offsets N + 1) entries and are written up to bow_n / fv_n /
+ * fv_offsets[fv_n] only.  N == 0 or every feature stopped: bow_n = fv_n = 0.  The _dev form is asynchronous on the ctx stream; the
+ * host form returns bow_n.  Refused (RFE_ERR_INVALID): N outside 0..4096; both or neither descriptor pointer; desc_f32 with D != 256;
+ * a vocabulary created on another device; desc_f32_dev not 16-byte or desc_u8_dev not 8-byte aligned. */
+int rfe_bow_transform_dev(rfe_ctx* ctx, const rfe_bow_vocab* vocab, const float* desc_f32_dev, const uint8_t* desc_u8_dev, int N, int levelsup,
+                          int32_t* word_dev, int32_t* node_dev, double* weight_dev, int32_t* bow_n_dev, int32_t* bow_word_dev,
+                          double* bow_value_dev, int32_t* fv_n_dev, int32_t* fv_node_dev, int32_t* fv_offsets_dev, int32_t* fv_feat_dev);
+int rfe_bow_transform(rfe_ctx* ctx, const rfe_bow_vocab* vocab, const float* desc_f32, const uint8_t* desc_u8, int N, int levelsup,
+                      int32_t* word, int32_t* node, double* weight, int32_t* bow_n, int32_t* bow_word, double* bow_value, int32_t* fv_n,
+                      int32_t* fv_node, int32_t* fv_offsets, int32_t* fv_feat);
+/* The keyframe database: BoW vectors (ascending words, values) in a device store that grows geometrically; an entry id is the number
+ * of adds before it since creation or the last clear, and stays valid through later adds and erases (an erased entry's words stay in the
+ * store until rfe_bow_db_clear).  rfe_bow_db_size = entry ids issued, erased ones included: the length of the per-entry arrays below.
+ * rfe_bow_db_query*: common [size] = the query's words present in the entry (0 for an erased one); over the entries that are not excluded
+ * (exclude [size] u8, may be NULL): max_common, n_sharing = entries with common > 0; min_common = (int)(max_common * 0.8f); scored [size]
+ * = not excluded and common > min_common; score [size] = L1Scoring::score(query, entry) where scored -- the terms |v - w| - |v| - |w|
+ * of the common words summed in ascending word order, then -sum / 2, in IEEE double -- and not written elsewhere.  stats [4] = max_common,
+ * min_common, n_sharing, n_scored.  The query's words must ascend (as rfe_bow_transform writes them); nq within 0..4096, an entry's n
+ * within 0..4096.  The _dev forms are asynchronous on the stream of the ctx the database was created on, except that an add that grows
+ * the store waits for that stream first.  The host query returns n_scored. */
+int rfe_bow_db_create(rfe_ctx* ctx, rfe_bow_db** out);
+void rfe_bow_db_destroy(rfe_bow_db* db);
+int rfe_bow_db_add_dev(rfe_bow_db* db, const int32_t* word_dev, const double* value_dev, int n, int32_t* entry_id);
+int rfe_bow_db_add(rfe_bow_db* db, const int32_t* word, const double* value, int n, int32_t* entry_id);
+int rfe_bow_db_erase(rfe_bow_db* db, int32_t entry_id);
+int rfe_bow_db_clear(rfe_bow_db* db);
+int rfe_bow_db_size(const rfe_bow_db* db);
+int rfe_bow_db_query_dev(rfe_bow_db* db, const int32_t* q_word_dev, const double* q_value_dev, int nq, const uint8_t* exclude_dev,
+                         int32_t* common_dev, uint8_t* scored_dev, double* score_dev, int32_t* stats_dev);
+int rfe_bow_db_query(rfe_bow_db* db, const int32_t* q_word, const double* q_value, int nq, const uint8_t* exclude, int32_t* common,
+                     uint8_t* scored, double* score, int32_t* stats);
+
 /* ---- multi-device pool (BASELINE configs[3] for a C / C++ host) ----
  * The reference runs on ONE device (device_id = 0, src/Extractors/superpoint_onnx.cc:19, src/Matchers/lightglue_onnx.cpp:24) and
  * is a C++ program (src/Tracking.cc:645-651); a pool gives such a host the frame sharding of rover-slam_amd/sharding.py without
@@ -742,6 +821,11 @@ int rfe_k_pool_inject_gather_failure(rfe_pool* pool, int member);
  * the initializers alone, no hyper-parameter readers).  RFE_OK, or RFE_ERR_IO with the reason in err.  tests/test_onnx_cpp.py holds it bit for bit
  * against rover-slam_amd/onnx_weights.py. */
 int rfe_k_onnx_convert(const char* path, int kind, int weights_only, float* blob, rfe_hparams* hp, char* err, int errlen);
+/* The vocabulary reader and rfe_bow_vocab_create's checks without a ctx (and without a GPU): hdr [6] = k, L, weighting, scoring, n_nodes, D
+ * of the stream at `path`; with the array pointers non-NULL (sized from a first call with all of them NULL) the tree as rfe_bow_vocab_desc
+ * lays it out.  RFE_OK, or RFE_ERR_IO / RFE_ERR_INVALID with the reason in err. */
+int rfe_k_bow_vocab_read(const char* path, int32_t* hdr, int32_t* parent, int32_t* child_offsets, int32_t* children, uint8_t* desc,
+                         double* weight, int32_t* word_id, char* err, int errlen);
 
 #ifdef __cplusplus
 }

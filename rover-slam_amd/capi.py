@@ -26,10 +26,13 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
+    "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
+    "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
+    "rfe_bow_db_query", "rfe_bow_db_query_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
-    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_cross_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert",
+    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_cross_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert", "rfe_k_bow_vocab_read",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -218,6 +221,40 @@ _tri = [C.c_void_p, C.POINTER(TriParams), C.POINTER(TriView), _fp, _fp, _ip, _fp
         _u8p, C.c_int, C.c_int, _ip, _ip, C.c_int, _ip, _fp, _u8p, _ip, _ip, _ip, _fp, _u8p, _ip, _ip]
 lib.rfe_triangulate_neighbours.argtypes = _tri
 lib.rfe_triangulate_neighbours_dev.argtypes = _tri
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
+BOW_L1_NORM = 0
+BOW_MAX_N = 4096
+
+
+class BowVocabDesc(C.Structure):
+    """include/rover_fe.h: rfe_bow_vocab_desc -- a DBoW3 vocabulary tree in flat host arrays."""
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32), ("n_nodes", C.c_int32), ("D", C.c_int32),
+                ("parent", C.c_void_p), ("child_offsets", C.c_void_p), ("children", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p),
+                ("word_id", C.c_void_p)]
+
+
+BOW_VOCAB_ARRAYS = (("parent", np.int32), ("child_offsets", np.int32), ("children", np.int32), ("desc", np.uint8), ("weight", np.float64),
+                    ("word_id", np.int32))
+lib.rfe_bow_vocab_create.argtypes = [C.c_void_p, C.POINTER(BowVocabDesc), C.POINTER(C.c_void_p)]
+lib.rfe_bow_vocab_load.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+lib.rfe_bow_vocab_destroy.argtypes = [C.c_void_p]
+lib.rfe_bow_vocab_destroy.restype = None
+lib.rfe_bow_vocab_info.argtypes = [C.c_void_p, _ip]
+_bowt = [C.c_void_p, C.c_void_p, _fp, _u8p, C.c_int, C.c_int, _ip, _ip, _vp, _ip, _ip, _vp, _ip, _ip, _ip, _ip]
+lib.rfe_bow_transform.argtypes = _bowt
+lib.rfe_bow_transform_dev.argtypes = _bowt
+lib.rfe_bow_db_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+lib.rfe_bow_db_destroy.argtypes = [C.c_void_p]
+lib.rfe_bow_db_destroy.restype = None
+lib.rfe_bow_db_add.argtypes = [C.c_void_p, _ip, _vp, C.c_int, C.POINTER(C.c_int32)]
+lib.rfe_bow_db_add_dev.argtypes = lib.rfe_bow_db_add.argtypes
+lib.rfe_bow_db_erase.argtypes = [C.c_void_p, C.c_int32]
+lib.rfe_bow_db_clear.argtypes = [C.c_void_p]
+lib.rfe_bow_db_size.argtypes = [C.c_void_p]
+_bowq = [C.c_void_p, _ip, _vp, C.c_int, _u8p, _ip, _u8p, _vp, _ip]
+lib.rfe_bow_db_query.argtypes = _bowq
+lib.rfe_bow_db_query_dev.argtypes = _bowq
+lib.rfe_k_bow_vocab_read.argtypes = [C.c_char_p, _ip, _ip, _ip, _ip, _u8p, _vp, _ip, C.c_char_p, C.c_int]
 lib.rfe_profile_enable.argtypes = [C.c_void_p, C.c_int]
 lib.rfe_profile_filter.argtypes = [C.c_void_p, C.c_char_p]
 lib.rfe_profile_reset.argtypes = [C.c_void_p]
@@ -307,6 +344,121 @@ class DevBuf:
         if self.ptr:
             lib.rfe_free(self.ctx.h, self.ptr)
             self.ptr = None
+
+
+def read_bow_vocab(path):
+    """The library's reader of DBoW3's uncompressed binary vocabulary stream, without a device (rfe_k_bow_vocab_read): a dict with k, L,
+    weighting, scoring, n_nodes, D and the arrays of rfe_bow_vocab_desc.  RfeError with the reader's reason when it refuses the file."""
+    hdr = np.zeros((6,), np.int32)
+    err = C.create_string_buffer(512)
+    rc = lib.rfe_k_bow_vocab_read(path.encode(), hdr.ctypes.data, None, None, None, None, None, None, err, 512)
+    if rc != 0:
+        raise RfeError(f"librover_fe error {rc}: {err.value.decode()}")
+    k, L, weighting, scoring, n, D = (int(v) for v in hdr)
+    v = {"k": k, "L": L, "weighting": weighting, "scoring": scoring, "n_nodes": n, "D": D,
+         "parent": np.zeros((n,), np.int32), "child_offsets": np.zeros((n + 1,), np.int32), "children": np.zeros((max(n - 1, 1),), np.int32),
+         "desc": np.zeros((n, D), np.uint8), "weight": np.zeros((n,), np.float64), "word_id": np.zeros((n,), np.int32)}
+    rc = lib.rfe_k_bow_vocab_read(path.encode(), hdr.ctypes.data, *[v[name].ctypes.data for name, _ in BOW_VOCAB_ARRAYS], err, 512)
+    if rc != 0:
+        raise RfeError(f"librover_fe error {rc}: {err.value.decode()}")
+    v["children"] = v["children"][:n - 1]
+    return v
+
+
+class BowVocab:
+    """A DBoW3 vocabulary on the device of `ctx` (rfe_bow_vocab_create / rfe_bow_vocab_load).  tree: a dict with k, L,
+    weighting, scoring, D and the arrays of rfe_bow_vocab_desc (n_nodes = len(weight)); path: an uncompressed DBoW3 binary stream."""
+
+    def __init__(self, ctx, tree=None, path=None):
+        assert (tree is None) != (path is None)
+        self.ctx, h = ctx, C.c_void_p()
+        if path is not None:
+            ctx._chk(lib.rfe_bow_vocab_load(ctx.h, path.encode(), C.byref(h)))
+        else:
+            a = {name: np.ascontiguousarray(tree[name], dt) for name, dt in BOW_VOCAB_ARRAYS}
+            d = BowVocabDesc(int(tree["k"]), int(tree["L"]), int(tree["weighting"]), int(tree["scoring"]),
+                             int(tree.get("n_nodes", len(a["weight"]))), int(tree["D"]), *[a[name].ctypes.data for name, _ in BOW_VOCAB_ARRAYS])
+            ctx._chk(lib.rfe_bow_vocab_create(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+        info = np.zeros((8,), np.int32)
+        lib.rfe_bow_vocab_info(self.h, info.ctypes.data)
+        self.k, self.L, self.n_nodes, self.n_words, self.D, self.weighting, self.scoring, self.depth = (int(v) for v in info)
+
+    def close(self):
+        if self.h:
+            lib.rfe_bow_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BowDatabase:
+    """The keyframe database's BoW vectors on the device (rfe_bow_db_*): add / erase / clear, and query = common-word counts,
+    the 0.8 max gate and the L1 scores of KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates."""
+
+    def __init__(self, ctx):
+        self.ctx, h = ctx, C.c_void_p()
+        ctx._chk(lib.rfe_bow_db_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib.rfe_bow_db_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.ctx._chk(lib.rfe_bow_db_size(self.h))
+
+    def add(self, word, value):
+        w, v = np.ascontiguousarray(word, np.int32).reshape(-1), np.ascontiguousarray(value, np.float64).reshape(-1)
+        assert len(w) == len(v)
+        e = C.c_int32(-1)
+        self.ctx._chk(lib.rfe_bow_db_add(self.h, w.ctypes.data, v.ctypes.data, len(w), C.byref(e)))
+        return e.value
+
+    def add_dev(self, word, value, n):
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        e = C.c_int32(-1)
+        self.ctx._chk(lib.rfe_bow_db_add_dev(self.h, a(word), a(value), int(n), C.byref(e)))
+        return e.value
+
+    def erase(self, entry):
+        self.ctx._chk(lib.rfe_bow_db_erase(self.h, int(entry)))
+
+    def clear(self):
+        self.ctx._chk(lib.rfe_bow_db_clear(self.h))
+
+    def query(self, word, value, exclude=None, score=None):
+        """Host arrays.  score: the array the scores are written into (float64 [len(self)]; zeros when None) -- entries that are not scored
+        keep what it held.  Returns a dict: common, scored, score, stats [4] = max_common, min_common, n_sharing, n_scored."""
+        E = len(self)
+        w, v = np.ascontiguousarray(word, np.int32).reshape(-1), np.ascontiguousarray(value, np.float64).reshape(-1)
+        assert len(w) == len(v)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, np.uint8).reshape(-1)
+        assert ex is None or len(ex) == E
+        common, scored = np.zeros((max(E, 1),), np.int32), np.zeros((max(E, 1),), np.uint8)
+        sc = np.zeros((max(E, 1),), np.float64)
+        if score is not None:
+            sc[:E] = score
+        st = np.zeros((4,), np.int32)
+        self.ctx._chk(lib.rfe_bow_db_query(self.h, w.ctypes.data, v.ctypes.data, len(w), _addr(ex), common.ctypes.data, scored.ctypes.data,
+                                           sc.ctypes.data, st.ctypes.data))
+        return {"common": common[:E], "scored": scored[:E], "score": sc[:E], "stats": st}
+
+    def query_dev(self, word, value, nq, common, scored, score, stats, exclude=None):
+        """rfe_bow_db_query_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self.ctx._chk(lib.rfe_bow_db_query_dev(self.h, a(word), a(value), int(nq), a(exclude), a(common), a(scored), a(score), a(stats)))
 
 
 def split_levels(flat, level_h, level_w):
@@ -855,6 +1007,33 @@ class Context:
                                                      a(depth2), a(has_mp2), a(n2), a(neighbour_valid), Nn, N2max, a(S), a(pairs), Kmax, a(code),
                                                      a(x3d), a(point_stereo), a(out_n), a(out_idx1), a(out_idx2), a(out_x3d), a(out_stereo),
                                                      a(matches), a(stats)))
+
+    def bow_transform(self, vocab, desc, levelsup=0):
+        """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint
+        descriptors (binarised by the call) or uint8 [N,D] bytes.  Returns a dict: word / node / weight [N] per feature, bow_word / bow_value
+        [bow_n], fv_node [fv_n], fv_offsets [fv_n + 1], fv_feat [fv_offsets[-1]]."""
+        d = np.asarray(desc)
+        assert d.dtype in (np.float32, np.uint8) and d.ndim == 2
+        d = np.ascontiguousarray(d)
+        N, n1 = d.shape[0], max(d.shape[0], 1)
+        f32 = d.ctypes.data if d.dtype == np.float32 else None
+        u8 = d.ctypes.data if d.dtype == np.uint8 else None
+        o = {"word": np.zeros((n1,), np.int32), "node": np.zeros((n1,), np.int32), "weight": np.zeros((n1,), np.float64),
+             "bow_n": np.zeros((1,), np.int32), "bow_word": np.zeros((n1,), np.int32), "bow_value": np.zeros((n1,), np.float64),
+             "fv_n": np.zeros((1,), np.int32), "fv_node": np.zeros((n1,), np.int32), "fv_offsets": np.zeros((n1 + 1,), np.int32),
+             "fv_feat": np.zeros((n1,), np.int32)}
+        self._chk(lib.rfe_bow_transform(self.h, vocab.h, f32, u8, N, int(levelsup), *[a.ctypes.data for a in o.values()]))
+        nb, nf = int(o["bow_n"][0]), int(o["fv_n"][0])
+        return {"word": o["word"][:N], "node": o["node"][:N], "weight": o["weight"][:N], "bow_word": o["bow_word"][:nb],
+                "bow_value": o["bow_value"][:nb], "fv_node": o["fv_node"][:nf], "fv_offsets": o["fv_offsets"][:nf + 1],
+                "fv_feat": o["fv_feat"][:int(o["fv_offsets"][nf])]}
+
+    def bow_transform_dev(self, vocab, N, levelsup, bow_n, bow_word, bow_value, fv_n, fv_node, fv_offsets, fv_feat, desc_f32=None, desc_u8=None,
+                          word=None, node=None, weight=None):
+        """rfe_bow_transform_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_bow_transform_dev(self.h, vocab.h, a(desc_f32), a(desc_u8), int(N), int(levelsup), a(word), a(node), a(weight), a(bow_n),
+                                            a(bow_word), a(bow_value), a(fv_n), a(fv_node), a(fv_offsets), a(fv_feat)))
 
     def distinctive_descriptors(self, desc, offsets):
         """MapPoint::ComputeDistinctiveDescriptors for many map points (MapPoint.cc:438-530)."""

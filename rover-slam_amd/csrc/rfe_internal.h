@@ -138,6 +138,7 @@ struct rfe_ctx {
     void* ws_ps = nullptr; size_t ws_ps_bytes = 0;   // rfe_search_by_projection*: grid, segment offsets, (index, distance) slots
     int ps_cap = 0;                                  // rfe_search_by_projection (host form): most slots any call has needed
     void* ws_tri = nullptr; size_t ws_tri_bytes = 0; // rfe_triangulate_neighbours*: per-slot results, claims, per-neighbour counts
+    void* ws_bow = nullptr; size_t ws_bow_bytes = 0; // rfe_bow_transform*: per-feature word / node / weight the caller did not ask for
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -374,5 +375,27 @@ void launch_tri_resolve(hipStream_t s, const int32_t* S, const uint8_t* nvalid, 
                         const float* wx3d, const uint8_t* wstereo, const int32_t* claim, int32_t* count, int32_t* code, float* x3d,
                         uint8_t* point_stereo, int32_t* out_n, int32_t* out_idx1, int32_t* out_idx2, float* out_x3d, uint8_t* out_stereo,
                         int32_t* matches, int32_t* stats);
+
+// bow.hip: Vocabulary::transform and the keyframe database's counts and L1 scores
+struct BowVocabDev {
+    const int32_t* child_off;   // [n_nodes + 1]
+    const int32_t* children;    // [n_nodes - 1]
+    const uint8_t* desc;        // [n_nodes, Dp], Dp = D rounded up to 16, zero-padded
+    const double* weight;       // [n_nodes]
+    const int32_t* word_id;     // [n_nodes]
+    int D, Dp, L;
+};
+constexpr int BOW_MAX_N = 4096;
+// per feature the descent: word / node / weight [N]
+void launch_bow_descend(hipStream_t s, const BowVocabDev& V, const float* desc_f32, const uint8_t* desc_u8, int N, int levelsup, int32_t* word,
+                        int32_t* node, double* weight);
+// the two sorted results from the per-feature arrays (1 <= N <= BOW_MAX_N); first_only: IDF / BINARY (addIfNotExist)
+void launch_bow_build(hipStream_t s, const int32_t* word, const int32_t* node, const double* weight, int N, bool first_only, int32_t* bow_n,
+                      int32_t* bow_word, double* bow_value, int32_t* fv_n, int32_t* fv_node, int32_t* fv_offsets, int32_t* fv_feat);
+void launch_bow_db_set_entry(hipStream_t s, long long* start, int32_t* len, int e, long long at, int n);
+// counts, then scores; stats [4] preset to 0
+void launch_bow_db_query(hipStream_t s, const int32_t* words, const double* values, const long long* start, const int32_t* len, int n_entries,
+                         const int32_t* q_word, const double* q_value, int nq, const uint8_t* exclude, int32_t* common, uint8_t* scored,
+                         double* score, int32_t* stats);
 
 }  // namespace rfe
