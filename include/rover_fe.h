@@ -622,6 +622,48 @@ int rfe_triangulate_neighbours(rfe_ctx* ctx, const rfe_tri_params* params, const
                                int32_t* code, float* x3d, uint8_t* point_stereo, int32_t* out_n, int32_t* out_idx1, int32_t* out_idx2,
                                float* out_x3d, uint8_t* out_stereo, int32_t* matches, int32_t* stats);
 
+/* ---- Optimizer::PoseOptimization on the device: motion-only Levenberg-Marquardt on matched points ----
+ * src/Optimizer.cc:55-401 over g2o's OptimizationAlgorithmLevenberg, one SE3 vertex and one unary edge per feature with a map point: B
+ * problems per call, one workgroup each, the four rounds, their LM iterations and the chi2 re-classification between them inside the
+ * kernel.  Double precision throughout; every sum over edges in one fixed order, so the outputs equal the restatement
+ * tests/pose_opt_ref.py bit for bit (6i states the arithmetic and its three departures from the reference's own build).
+ * Per problem, of N rows the first n (n_dev, clamped to 0..N; NULL = N) are features:
+ *   pose0 [7]      the frame's Tcw as qx qy qz qw tx ty tz (floats), the start of EVERY round
+ *   kpts_un [N,2]  mvKeysUn[i].pt;  octave [N] (NULL = 0; outside 0..nlevels-1 reads level 0);  uright [N] mvuRight (NULL = all mono; < 0:
+ *                  a mono edge, otherwise stereo);  xw [N,3] the map point's GetWorldPos();  has_mp [N] != 0: mvpMapPoints[i] != NULL
+ * params: fx, fy, cx, cy, bf = mbf; inv_level_sigma2 = mvInvLevelSigma2; iterations per round (0 = the reference's 10) and max_trials
+ *   (0 = g2o's 10).
+ * Outputs: pose [7] doubles, the estimate after the last round (pose0 widened when fewer than 3 edges: the reference returns before
+ *   SetPose); pose_f32 its plain cast, which a later call can take as pose0; outlier [N] = mvbOutlier, written where has_mp is set among
+ *   the n features and left alone elsewhere; chi2 [N] the float chi2 the last classification compared, written like outlier once a round
+ *   has run; trace [4,8] per round: LM iterations, trials, the final lambda, the final currentChi, inliers after the round, 0, 0, 0 (rows of
+ *   rounds not run are 0); stats [8]: 0 the return value nInitialCorrespondences - nBad (0 below three edges), 1 nInitialCorrespondences,
+ *   2 nBad, 3 rounds run, 4 LM iterations, 5 trials, 6 rejected trials, 7 flags: 1 a round ended on a rejected trial (its classification
+ *   used the errors of the rejected estimate, as the reference's does), 2 a solve found the system not positive, 4 a trial estimate or the
+ *   final pose was not finite.
+ * The _dev form is asynchronous on the ctx stream: no host synchronisation, no host read of device data, no workspace.  The host form
+ * stages its arrays (outlier and chi2 go in and out) and returns stats[0] of problem 0 (0 when B = 0).
+ * Refused (RFE_ERR_INVALID): B outside 0..64; N outside 0..4096; nlevels outside 1..RFE_MAX_LEVELS; a negative iterations[] or
+ *   max_trials; a NULL required pointer (params, pose0, pose, outlier, stats; kpts_un, xw, has_mp when B N > 0); host form only: a
+ *   non-finite fx, fy, cx, cy, bf, inv_level_sigma2 or pose0.  The per-feature arrays are not checked: a NaN world position runs through
+ *   as in the reference and raises flag 4.
+ * Out of scope: two-camera rigs (mpCamera2, EdgeSE3ProjectXYZOnlyPoseToBody), KannalaBrandt8 and the inertial variants
+ *   (PoseInertialOptimization*) -- the caller keeps the reference's function for those. */
+typedef struct rfe_pose_params {
+    float fx, fy, cx, cy, bf;
+    int32_t nlevels;                          /* 1..RFE_MAX_LEVELS */
+    float inv_level_sigma2[RFE_MAX_LEVELS];   /* mvInvLevelSigma2 */
+    int32_t iterations[4];                    /* 0 = the reference's 10 */
+    int32_t max_trials;                       /* 0 = g2o's 10 */
+} rfe_pose_params;
+int rfe_pose_optimization_dev(rfe_ctx* ctx, const rfe_pose_params* params, const float* pose0_dev, const float* kpts_un_dev,
+                              const int32_t* octave_dev, const float* uright_dev, const float* xw_dev, const uint8_t* has_mp_dev,
+                              const int32_t* n_dev, int B, int N, double* pose_dev, float* pose_f32_dev, uint8_t* outlier_dev, float* chi2_dev,
+                              double* trace_dev, int32_t* stats_dev);
+int rfe_pose_optimization(rfe_ctx* ctx, const rfe_pose_params* params, const float* pose0, const float* kpts_un, const int32_t* octave,
+                          const float* uright, const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose,
+                          float* pose_f32, uint8_t* outlier, float* chi2, double* trace, int32_t* stats);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates

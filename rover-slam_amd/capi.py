@@ -26,6 +26,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -221,6 +222,30 @@ _tri = [C.c_void_p, C.POINTER(TriParams), C.POINTER(TriView), _fp, _fp, _ip, _fp
         _u8p, C.c_int, C.c_int, _ip, _ip, C.c_int, _ip, _fp, _u8p, _ip, _ip, _ip, _fp, _u8p, _ip, _ip]
 lib.rfe_triangulate_neighbours.argtypes = _tri
 lib.rfe_triangulate_neighbours_dev.argtypes = _tri
+
+
+class PoseParams(C.Structure):
+    """include/rover_fe.h: rfe_pose_params -- intrinsics, mbf, mvInvLevelSigma2 and the LM schedule of one PoseOptimization call."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("nlevels", C.c_int32),
+                ("inv_level_sigma2", C.c_float * MAX_LEVELS), ("iterations", C.c_int32 * 4), ("max_trials", C.c_int32)]
+
+
+def pose_params(fx, fy, cx, cy, bf, inv_level_sigma2=(1.0,), iterations=(0, 0, 0, 0), max_trials=0, nlevels=None):
+    """rfe_pose_params from plain values (iterations / max_trials 0 = the reference's 10)"""
+    p = PoseParams()
+    p.fx, p.fy, p.cx, p.cy, p.bf = (float(v) for v in (fx, fy, cx, cy, bf))
+    p.nlevels = len(inv_level_sigma2) if nlevels is None else int(nlevels)
+    for l, v in enumerate(list(inv_level_sigma2)[:MAX_LEVELS]):
+        p.inv_level_sigma2[l] = float(v)
+    p.iterations[:] = [int(v) for v in iterations]
+    p.max_trials = int(max_trials)
+    return p
+
+
+POSE_OUTPUTS = ("pose_f32", "chi2", "trace")
+_pose = [C.c_void_p, C.POINTER(PoseParams), _fp, _fp, _ip, _fp, _fp, _u8p, _ip, C.c_int, C.c_int, _vp, _fp, _u8p, _fp, _vp, _ip]
+lib.rfe_pose_optimization.argtypes = _pose
+lib.rfe_pose_optimization_dev.argtypes = _pose
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
 BOW_MAX_N = 4096
@@ -1007,6 +1032,49 @@ class Context:
                                                      a(depth2), a(has_mp2), a(n2), a(neighbour_valid), Nn, N2max, a(S), a(pairs), Kmax, a(code),
                                                      a(x3d), a(point_stereo), a(out_n), a(out_idx1), a(out_idx2), a(out_x3d), a(out_stereo),
                                                      a(matches), a(stats)))
+
+    def pose_optimization(self, params, pose0, kpts_un, xw, has_mp, octave=None, uright=None, n=None, outlier=None, chi2=None,
+                          outputs=POSE_OUTPUTS):
+        """Optimizer::PoseOptimization for B problems (rfe_pose_optimization, host arrays; DESIGN.md 6i).  params: a PoseParams
+        (pose_params()); pose0 [B,7] qx qy qz qw tx ty tz; kpts_un [B,N,2], xw [B,N,3], has_mp / octave / uright [B,N], n [B] or None.
+        outlier / chi2: what those arrays hold where the call does not write (default 0).  outputs: the optional arrays to ask for (the
+        others are passed as NULL).  Returns a dict: pose [B,7] float64, outlier [B,N], stats [B,8], ret, and pose_f32 / chi2 / trace
+        [B,4,8] as asked."""
+        p0 = np.ascontiguousarray(pose0, np.float32).reshape(-1, 7)
+        B = p0.shape[0]
+        k = np.ascontiguousarray(kpts_un, np.float32)
+        N = k.size // (2 * B) if B else 0
+        k = k.reshape(B, N, 2)
+        f = B * N
+        flat = lambda a, dt, m: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
+        x, m = flat(xw, np.float32, f * 3), flat(has_mp, np.uint8, f)
+        o, u, nn = flat(octave, np.int32, f), flat(uright, np.float32, f), flat(n, np.int32, B)
+        assert len(x) == f * 3 and len(m) == f and (o is None or len(o) == f) and (u is None or len(u) == f) and (nn is None or len(nn) == B)
+        b1, f1 = max(B, 1), max(f, 1)
+        out = np.zeros((f1,), np.uint8)
+        c2 = np.zeros((f1,), np.float32)
+        if outlier is not None:
+            out[:f] = np.asarray(outlier, np.uint8).reshape(-1)
+        if chi2 is not None:
+            c2[:f] = np.asarray(chi2, np.float32).reshape(-1)
+        pose, pf = np.zeros((b1, 7), np.float64), np.zeros((b1, 7), np.float32)
+        tr, st = np.zeros((b1, 4, 8), np.float64), np.zeros((b1, 8), np.int32)
+        opt = {"pose_f32": pf, "chi2": c2, "trace": tr}
+        ret = self._chk(lib.rfe_pose_optimization(self.h, C.byref(params), _addr(p0), _addr(k), _addr(o), _addr(u), _addr(x), _addr(m), _addr(nn),
+                                                  B, N, pose.ctypes.data, pf.ctypes.data if "pose_f32" in outputs else None, out.ctypes.data,
+                                                  c2.ctypes.data if "chi2" in outputs else None, tr.ctypes.data if "trace" in outputs else None,
+                                                  st.ctypes.data))
+        r = {"pose": pose[:B], "outlier": out[:f].reshape(B, N), "stats": st[:B], "ret": ret}
+        r.update({key: (a[:f].reshape(B, N) if key == "chi2" else a[:B]) for key, a in opt.items() if key in outputs})
+        return r
+
+    def pose_optimization_dev(self, params, pose0, kpts_un, xw, has_mp, B, N, pose, outlier, stats, octave=None, uright=None, n=None,
+                              pose_f32=None, chi2=None, trace=None):
+        """rfe_pose_optimization_dev: params is a host structure, every array a DevBuf (or a raw device address / torch tensor);
+        asynchronous on the ctx stream."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        self._chk(lib.rfe_pose_optimization_dev(self.h, C.byref(params), a(pose0), a(kpts_un), a(octave), a(uright), a(xw), a(has_mp), a(n),
+                                                int(B), int(N), a(pose), a(pose_f32), a(outlier), a(chi2), a(trace), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

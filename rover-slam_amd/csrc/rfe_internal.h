@@ -398,4 +398,10 @@ void launch_bow_db_query(hipStream_t s, const int32_t* words, const double* valu
                          const int32_t* q_word, const double* q_value, int nq, const uint8_t* exclude, int32_t* common, uint8_t* scored,
                          double* score, int32_t* stats);
 
+// pose_opt.hip: Optimizer::PoseOptimization, one workgroup per problem.  octave / uright / n / pose_f32 / chi2 / trace may
+// be NULL; needs no workspace and presets nothing
+void launch_pose_opt(hipStream_t s, const rfe_pose_params& P, const float* pose0, const float* kpts, const int32_t* octave, const float* uright,
+                     const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose, float* pose_f32, uint8_t* outlier,
+                     float* chi2, double* trace, int32_t* stats);
+
 }  // namespace rfe
