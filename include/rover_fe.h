@@ -668,6 +668,14 @@ int rfe_pose_optimization(rfe_ctx* ctx, const rfe_pose_params* params, const flo
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates
  * (src/KeyFrameDatabase.cc:660-740, :1045-1100) up to and including the L1 scores.
+ * The reference's own bodies behind this contract, as oracle/ref_classic/build_ref.py cuts or checks them (tests/test_ref_bow.py):
+ *   Thirdparty/DBoW3/src/Vocabulary.cpp: the constructor :10-16, createScoringObject :48-80, the destructor :112-115, transform(features,
+ *     v, fv, levelsup) :752-818, the per-feature overload with nid :836-874, toStream :1180-1257, fromStream :1335-1406;
+ *   Thirdparty/DBoW3/src/DescManip.cpp: distance :92-130, toStream :249-258, fromStream :260-267;
+ *   Thirdparty/DBoW3/src/BowVector.cpp: addWeight :34-46, addIfNotExist :50-58, normalize :62-84;
+ *   Thirdparty/DBoW3/src/FeatureVector.cpp: addFeature :31-45;  Thirdparty/DBoW3/src/ScoringObject.cpp: L1Scoring::score :23-68;
+ *   src/KeyFrameDatabase.cc: add :44-54, erase :65-85, the counting, gating and scoring of DetectNBestCandidates_sp :661-739 and of
+ *     DetectRelocalizationCandidates :1047-1099.
  *
  * A vocabulary is a tree in flat host arrays (rfe_bow_vocab_desc): node 0 is the root, children [child_offsets[i], child_offsets[i + 1])
  * are node i's children in their stored order, desc [n_nodes, D] u8 the node descriptors (row 0 is ignored), weight [n_nodes] f64,

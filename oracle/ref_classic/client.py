@@ -1,4 +1,8 @@
-"""Python side of oracle/_ref/ref_classic (built by build_ref.py): one child process per call, raw arrays through two temporary files.
+"""Python side of oracle/_ref/ref_classic and oracle/_ref/ref_bow (built by build_ref.py): one child process per call, raw arrays through
+two temporary files.  ref_classic runs the classic stages' bodies (stereo, geometry, distance, distinctive, normkp, binarize); ref_bow
+is a second stand-alone program (ref_bow_main.cc, no Python in the process) around DBoW3's and KeyFrameDatabase's own bodies:
+voc_dump / voc_write (Vocabulary::fromStream, toStream), transform (Vocabulary::transform), score (L1Scoring::score), kfdb
+(KeyFrameDatabase::add / erase and the fronts of DetectNBestCandidates_sp / DetectRelocalizationCandidates).
 Test and fixture-generation infrastructure only; nothing here runs on a GPU machine."""
 import os
 import struct
@@ -9,7 +13,7 @@ import numpy as np
 
 from . import build_ref
 
-_CODES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2}
+_CODES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float32): 2, np.dtype(np.float64): 3}
 _DTYPES = {v: k for k, v in _CODES.items()}
 
 
@@ -17,13 +21,17 @@ class RefError(RuntimeError):
     pass
 
 
-def binary(sanitized=False):
-    return os.path.join(build_ref.OUT, "ref_classic_san" if sanitized else "ref_classic")
+def binary(sanitized=False, program="ref_classic"):
+    return os.path.join(build_ref.OUT, program + ("_san" if sanitized else ""))
 
 
-def usable(sanitized=False):
+def usable(sanitized=False, program="ref_classic"):
     """the harness exists AND the checkout it was cut from is present (a leftover build without its source is not trusted)"""
-    return os.path.isfile(binary(sanitized)) and build_ref.available()
+    return os.path.isfile(binary(sanitized, program)) and build_ref.available()
+
+
+def usable_bow(sanitized=False):
+    return usable(sanitized, "ref_bow")
 
 
 def _write(path, arrays):
@@ -48,8 +56,8 @@ def _read(path):
     return out
 
 
-def run(op, arrays, sanitized=False, timeout=600):
-    exe = binary(sanitized)
+def run(op, arrays, sanitized=False, timeout=600, program="ref_classic"):
+    exe = binary(sanitized, program)
     if not os.path.isfile(exe):
         raise RefError(f"{exe} is not built (python oracle/ref_classic/build_ref.py)")
     with tempfile.TemporaryDirectory() as d:
@@ -57,7 +65,7 @@ def run(op, arrays, sanitized=False, timeout=600):
         _write(fin, arrays)
         r = subprocess.run([exe, op, fin, fout], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout)
         if r.returncode != 0:
-            raise RefError(f"ref_classic {op} ended with {r.returncode}: {r.stderr.decode(errors='replace')[-2000:]}")
+            raise RefError(f"{program} {op} ended with {r.returncode}: {r.stderr.decode(errors='replace')[-2000:]}")
         return _read(fout)
 
 
@@ -101,3 +109,74 @@ def normalize_keypoints(kpts, h, w, sanitized=False):
 def binarize(desc, sanitized=False):
     d = _f(desc, (-1, 256))
     return run("binarize", [d], sanitized)[0].reshape(-1, 256)
+
+
+# ---------------------------------------------------------------- ref_bow: DBoW3 and KeyFrameDatabase
+def _i(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+def _stream(data):
+    return np.frombuffer(bytes(data), np.uint8)
+
+
+def voc_dump(stream, sanitized=False):
+    """Vocabulary::fromStream of the bytes, then the tree as the reference holds it: a dict with k, L, scoring, weighting, n_nodes, n_words,
+    D and parent, child_offsets, children (in m_nodes[i].children's order), desc [n_nodes, D] (row 0 zeros), weight f64, word_id (-1 for a
+    node with children), words [n_words] = the node of every word"""
+    hdr, parent, off, children, cols, desc, weight, word_id, words = run("voc_dump", [_stream(stream)], sanitized, program="ref_bow")
+    k, L, scoring, weighting, n, nw = (int(v) for v in hdr)
+    D = int(cols[1]) if n > 1 else 0
+    if not (cols[0] == 0 and (cols[1:] == D).all()):
+        raise RefError("voc_dump: descriptors of different widths")
+    full = np.zeros((n, D), np.uint8)
+    full[1:] = desc.reshape(n - 1, D)
+    return {"k": k, "L": L, "scoring": scoring, "weighting": weighting, "n_nodes": n, "n_words": nw, "D": D, "parent": parent,
+            "child_offsets": off, "children": children, "desc": full, "weight": weight, "word_id": word_id, "words": words}
+
+
+def voc_write(stream, compressed=False, sanitized=False):
+    """fromStream, then the bytes Vocabulary::toStream(out, compressed) writes"""
+    return run("voc_write", [_stream(stream), np.array([int(compressed)], np.int32)], sanitized, program="ref_bow")[0].tobytes()
+
+
+BOW_KEYS = ("word", "nid", "weight", "bow_word", "bow_value", "fv_node", "fv_offsets", "fv_feat")
+
+
+def transform(stream, feats, levelsup, sanitized=False):
+    """Vocabulary::transform(features, v, fv, levelsup) on uint8 [N,D] features; a dict of BOW_KEYS.  nid == -1 marks a descent that never
+    wrote *nid: the FeatureVector of such a case is filed under an uninitialised node id and must not be used."""
+    f = np.ascontiguousarray(feats, np.uint8)
+    out = run("transform", [_stream(stream), f.reshape(-1), np.array([f.shape[0], f.shape[1], levelsup], np.int32)], sanitized, program="ref_bow")
+    return dict(zip(BOW_KEYS, out))
+
+
+def score(w1, v1, w2, v2, sanitized=False):
+    """L1Scoring::score of two BowVectors (ascending words), as float64"""
+    f = lambda a: np.ascontiguousarray(a, np.float64).reshape(-1)   # noqa: E731
+    return run("score", [_i(w1), f(v1), _i(w2), f(v2)], sanitized, program="ref_bow")[0][0]
+
+
+KFDB_ADD, KFDB_ERASE, KFDB_QUERY_SP, KFDB_QUERY_RELOC = 0, 1, 2, 3
+KFDB_KEYS = ("sharing", "words", "scored", "score", "score64", "stats")
+
+
+def kfdb(n_words, ops, bows, connected, sanitized=False):
+    """A script over KeyFrameDatabase: ops = [(KFDB_*, arg)], bows = [(word, value)], connected = one list of keyframe indices per query.
+    Returns a dict of KFDB_KEYS, per query x keyframe (E = number of adds): sharing (in lKFsSharingWords), words (the common-word counter as
+    the reference leaves it; -1 untouched), scored, score (the stored float; -9.5 not scored), score64 (the double it was made from);
+    stats [n_queries, 5] = returned early, maxCommonWords, minCommonWords, len(lKFsSharingWords), len(lScoreAndMatch)."""
+    ops = np.ascontiguousarray(ops, np.int32).reshape(-1, 2)
+    boff = np.zeros((len(bows) + 1,), np.int32); boff[1:] = np.cumsum([len(w) for w, _ in bows])
+    bw = np.concatenate([_i(w) for w, _ in bows]) if bows else np.zeros((0,), np.int32)
+    bx = np.concatenate([np.ascontiguousarray(x, np.float64).reshape(-1) for _, x in bows]) if bows else np.zeros((0,), np.float64)
+    coff = np.zeros((len(connected) + 1,), np.int32); coff[1:] = np.cumsum([len(c) for c in connected])
+    cc = np.concatenate([_i(c) for c in connected]) if connected else np.zeros((0,), np.int32)
+    out = run("kfdb", [np.array([n_words], np.int32), ops.reshape(-1), boff, bw.astype(np.int32), bx, coff, cc.astype(np.int32)], sanitized,
+              program="ref_bow")
+    E, Q = int((ops[:, 0] == KFDB_ADD).sum()), len(connected)
+    r = dict(zip(KFDB_KEYS, out))
+    for k in KFDB_KEYS[:-1]:
+        r[k] = r[k].reshape(Q, E)
+    r["stats"] = r["stats"].reshape(Q, 5)
+    return r

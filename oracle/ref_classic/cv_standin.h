@@ -1,8 +1,10 @@
 // Minimal stand-in for the few OpenCV names the classic Rover-SLAM function bodies use (oracle/ref_classic/build_ref.py).
 // Written for this project; no OpenCV text.  Only what those bodies touch is here: a reference-counted 2-D Mat of u8 / f32 with
-// views, KeyPoint / Point2f / Size, norm (L1 / L2), threshold (THRESH_BINARY) and cvRound.
+// views, KeyPoint / Point2f / Size, norm (L1 / L2), threshold (THRESH_BINARY) and cvRound; for DBoW3 (ref_bow_main.cc) also
+// Mat::create / ptr<T> / isContinuous and the NAMES FileStorage / FileNode, declared only (Vocabulary.h mentions them).
 #ifndef RFE_REF_CV_STANDIN_H
 #define RFE_REF_CV_STANDIN_H
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -103,11 +105,11 @@ public:
         return m;
     }
     const uchar* ptr(int y) const { return data + (size_t)y * step; }
-
-private:
-    int type_;
-    std::shared_ptr<std::vector<uchar> > own_;
-    static size_t esz(int type) { return type == CV_32F ? 4 : 1; }
+    // typed row pointer; as in OpenCV the type is the caller's claim (DescManip::distance reads CV_8U rows as uint64_t)
+    template <typename T> T* ptr(int y = 0) { rowchk(y); return (T*)(data + (size_t)y * step); }
+    template <typename T> const T* ptr(int y = 0) const { rowchk(y); return (const T*)(data + (size_t)y * step); }
+    bool isContinuous() const { return rows <= 1 || step == (size_t)cols * elemSize(); }
+    // a fresh zeroed buffer of the given shape (OpenCV keeps the old one when the shape is unchanged and does not zero)
     void create(int r, int c, int type) {
         if (type != CV_8U && type != CV_32F) throw Exception("Mat: unsupported type");
         rows = r; cols = c; type_ = type; tag = -1;
@@ -115,10 +117,19 @@ private:
         own_ = std::make_shared<std::vector<uchar> >((size_t)r * step + 1, (uchar)0);
         data = own_->data();
     }
+
+private:
+    int type_;
+    std::shared_ptr<std::vector<uchar> > own_;
+    static size_t esz(int type) { return type == CV_32F ? 4 : 1; }
+    void rowchk(int y) const { if (y < 0 || (y >= rows && !(y == 0 && rows == 0))) throw Exception("Mat::ptr out of range"); }
     template <typename T> void chk(int y, int x) const {
         if (sizeof(T) != elemSize() || y < 0 || y >= rows || x < 0 || x >= cols) throw Exception("Mat::at out of range");
     }
 };
+
+class FileStorage;   // named by Vocabulary.h's YAML save / load declarations; nothing here defines or calls them
+class FileNode;
 
 enum { NORM_L1 = 2, NORM_L2 = 4 };
 enum { THRESH_BINARY = 0 };

@@ -2,6 +2,8 @@
 // (oracle/ref_classic/build_ref.py).  Written for this project.  Member names and TYPES follow the reference's headers
 // (include/Frame.h, include/MapPoint.h, include/Matchers/SPmatcher.h, include/Extractors/SPextractor.h): the arithmetic of the
 // bodies depends on them, e.g. `double scaleFactor` makes mvScaleFactor[i-1]*scaleFactor a double product.
+// With RFE_REF_BOW (ref_bow_main.cc) also the members KeyFrameDatabase's BoW bodies touch (include/KeyFrame.h, include/Frame.h,
+// include/KeyFrameDatabase.h), over DBoW3's OWN headers, which build_ref.py puts on the include path from the checkout.
 #ifndef RFE_REF_CLASSES_H
 #define RFE_REF_CLASSES_H
 #include <algorithm>
@@ -13,6 +15,12 @@
 #include <tuple>
 #include <vector>
 #include "cv_standin.h"
+#ifdef RFE_REF_BOW
+#include <list>
+#include <set>
+#include "BowVector.h"
+#include "Vocabulary.h"
+#endif
 
 namespace ORB_SLAM3 {
 using namespace std;   // the reference's sources see std through their headers
@@ -39,6 +47,10 @@ public:
     vector<float> mvScaleFactors;
     vector<float> mvInvScaleFactors;
     cv::Mat imgLeft, imgRight;
+#ifdef RFE_REF_BOW
+    DBoW3::BowVector mBow3Vec;
+    long unsigned int mnId;
+#endif
 };
 
 class KeyFrame {
@@ -47,6 +59,18 @@ public:
     bool isBad() { return bad; }
     cv::Mat mDescriptors;
     bool bad;
+#ifdef RFE_REF_BOW
+    std::set<KeyFrame*> GetConnectedKeyFrames() { return connected; }
+    std::set<KeyFrame*> connected;     // the stand-in's own: what GetConnectedKeyFrames returns
+    long unsigned int mnId;
+    long unsigned int mnRelocQuery;
+    int mnRelocWords;
+    float mRelocScore;
+    long unsigned int mnPlaceRecognitionQuery;
+    int mnPlaceRecognitionWords;
+    float mPlaceRecognitionScore;
+    DBoW3::BowVector mBow3Vec;
+#endif
 };
 
 class MapPoint {
@@ -78,6 +102,34 @@ public:
     std::vector<float> mvLevelSigma2;
     std::vector<float> mvInvLevelSigma2;
 };
+
+#ifdef RFE_REF_BOW
+typedef DBoW3::Vocabulary SPVocabulary;
+class Map;
+
+class KeyFrameDatabase {
+public:
+    // the reference sizes the inverted file by voc.size(); the scripts bring their own word range
+    KeyFrameDatabase(const SPVocabulary& voc, size_t n_words) : mpVoc(&voc) { mvInvertedFile.resize(n_words); }
+    void add(KeyFrame* pKF);
+    void erase(KeyFrame* pKF);
+    // what the two fronts leave behind when the cut range has run to its end (early == true: it returned inside the range)
+    struct Front {
+        bool early;
+        int maxCommonWords, minCommonWords;
+        std::list<KeyFrame*> sharing;
+        std::list<std::pair<float, KeyFrame*> > scored;
+        Front() : early(true), maxCommonWords(0), minCommonWords(0) {}
+    };
+    // body = DetectNBestCandidates_sp from its first declaration to the end of the scoring loop
+    void FrontNBest_sp(KeyFrame* pKF, Front& front);
+    // body = DetectRelocalizationCandidates from its first declaration to the end of the scoring loop
+    std::vector<KeyFrame*> FrontReloc(Frame* F, Front& front);
+    const SPVocabulary* mpVoc;
+    std::vector<list<KeyFrame*> > mvInvertedFile;
+    std::mutex mMutex;
+};
+#endif
 
 }  // namespace ORB_SLAM3
 #endif

@@ -1,13 +1,14 @@
 // Command-line harness around the reference's OWN function bodies (the *.inc files build_ref.py cuts out of the Rover-SLAM checkout;
 // they are build products under oracle/_ref/ and never committed).  Everything in this file is the project's: argument plumbing only.
 //   ref_classic <op> <in> <out>       op: stereo | geometry | distance | distinctive | normkp | binarize
-// <in> / <out>: int32 count, then per array { int32 dtype (0 u8, 1 i32, 2 f32), int64 elements, data }.
+// <in> / <out>: the array files of ref_io.h.
 // A case outside the reference's defined behaviour ends THIS process (exception, library assertion, sanitizer), not the caller.
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include "ref_classes.h"
+#include "ref_io.h"
 
 // ---- the reference's text ---------------------------------------------------------------------------------------------------
 namespace ORB_SLAM3 {
@@ -35,56 +36,6 @@ cv::Size SPextractor::LevelSize(cv::Mat image, int level) {
 
 // ---- plumbing ---------------------------------------------------------------------------------------------------------------
 namespace {
-struct Arr {
-    int32_t dtype;
-    std::vector<unsigned char> bytes;
-    size_t n() const { return bytes.size() / (dtype == 0 ? 1 : 4); }
-    const uint8_t* u8() const { need(0); return bytes.data(); }
-    const int32_t* i32() const { need(1); return (const int32_t*)bytes.data(); }
-    const float* f32() const { need(2); return (const float*)bytes.data(); }
-    void need(int t) const { if (dtype != t) throw std::runtime_error("array dtype mismatch"); }
-};
-
-std::vector<Arr> read_all(const char* path) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-    int32_t count = 0;
-    if (std::fread(&count, 4, 1, f) != 1 || count < 0 || count > 64) throw std::runtime_error("bad header");
-    std::vector<Arr> out((size_t)count);
-    for (auto& a : out) {
-        int64_t n = 0;
-        if (std::fread(&a.dtype, 4, 1, f) != 1 || std::fread(&n, 8, 1, f) != 1 || a.dtype < 0 || a.dtype > 2 || n < 0)
-            throw std::runtime_error("bad array header");
-        a.bytes.resize((size_t)n * (a.dtype == 0 ? 1 : 4));
-        if (!a.bytes.empty() && std::fread(a.bytes.data(), 1, a.bytes.size(), f) != a.bytes.size()) throw std::runtime_error("short read");
-    }
-    std::fclose(f);
-    return out;
-}
-
-struct Writer {
-    std::vector<Arr> arrs;
-    template <typename T> void add(int dtype, const T* p, size_t n) {
-        Arr a; a.dtype = dtype;
-        a.bytes.assign((const unsigned char*)p, (const unsigned char*)p + n * sizeof(T));
-        arrs.push_back(a);
-    }
-    void write(const char* path) {
-        FILE* f = std::fopen(path, "wb");
-        if (!f) throw std::runtime_error(std::string("cannot write ") + path);
-        int32_t count = (int32_t)arrs.size();
-        std::fwrite(&count, 4, 1, f);
-        for (auto& a : arrs) {
-            int64_t n = (int64_t)a.n();
-            std::fwrite(&a.dtype, 4, 1, f); std::fwrite(&n, 8, 1, f);
-            if (!a.bytes.empty()) std::fwrite(a.bytes.data(), 1, a.bytes.size(), f);
-        }
-        if (std::fclose(f) != 0) throw std::runtime_error("write failed");
-    }
-};
-
-void want(bool ok, const char* what) { if (!ok) throw std::runtime_error(what); }
-
 // in: pi [H, W, nlevels, N, Nr], pf [mb, mbf, scale_factor], imgL, imgR u8 [H*W] (level 0), kL f32 [N*2], octL i32 [N], kR, octR,
 // dL f32 [N*256], dR.  out: mvuRight f32 [N], mvDepth f32 [N]
 void op_stereo(const std::vector<Arr>& in, Writer& out) {

@@ -4,7 +4,10 @@ checkout) as fixtures tests/golden/ref_*.npz: inputs, the reference's outputs, a
 Fixed seeds, CPU only.  Keypoints and descriptors come from the CPU oracle (pyramid levels through tests/pyramid_ref.py); descriptors of
 extracted cases are rounded to int8 codes * 2**-7 BEFORE the reference sees them, so the stored codes are the exact inputs.
 
-    python tools/gen_ref_golden.py [--report profiles/ref_classic_census.md]
+Place recognition (--only bow): tests/golden/ref_bow_*.npz from oracle/_ref/ref_bow, DBoW3's and KeyFrameDatabase's own bodies; inputs
+from tests/ref_bow_cases.py.  --check records into a temporary directory instead and compares the bytes with the committed files.
+
+    python tools/gen_ref_golden.py [--report profiles/ref_classic_census.md] [--only bow] [--check]
 """
 import argparse
 import os
@@ -17,6 +20,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import pyramid_ref as PR                      # noqa: E402
+import bow_ref as BR                          # noqa: E402
+import ref_bow_cases as BC                    # noqa: E402
 import ref_classic_cases as RC                # noqa: E402
 import stereo_pyramid_ref as SR               # noqa: E402
 from oracle import oracle as O                # noqa: E402
@@ -159,12 +164,82 @@ def gen_small(sanitized):
     print("distance / normkp / binarize recorded")
 
 
+def gen_bow(sanitized):
+    """vocabularies as DBoW3's toStream wrote them, its dump of them, Vocabulary::transform on every case, the database scripts"""
+    for name in BC.VOCABS:
+        v, pools, cases = BC.source(name)
+        stream = R.voc_write(BR.stream_bytes(v), False, sanitized=sanitized)          # our writer -> fromStream -> DBoW3's toStream
+        d = R.voc_dump(stream, sanitized=sanitized)
+        arrays = {"stream": np.frombuffer(stream, np.uint8), "pools": np.array(list(pools)),
+                  "dump_hdr": np.array([d[k] for k in ("k", "L", "scoring", "weighting", "n_nodes", "n_words", "D")], np.int32),
+                  "dump_words": d["words"], "cases": np.array([(list(pools).index(p), n, u) for p, n, u in cases], np.int32)}
+        if name == "oneword":                                                          # the smallest tree: also as a compressed stream
+            arrays["stream_compressed"] = np.frombuffer(R.voc_write(stream, True, sanitized=sanitized), np.uint8)
+        for k in BR.VOCAB_ARRAYS:
+            arrays["dump_" + k] = d[k]
+        for p, a in pools.items():
+            arrays["pool_" + p] = a
+        census, fv_ok = [], []
+        dv = BC.dump_dict(arrays)
+        for i, (p, n, u) in enumerate(cases):
+            r = R.transform(stream, pools[p][:n], u, sanitized=sanitized)
+            ok = bool((r["nid"] >= 0).all())
+            fv_ok.append(ok)
+            for k in BC.BOW_OUT:
+                if ok or not k.startswith("fv_"):                                      # an unwritten *nid: the FeatureVector is garbage
+                    arrays[f"c{i}_{k}"] = r[k]
+            census.append(BC.transform_census(dv, pools[p][:n], u))
+        arrays["fv_recorded"] = np.array(fv_ok, np.uint8)
+        arrays["census_keys"] = np.array(BC.TRANSFORM_CENSUS)
+        arrays["census"] = np.array(census, np.int64)
+        files = RC.save("bow_" + name, arrays)
+        print(f"bow_{name}: {d['n_nodes']} nodes, {len(cases)} cases, census {np.sum(census, axis=0).tolist()}, "
+              f"{sum(os.path.getsize(f) for f in files)} bytes in {len(files)} file(s)")
+    arrays = {"scripts": np.array([s["name"] for s in BC.kfdb_scripts()]), "census_keys": np.array(BC.KFDB_CENSUS)}
+    for s in BC.kfdb_scripts():
+        r = R.kfdb(s["n_words"], s["ops"], s["bows"], s["connected"], sanitized=sanitized)
+        for k, a in BC.pack_script(s).items():
+            arrays[f"{s['name']}_{k}"] = a
+        for k in BC.KFDB_OUT:
+            arrays[f"{s['name']}_{k}"] = r[k]
+        arrays[f"{s['name']}_census"] = np.array(BC.kfdb_census(s), np.int64)
+        print(f"bow_kfdb {s['name']}: {int(r['sharing'].shape[1])} entries, {len(s['connected'])} queries, census {arrays[s['name'] + '_census'].tolist()}")
+    # L1Scoring::score on its own: pairs of the scripts' BowVectors, the score as float64
+    s = BC.script_grow()
+    pairs = [(600, e) for e in range(0, 600, 37)] + [(601, 601), (602, 5), (603, 600), (601, 600)]
+    arrays["score_pairs"] = np.array(pairs, np.int32)
+    arrays["score_ref"] = np.array([R.score(*s["bows"][a], *s["bows"][b], sanitized=sanitized) for a, b in pairs], np.float64)
+    files = RC.save("bow_kfdb", arrays)
+    print(f"bow_kfdb: {sum(os.path.getsize(f) for f in files)} bytes in {len(files)} file(s)")
+
+
+def check_bow(sanitized):
+    """regenerate into a temporary directory: every ref_bow_* file must come out with the committed bytes"""
+    import filecmp
+    import glob
+    import tempfile
+    kept = RC.GOLDEN
+    with tempfile.TemporaryDirectory() as d:
+        RC.GOLDEN = d
+        try:
+            gen_bow(sanitized)
+        finally:
+            RC.GOLDEN = kept
+        new = sorted(os.path.basename(f) for f in glob.glob(os.path.join(d, "ref_bow_*.npz")))
+        old = sorted(os.path.basename(f) for f in glob.glob(os.path.join(kept, "ref_bow_*.npz")))
+        bad = [f for f in new if f not in old or not filecmp.cmp(os.path.join(d, f), os.path.join(kept, f), shallow=False)]
+        if new != old or bad:
+            sys.exit(f"--check: the regenerated fixtures differ: {bad or (new, old)}")
+    print(f"--check: {len(new)} ref_bow_* files regenerated with identical bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--report", default=None, help="write the census tables (markdown) here")
-    ap.add_argument("--only", default="", help="comma-separated subset of: stereo,geometry,distinctive,small")
+    ap.add_argument("--only", default="", help="comma-separated subset of: stereo,geometry,distinctive,small,bow")
+    ap.add_argument("--check", action="store_true", help="bow: regenerate into a temporary directory and compare the bytes")
     args = ap.parse_args()
-    if not R.usable():
+    if not R.usable() or not R.usable_bow():
         sys.exit("oracle/_ref/ref_classic is not built (python oracle/ref_classic/build_ref.py needs the Rover-SLAM checkout)")
     sanitized = R.usable(sanitized=True)
     try:
@@ -174,6 +249,10 @@ def main():
     print(f"reference harness: {'AddressSanitizer + UBSan' if sanitized else 'plain'} build")
     only = set(filter(None, args.only.split(",")))
     report, notes = [], []
+    if args.check:
+        return check_bow(sanitized and R.usable_bow(sanitized=True))
+    if not only or "bow" in only:
+        gen_bow(sanitized and R.usable_bow(sanitized=True))
     if not only or "geometry" in only:
         gen_geometry(sanitized, notes)
     if not only or "distinctive" in only:
