@@ -664,6 +664,55 @@ int rfe_pose_optimization(rfe_ctx* ctx, const rfe_pose_params* params, const flo
                           const float* uright, const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose,
                           float* pose_f32, uint8_t* outlier, float* chi2, double* trace, int32_t* stats);
 
+/* ---- Sim3Solver on the device: every RANSAC hypothesis of a loop-closing candidate in one call ----
+ * src/Sim3Solver.cc:61-483 as LoopClosing::DetectCommonRegionsFromBoW drives it (SetRansacParameters, then iterate(20, ..) until bConverge
+ * or bNoMore): B problems per call, each with its own correspondences, poses, cameras, min_inliers and iteration count.  The front
+ * (:61-121) takes both map points of every correspondence into their camera frames and images, one wave per hypothesis runs ComputeSim3
+ * (:319-420, Horn's closed form) on its triple and counts the inliers of CheckInliers (:423-447), and one workgroup per problem makes the
+ * reference's sequential choice: the FIRST hypothesis h < its whose count exceeds min_inliers (bConverge), otherwise the LAST hypothesis
+ * that reaches the maximum count (bNoMore).  fp32, one rounding per operation, sums left to right; the outputs equal the restatement
+ * tests/sim3_solver_ref.py bit for bit (6j states the arithmetic and its departures from the reference's own build: a fixed-schedule
+ * Jacobi for Eigen's EigenSolver, the rotation straight from the unit quaternion, fixed evaluation orders, the random stream).
+ * params [B] is a HOST array in both forms.  Per problem, of N rows the first n (clamped to 0..N) are correspondences and of H draws the
+ * first its are used:
+ *   params[b]      rcw1 / rcw2 row-major and tcw1 / tcw2: pKF1's and pKF2's pose; fx fy cx cy of each Pinhole camera; fix_scale;
+ *                  min_inliers (mRansacMinInliers); its = mRansacMaxIts AFTER SetRansacParameters (rfe_sim3_ransac_iterations); n
+ *   xw1, xw2 [N,3] GetWorldPos() of pMP1 and pMP2;  sigma2_1, sigma2_2 [N] mvLevelSigma2[octave] of the keypoint in pKF1 and in pKFm: the
+ *                  bound of a side is (float)(uint64)(9.210 * (double)sigma2), mvnMaxError being a vector<size_t>
+ *   draws [H,3]    the three RandomInt(0, size - 1) results of every iteration, resolved through the reference's swap-with-back list; a
+ *                  draw outside 0..n-1-k is clamped and raises flag 8
+ * Outputs per problem: T12 [16] row-major, R [9], t [3], s: mBestT12 / mBestRotation / mBestTranslation / mBestScale (the identity, 0 and 1
+ *   when no hypothesis ran; NaN where the chosen triple's quaternion has a zero vector part, as the reference's 0 / 0 at :375 leaves them);
+ *   inliers [N] the winner's mvbInliersi (all 0 without convergence, as vbInliers is; index it through mvnIndices1 yourself);
+ *   best_inliers [N] mvbBestInliers; counts [H] mnInliersi of EVERY h < its (those behind the winner the reference would not have run);
+ *   hyps [H,32] per hypothesis T12 [16], R [9], t [3], s, flags (int32 bits: 1 NaN rotation, 8 a clamped draw), 0, 0;
+ *   stats [8]: 0 bConverge, 1 nInliers, 2 mnBestInliers, 3 the chosen hypothesis (-1: none ran), 4 mnIterations, 5 bNoMore, 6 hypotheses
+ *   with a NaN rotation among the first mnIterations, 7 flags: 1 n < min_inliers, 2 n < 3 (the reference would draw from an empty list:
+ *   handled as 1), 8 a clamped draw among the first its.  Rows behind n, entries behind its and rows of hyps behind its are left alone.
+ * The _dev form is asynchronous on the ctx stream: no host synchronisation, no host read of device data, no allocation once the ctx's
+ * workspace has the call's size; one front launch per 16 problems, one hypothesis launch, one selection launch.  The host form stages its
+ * arrays and returns stats[0] of problem 0 (0 when B = 0).  inliers, best_inliers, counts, hyps, R, t and s may be NULL.
+ * Refused (RFE_ERR_INVALID): B outside 0..64; N outside 0..4096; H outside 1..1024; its outside 1..H; min_inliers < 0; a NULL required
+ *   pointer (params, draws, T12, stats; xw1, xw2, sigma2_1, sigma2_2 when B N > 0); host form only: a non-finite pose or intrinsic, a
+ *   negative or non-finite sigma2 among the n rows.  Positions are not checked: a NaN runs through as an outlier.
+ * rfe_sim3_ransac_iterations is SetRansacParameters' arithmetic (:137-147) on the host's libm: epsilon = (float)min_inliers / n, 1 when
+ *   min_inliers == n, otherwise ceil(log(1 - probability) / log(1 - pow(epsilon, 3))), a quotient that is NaN or outside int converting
+ *   to INT_MIN as on x86-64, then max(1, min(., max_its)).
+ * Out of scope: KannalaBrandt8 cameras, OptimizeSim3, the descriptor matching in front, a device-side random generator. */
+typedef struct rfe_sim3_solver_params {
+    float rcw1[9], tcw1[3], rcw2[9], tcw2[3];   /* row-major */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    int32_t fix_scale, min_inliers, its, n;
+} rfe_sim3_solver_params;
+int rfe_sim3_ransac_dev(rfe_ctx* ctx, const rfe_sim3_solver_params* params, const float* xw1_dev, const float* xw2_dev,
+                        const float* sigma2_1_dev, const float* sigma2_2_dev, const int32_t* draws_dev, int B, int N, int H, float* T12_dev,
+                        float* R_dev, float* t_dev, float* s_dev, uint8_t* inliers_dev, uint8_t* best_inliers_dev, int32_t* counts_dev,
+                        float* hyps_dev, int32_t* stats_dev);
+int rfe_sim3_ransac(rfe_ctx* ctx, const rfe_sim3_solver_params* params, const float* xw1, const float* xw2, const float* sigma2_1,
+                    const float* sigma2_2, const int32_t* draws, int B, int N, int H, float* T12, float* R, float* t, float* s,
+                    uint8_t* inliers, uint8_t* best_inliers, int32_t* counts, float* hyps, int32_t* stats);
+int rfe_sim3_ransac_iterations(double probability, int min_inliers, int n, int max_its);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates

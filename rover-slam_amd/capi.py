@@ -26,7 +26,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -246,6 +246,39 @@ POSE_OUTPUTS = ("pose_f32", "chi2", "trace")
 _pose = [C.c_void_p, C.POINTER(PoseParams), _fp, _fp, _ip, _fp, _fp, _u8p, _ip, C.c_int, C.c_int, _vp, _fp, _u8p, _fp, _vp, _ip]
 lib.rfe_pose_optimization.argtypes = _pose
 lib.rfe_pose_optimization_dev.argtypes = _pose
+
+
+class Sim3SolverParams(C.Structure):
+    """include/rover_fe.h: rfe_sim3_solver_params -- both keyframes' poses and cameras, fix_scale, min_inliers, its and n of one Sim3Solver
+    problem."""
+    _fields_ = [("rcw1", C.c_float * 9), ("tcw1", C.c_float * 3), ("rcw2", C.c_float * 9), ("tcw2", C.c_float * 3),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("fix_scale", C.c_int32), ("min_inliers", C.c_int32), ("its", C.c_int32), ("n", C.c_int32)]
+
+
+def sim3_solver_params(problems):
+    """an rfe_sim3_solver_params array from dicts with rcw1, tcw1, rcw2, tcw2, cam1 / cam2 = (fx, fy, cx, cy), fix_scale, min_inliers, its, n"""
+    arr = (Sim3SolverParams * max(len(problems), 1))()
+    for p, d in zip(arr, problems):
+        for k in ("rcw1", "tcw1", "rcw2", "tcw2"):
+            getattr(p, k)[:] = [float(v) for v in np.asarray(d[k], np.float32).reshape(-1)]
+        p.fx1, p.fy1, p.cx1, p.cy1 = (float(v) for v in d["cam1"])
+        p.fx2, p.fy2, p.cx2, p.cy2 = (float(v) for v in d["cam2"])
+        p.fix_scale, p.min_inliers, p.its, p.n = int(d["fix_scale"]), int(d["min_inliers"]), int(d["its"]), int(d["n"])
+    return arr
+
+
+SIM3_RANSAC_OUTPUTS = ("R", "t", "s", "inliers", "best_inliers", "counts", "hyps")
+_s3 = [C.c_void_p, C.c_void_p, _fp, _fp, _fp, _fp, _ip, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _u8p, _u8p, _ip, _fp, _ip]
+lib.rfe_sim3_ransac.argtypes = _s3
+lib.rfe_sim3_ransac_dev.argtypes = _s3
+lib.rfe_sim3_ransac_iterations.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int]
+
+
+def sim3_ransac_iterations(probability, min_inliers, n, max_its):
+    """SetRansacParameters' mRansacMaxIts (rfe_sim3_ransac_iterations; needs no device)"""
+    return int(lib.rfe_sim3_ransac_iterations(float(probability), int(min_inliers), int(n), int(max_its)))
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
 BOW_MAX_N = 4096
@@ -1075,6 +1108,43 @@ class Context:
         a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
         self._chk(lib.rfe_pose_optimization_dev(self.h, C.byref(params), a(pose0), a(kpts_un), a(octave), a(uright), a(xw), a(has_mp), a(n),
                                                 int(B), int(N), a(pose), a(pose_f32), a(outlier), a(chi2), a(trace), a(stats)))
+
+    def sim3_ransac(self, problems, xw1, xw2, sigma2_1, sigma2_2, draws, fill=None, outputs=SIM3_RANSAC_OUTPUTS):
+        """Sim3Solver's RANSAC for B problems (rfe_sim3_ransac, host arrays).  problems: B dicts (sim3_solver_params()) or the
+        ctypes array; xw1 / xw2 [B,N,3], sigma2_1 / sigma2_2 [B,N], draws [B,H,3].  fill: what inliers / best_inliers [B,N], counts [B,H] and
+        hyps [B,H,32] hold where the call does not write (default 0).  outputs: the optional arrays to ask for.  Returns a dict: T12 [B,16],
+        stats [B,8], ret and the optional arrays."""
+        P = problems if isinstance(problems, C.Array) else sim3_solver_params(problems)
+        B = len(problems)
+        d = np.ascontiguousarray(draws, np.int32)
+        H = d.size // (3 * B) if B else 1
+        x1, x2 = np.ascontiguousarray(xw1, np.float32), np.ascontiguousarray(xw2, np.float32)
+        N = x1.size // (3 * B) if B else 0
+        g1, g2 = np.ascontiguousarray(sigma2_1, np.float32), np.ascontiguousarray(sigma2_2, np.float32)
+        assert x2.size == x1.size == B * N * 3 and g1.size == g2.size == B * N and d.size == B * H * 3
+        b1 = max(B, 1)
+        shape = {"T12": (b1, 16), "R": (b1, 9), "t": (b1, 3), "s": (b1,), "inliers": (b1, max(N, 1)), "best_inliers": (b1, max(N, 1)),
+                 "counts": (b1, H), "hyps": (b1, H, 32), "stats": (b1, 8)}
+        dt = {"inliers": np.uint8, "best_inliers": np.uint8, "counts": np.int32, "stats": np.int32}
+        o = {k: np.zeros(shape[k], dt.get(k, np.float32)) for k in shape}
+        for k, v in (fill or {}).items():
+            o[k][:B, :np.asarray(v).shape[1]] = v
+        arg = lambda k: o[k].ctypes.data if k in outputs else None   # noqa: E731
+        ret = self._chk(lib.rfe_sim3_ransac(self.h, C.addressof(P), _addr(x1), _addr(x2), _addr(g1), _addr(g2), _addr(d), B, N, H,
+                                            o["T12"].ctypes.data, arg("R"), arg("t"), arg("s"), arg("inliers"), arg("best_inliers"), arg("counts"),
+                                            arg("hyps"), o["stats"].ctypes.data))
+        r = {k: (o[k][:B, :N] if k in ("inliers", "best_inliers") else o[k][:B]) for k in ("T12", "stats") + tuple(outputs)}
+        r["ret"] = ret
+        return r
+
+    def sim3_ransac_dev(self, problems, xw1, xw2, sigma2_1, sigma2_2, draws, B, N, H, T12, stats, R=None, t=None, s=None, inliers=None,
+                        best_inliers=None, counts=None, hyps=None):
+        """rfe_sim3_ransac_dev: problems is a HOST array (sim3_solver_params()), every other array a DevBuf (or a raw device address / torch
+        tensor); asynchronous on the ctx stream."""
+        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        P = problems if isinstance(problems, C.Array) else sim3_solver_params(problems)
+        self._chk(lib.rfe_sim3_ransac_dev(self.h, C.addressof(P), a(xw1), a(xw2), a(sigma2_1), a(sigma2_2), a(draws), int(B), int(N), int(H),
+                                          a(T12), a(R), a(t), a(s), a(inliers), a(best_inliers), a(counts), a(hyps), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

@@ -139,6 +139,7 @@ struct rfe_ctx {
     int ps_cap = 0;                                  // rfe_search_by_projection (host form): most slots any call has needed
     void* ws_tri = nullptr; size_t ws_tri_bytes = 0; // rfe_triangulate_neighbours*: per-slot results, claims, per-neighbour counts
     void* ws_bow = nullptr; size_t ws_bow_bytes = 0; // rfe_bow_transform*: per-feature word / node / weight the caller did not ask for
+    void* ws_s3 = nullptr; size_t ws_s3_bytes = 0;   // rfe_sim3_ransac*: per-problem records, the front's rows, counts and hypotheses the caller did not ask for
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -403,5 +404,17 @@ void launch_bow_db_query(hipStream_t s, const int32_t* words, const double* valu
 void launch_pose_opt(hipStream_t s, const rfe_pose_params& P, const float* pose0, const float* kpts, const int32_t* octave, const float* uright,
                      const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose, float* pose_f32, uint8_t* outlier,
                      float* chi2, double* trace, int32_t* stats);
+
+// sim3_solver.hip: Sim3Solver's RANSAC with every hypothesis at once.  params is a HOST array: the front takes it by value,
+// S3_FRONT_CHUNK problems per launch, and leaves prob [B]; front [B, 12, N], counts [B, H] and hyps [B, H, 32] are workspace (or the
+// caller's counts / hyps).  R / t / sc / inliers / best_inliers may be NULL; presets nothing
+constexpr int S3_FRONT_CHUNK = 16;
+struct Sim3Prob { float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2; int32_t fix_scale, min_inliers, its, n; };
+void launch_sim3_front(hipStream_t s, const rfe_sim3_solver_params* params, const float* xw1, const float* xw2, const float* sg1, const float* sg2,
+                       int B, int N, Sim3Prob* prob, float* front);
+void launch_sim3_hypotheses(hipStream_t s, const Sim3Prob* prob, const float* front, const int32_t* draws, int B, int N, int H, int32_t* counts,
+                            float* hyps);
+void launch_sim3_select(hipStream_t s, const Sim3Prob* prob, const float* front, const int32_t* counts, const float* hyps, int B, int N, int H,
+                        float* T12, float* R, float* t, float* sc, uint8_t* inliers, uint8_t* best_inliers, int32_t* stats);
 
 }  // namespace rfe
