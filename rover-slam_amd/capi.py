@@ -404,6 +404,45 @@ class DevBuf:
             self.ptr = None
 
 
+def _dev(x):
+    """address of a DevBuf / raw device address / torch tensor: what the _dev wrappers take for every array."""
+    return x.ptr if isinstance(x, DevBuf) else _addr(x)
+
+
+def _f32_rows(a, w):
+    """a as contiguous float32 rows of w."""
+    return np.ascontiguousarray(a, np.float32).reshape(-1, w)
+
+
+def _opt(a, dt):
+    """an optional array: None, or a flat and contiguous as dt."""
+    return None if a is None else np.ascontiguousarray(a, dt).reshape(-1)
+
+
+# per-map-point outputs of the projection-search fronts as the host wrappers preset them (n = max(Np, 1))
+_PS_POINT_OUT = {"proj": lambda n: np.zeros((n, 2), np.float32), "radius": lambda n: np.zeros((n,), np.float32),
+                 "proj_xr": lambda n: np.zeros((n,), np.float32), "depth": lambda n: np.zeros((n,), np.float32),
+                 "view_cos": lambda n: np.zeros((n,), np.float32), "level": lambda n: np.full((n,), -1, np.int32),
+                 "reject": lambda n: np.ones((n,), np.int32)}
+
+
+def _ps_outputs(first, Np, Nf, front=()):
+    """output arrays of a projection-search host wrapper in the order the C entry takes them: `first` [Nf] (assign / matched), best_idx /
+    best_dist / second_dist [Np], then the front's (keys of _PS_POINT_OUT)."""
+    n1, f1 = max(Np, 1), max(Nf, 1)
+    o = {first: np.full((f1,), -1, np.int32), "best_idx": np.full((n1,), -1, np.int32), "best_dist": np.full((n1,), 256, np.float32),
+         "second_dist": np.full((n1,), 256, np.float32)}
+    o.update((k, _PS_POINT_OUT[k](n1)) for k in front)
+    return o
+
+
+def _ps_result(o, first, Np, Nf, nmatches, stats):
+    """the dict a projection-search host wrapper returns: the arrays of _ps_outputs cut to their counts, nmatches, stats."""
+    out = {k: (v[:Nf] if k == first else v[:Np]) for k, v in o.items()}
+    out.update(nmatches=nmatches, stats=stats)
+    return out
+
+
 def read_bow_vocab(path):
     """The library's reader of DBoW3's uncompressed binary vocabulary stream, without a device (rfe_k_bow_vocab_read): a dict with k, L,
     weighting, scoring, n_nodes, D and the arrays of rfe_bow_vocab_desc.  RfeError with the reader's reason when it refuses the file."""
@@ -485,7 +524,7 @@ class BowDatabase:
         return e.value
 
     def add_dev(self, word, value, n):
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         e = C.c_int32(-1)
         self.ctx._chk(lib.rfe_bow_db_add_dev(self.h, a(word), a(value), int(n), C.byref(e)))
         return e.value
@@ -515,7 +554,7 @@ class BowDatabase:
 
     def query_dev(self, word, value, nq, common, scored, score, stats, exclude=None):
         """rfe_bow_db_query_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self.ctx._chk(lib.rfe_bow_db_query_dev(self.h, a(word), a(value), int(nq), a(exclude), a(common), a(scored), a(score), a(stats)))
 
 
@@ -915,27 +954,23 @@ class Context:
         """SPmatcher::SearchByProjection1 as one call (rfe_search_by_projection, host arrays).  bounds = (min_x, min_y, max_x, max_y);
         exactly one of kpts [Nf,2] f32 and kxy [Nf,2] i32.  Returns a dict: assign [Nf], best_idx / best_dist / second_dist [Nq],
         nmatches, stats [4] (nmatches, candidates, rounds, overflow)."""
-        qa = np.ascontiguousarray(q, np.float32).reshape(-1, 256); fa = np.ascontiguousarray(f, np.float32).reshape(-1, 256)
-        pa = np.ascontiguousarray(proj, np.float32).reshape(-1, 2); ra = np.ascontiguousarray(radius, np.float32).reshape(-1)
+        qa, fa, pa, ra = _f32_rows(q, 256), _f32_rows(f, 256), _f32_rows(proj, 2), np.ascontiguousarray(radius, np.float32).reshape(-1)
         Nq, Nf = qa.shape[0], fa.shape[0]
         assert pa.shape[0] == Nq and ra.shape[0] == Nq
-        opt = lambda a, dt, n: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
-        ka, xa = opt(kpts, np.float32, Nf), opt(kxy, np.int32, Nf)
-        lv, ob = opt(pred_level, np.int32, Nq), opt(observed, np.uint8, Nq)
-        oc, sk = opt(octave, np.int32, Nf), opt(skip, np.uint8, Nf)
-        asg = np.full((max(Nf, 1),), -1, np.int32); st = np.zeros((4,), np.int32)
-        bi = np.full((max(Nq, 1),), -1, np.int32); bd = np.full((max(Nq, 1),), 256, np.float32); sd = np.full((max(Nq, 1),), 256, np.float32)
+        ka, xa, lv, ob = _opt(kpts, np.float32), _opt(kxy, np.int32), _opt(pred_level, np.int32), _opt(observed, np.uint8)
+        oc, sk = _opt(octave, np.int32), _opt(skip, np.uint8)
+        o, st = _ps_outputs("assign", Nq, Nf), np.zeros((4,), np.int32)
         n = self._chk(lib.rfe_search_by_projection(self.h, qa.ctypes.data, pa.ctypes.data, ra.ctypes.data, _addr(lv), _addr(ob), Nq,
                                                    fa.ctypes.data, _addr(ka), _addr(xa), _addr(oc), _addr(sk), Nf, *[float(b) for b in bounds],
-                                                   th_high, asg.ctypes.data, bi.ctypes.data, bd.ctypes.data, sd.ctypes.data, st.ctypes.data))
-        return {"assign": asg[:Nf], "best_idx": bi[:Nq], "best_dist": bd[:Nq], "second_dist": sd[:Nq], "nmatches": n, "stats": st}
+                                                   th_high, *[o[k].ctypes.data for k in o], st.ctypes.data))
+        return _ps_result(o, "assign", Nq, Nf, n, st)
 
     def search_by_projection_dev(self, q, proj, radius, Nq, f, Nf, bounds, cand_cap, assign, stats, kpts=None, kxy=None, pred_level=None,
                                  observed=None, octave=None, skip=None, nf_dev=None, th_high=1.4, best_idx=None, best_dist=None,
                                  second_dist=None):
         """rfe_search_by_projection_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
         outputs land in assign [Nf], stats [4] and the optional best_idx / best_dist / second_dist [Nq]."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_search_by_projection_dev(self.h, a(q), a(proj), a(radius), a(pred_level), a(observed), Nq, a(f), a(kpts), a(kxy),
                                                    a(octave), a(skip), Nf, a(nf_dev), *[float(b) for b in bounds], th_high, cand_cap,
                                                    a(assign), a(best_idx), a(best_dist), a(second_dist), a(stats)))
@@ -945,31 +980,23 @@ class Context:
         """The Sim3 SearchByProjection overloads of loop closing as one call (rfe_search_by_projection_sim3, host arrays).
         params: a Sim3Params (sim3_params()); scale_dist [Np] is the bare mfMaxDistance of PredictScale; exactly one of kpts [Nf,2] f32 and kxy [Nf,2] i32.  Returns a dict: matched [Nf], best_idx /
         best_dist / second_dist / radius / level / reject [Np], proj [Np,2], nmatches, stats [8]."""
-        f32 = lambda a, w: np.ascontiguousarray(a, np.float32).reshape(-1, w)   # noqa: E731
-        qa, fa, pa, na = f32(q, 256), f32(f, 256), f32(pw, 3), f32(normal, 3)
+        qa, fa, pa, na = _f32_rows(q, 256), _f32_rows(f, 256), _f32_rows(pw, 3), _f32_rows(normal, 3)
         mn, mx, sc = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (min_dist, max_dist, scale_dist))
         Np, Nf = qa.shape[0], fa.shape[0]
         assert pa.shape[0] == Np and na.shape[0] == Np and mn.shape[0] == Np and mx.shape[0] == Np and sc.shape[0] == Np
-        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
-        va, ka, xa, mi = opt(valid, np.uint8), opt(kpts, np.float32), opt(kxy, np.int32), opt(matched_in, np.uint8)
-        n1, f1 = max(Np, 1), max(Nf, 1)
-        o = {"matched": np.full((f1,), -1, np.int32), "best_idx": np.full((n1,), -1, np.int32), "best_dist": np.full((n1,), 256, np.float32),
-             "second_dist": np.full((n1,), 256, np.float32), "proj": np.zeros((n1, 2), np.float32), "radius": np.zeros((n1,), np.float32),
-             "level": np.full((n1,), -1, np.int32), "reject": np.ones((n1,), np.int32)}
-        st = np.zeros((8,), np.int32)
+        va, ka, xa, mi = _opt(valid, np.uint8), _opt(kpts, np.float32), _opt(kxy, np.int32), _opt(matched_in, np.uint8)
+        o, st = _ps_outputs("matched", Np, Nf, ("proj", "radius", "level", "reject")), np.zeros((8,), np.int32)
         n = self._chk(lib.rfe_search_by_projection_sim3(self.h, C.byref(params), qa.ctypes.data, pa.ctypes.data, na.ctypes.data, mn.ctypes.data,
                                                         mx.ctypes.data, sc.ctypes.data, _addr(va), Np, fa.ctypes.data, _addr(ka), _addr(xa), _addr(mi), Nf,
                                                         float(th_accept), *[o[k].ctypes.data for k in o], st.ctypes.data))
-        out = {k: (v[:Nf] if k == "matched" else v[:Np]) for k, v in o.items()}
-        out.update(nmatches=n, stats=st)
-        return out
+        return _ps_result(o, "matched", Np, Nf, n, st)
 
     def search_by_projection_sim3_dev(self, params, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, Nf, th_accept, cand_cap, matched, stats,
                                       valid=None, kpts=None, kxy=None, matched_in=None, nf_dev=None, best_idx=None, best_dist=None,
                                       second_dist=None, proj=None, radius=None, level=None, reject=None):
         """rfe_search_by_projection_sim3_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
         outputs land in matched [Nf], stats [8] and the optional per-map-point arrays."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_search_by_projection_sim3_dev(self.h, C.byref(params), a(q), a(pw), a(normal), a(min_dist), a(max_dist), a(scale_dist), a(valid), Np,
                                                         a(f), a(kpts), a(kxy), a(matched_in), Nf, a(nf_dev), float(th_accept), cand_cap,
                                                         a(matched), a(best_idx), a(best_dist), a(second_dist), a(proj), a(radius), a(level),
@@ -981,33 +1008,25 @@ class Context:
         FrustumParams (frustum_params()); scale_dist [Np] is the bare mfMaxDistance of PredictScale; exactly one of kpts [Nf,2] f32 and kxy
         [Nf,2] i32.  Returns a dict: assign [Nf], best_idx / best_dist / second_dist / proj_xr / depth / view_cos / level / reject [Np],
         proj [Np,2], nmatches, stats [8]."""
-        f32 = lambda a, w: np.ascontiguousarray(a, np.float32).reshape(-1, w)   # noqa: E731
-        qa, fa, pa, na = f32(q, 256), f32(f, 256), f32(pw, 3), f32(normal, 3)
+        qa, fa, pa, na = _f32_rows(q, 256), _f32_rows(f, 256), _f32_rows(pw, 3), _f32_rows(normal, 3)
         mn, mx, sc = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (min_dist, max_dist, scale_dist))
         Np, Nf = qa.shape[0], fa.shape[0]
         assert pa.shape[0] == Np and na.shape[0] == Np and mn.shape[0] == Np and mx.shape[0] == Np and sc.shape[0] == Np
-        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
-        va, ob, ka, xa = opt(valid, np.uint8), opt(observed, np.uint8), opt(kpts, np.float32), opt(kxy, np.int32)
-        oc, sk = opt(octave, np.int32), opt(skip, np.uint8)
-        n1, f1 = max(Np, 1), max(Nf, 1)
-        o = {"assign": np.full((f1,), -1, np.int32), "best_idx": np.full((n1,), -1, np.int32), "best_dist": np.full((n1,), 256, np.float32),
-             "second_dist": np.full((n1,), 256, np.float32), "proj": np.zeros((n1, 2), np.float32), "proj_xr": np.zeros((n1,), np.float32),
-             "depth": np.zeros((n1,), np.float32), "view_cos": np.zeros((n1,), np.float32), "level": np.full((n1,), -1, np.int32),
-             "reject": np.ones((n1,), np.int32)}
+        va, ob, ka, xa = _opt(valid, np.uint8), _opt(observed, np.uint8), _opt(kpts, np.float32), _opt(kxy, np.int32)
+        oc, sk = _opt(octave, np.int32), _opt(skip, np.uint8)
+        o = _ps_outputs("assign", Np, Nf, ("proj", "proj_xr", "depth", "view_cos", "level", "reject"))
         st = np.zeros((8,), np.int32)
         n = self._chk(lib.rfe_search_local_points(self.h, C.byref(params), qa.ctypes.data, pa.ctypes.data, na.ctypes.data, mn.ctypes.data,
                                                   mx.ctypes.data, sc.ctypes.data, _addr(va), _addr(ob), Np, fa.ctypes.data, _addr(ka), _addr(xa),
                                                   _addr(oc), _addr(sk), Nf, float(th_high), *[o[k].ctypes.data for k in o], st.ctypes.data))
-        out = {k: (v[:Nf] if k == "assign" else v[:Np]) for k, v in o.items()}
-        out.update(nmatches=n, stats=st)
-        return out
+        return _ps_result(o, "assign", Np, Nf, n, st)
 
     def search_local_points_dev(self, params, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, Nf, cand_cap, assign, stats, valid=None,
                                 observed=None, kpts=None, kxy=None, octave=None, skip=None, nf_dev=None, th_high=1.4, best_idx=None,
                                 best_dist=None, second_dist=None, proj=None, proj_xr=None, depth=None, view_cos=None, level=None, reject=None):
         """rfe_search_local_points_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream,
         outputs land in assign [Nf], stats [8] and the optional per-map-point arrays."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_search_local_points_dev(self.h, C.byref(params), a(q), a(pw), a(normal), a(min_dist), a(max_dist), a(scale_dist), a(valid),
                                                   a(observed), Np, a(f), a(kpts), a(kxy), a(octave), a(skip), Nf, a(nf_dev), float(th_high),
                                                   cand_cap, a(assign), a(best_idx), a(best_dist), a(second_dist), a(proj), a(proj_xr), a(depth),
@@ -1028,13 +1047,12 @@ class Context:
         N2max = k2.shape[1]
         v2 = (TriView * max(Nn, 1))(*views2)
         flat = lambda a, dt, n: np.ascontiguousarray(a, dt).reshape(-1)[:n] if n else np.zeros((0,), dt)   # noqa: E731
-        opt = lambda a, n: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1)           # noqa: E731
         o1, u1, d1, m1 = flat(octave1, np.int32, N1), flat(uright1, np.float32, N1), flat(depth1, np.float32, N1), flat(has_mp1, np.uint8, N1)
         f2 = Nn * N2max
         o2, u2, d2, m2 = flat(octave2, np.int32, f2), flat(uright2, np.float32, f2), flat(depth2, np.float32, f2), flat(has_mp2, np.uint8, f2)
         assert len(o1) == N1 and len(m1) == N1 and len(o2) == f2 and len(m2) == f2
         nn2, Sa = flat(n2, np.int32, Nn), flat(S, np.int32, Nn)
-        r1, r2 = opt(kpts1_raw, N1), opt(kpts2_raw, f2)
+        r1, r2 = _opt(kpts1_raw, np.float32), _opt(kpts2_raw, np.float32)
         nv = None if neighbour_valid is None else np.ascontiguousarray(neighbour_valid, np.uint8).reshape(-1)
         n1, s1 = max(N1, 1), max(Nn * Kmax, 1)
         o = {"code": np.full((s1,), -1, np.int32), "x3d": np.zeros((s1, 3), np.float32), "point_stereo": np.zeros((s1,), np.uint8),
@@ -1059,7 +1077,7 @@ class Context:
                                    matches=None):
         """rfe_triangulate_neighbours_dev: params and view1 are host structures, every array (views2 [Nn] included) a DevBuf (or a raw
         device address / torch tensor); asynchronous on the ctx stream.  The out_* arrays need room for N1 entries."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_triangulate_neighbours_dev(self.h, C.byref(params), C.byref(view1), a(kpts1), a(kpts1_raw), a(octave1), a(uright1),
                                                      a(depth1), a(has_mp1), N1, a(views2), a(kpts2), a(kpts2_raw), a(octave2), a(uright2),
                                                      a(depth2), a(has_mp2), a(n2), a(neighbour_valid), Nn, N2max, a(S), a(pairs), Kmax, a(code),
@@ -1079,9 +1097,8 @@ class Context:
         N = k.size // (2 * B) if B else 0
         k = k.reshape(B, N, 2)
         f = B * N
-        flat = lambda a, dt, m: None if a is None else np.ascontiguousarray(a, dt).reshape(-1)   # noqa: E731
-        x, m = flat(xw, np.float32, f * 3), flat(has_mp, np.uint8, f)
-        o, u, nn = flat(octave, np.int32, f), flat(uright, np.float32, f), flat(n, np.int32, B)
+        x, m = _opt(xw, np.float32), _opt(has_mp, np.uint8)
+        o, u, nn = _opt(octave, np.int32), _opt(uright, np.float32), _opt(n, np.int32)
         assert len(x) == f * 3 and len(m) == f and (o is None or len(o) == f) and (u is None or len(u) == f) and (nn is None or len(nn) == B)
         b1, f1 = max(B, 1), max(f, 1)
         out = np.zeros((f1,), np.uint8)
@@ -1105,7 +1122,7 @@ class Context:
                               pose_f32=None, chi2=None, trace=None):
         """rfe_pose_optimization_dev: params is a host structure, every array a DevBuf (or a raw device address / torch tensor);
         asynchronous on the ctx stream."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_pose_optimization_dev(self.h, C.byref(params), a(pose0), a(kpts_un), a(octave), a(uright), a(xw), a(has_mp), a(n),
                                                 int(B), int(N), a(pose), a(pose_f32), a(outlier), a(chi2), a(trace), a(stats)))
 
@@ -1141,7 +1158,7 @@ class Context:
                         best_inliers=None, counts=None, hyps=None):
         """rfe_sim3_ransac_dev: problems is a HOST array (sim3_solver_params()), every other array a DevBuf (or a raw device address / torch
         tensor); asynchronous on the ctx stream."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         P = problems if isinstance(problems, C.Array) else sim3_solver_params(problems)
         self._chk(lib.rfe_sim3_ransac_dev(self.h, C.addressof(P), a(xw1), a(xw2), a(sigma2_1), a(sigma2_2), a(draws), int(B), int(N), int(H),
                                           a(T12), a(R), a(t), a(s), a(inliers), a(best_inliers), a(counts), a(hyps), a(stats)))
@@ -1169,7 +1186,7 @@ class Context:
     def bow_transform_dev(self, vocab, N, levelsup, bow_n, bow_word, bow_value, fv_n, fv_node, fv_offsets, fv_feat, desc_f32=None, desc_u8=None,
                           word=None, node=None, weight=None):
         """rfe_bow_transform_dev: every array a DevBuf (or a raw device address / torch tensor); asynchronous on the ctx stream."""
-        a = lambda x: x.ptr if isinstance(x, DevBuf) else _addr(x)   # noqa: E731
+        a = _dev
         self._chk(lib.rfe_bow_transform_dev(self.h, vocab.h, a(desc_f32), a(desc_u8), int(N), int(levelsup), a(word), a(node), a(weight), a(bow_n),
                                             a(bow_word), a(bow_value), a(fv_n), a(fv_node), a(fv_offsets), a(fv_feat)))
 

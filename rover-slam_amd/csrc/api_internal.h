@@ -10,6 +10,12 @@ namespace rfe {
 
 inline size_t al(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
+// neither infinite nor NaN: the test the host entries make of their float arguments, over one value, n values, an array or a list
+inline bool finite(float v) { return v - v == 0.f; }
+inline bool finite(const float* p, size_t n) { for (size_t i = 0; i < n; ++i) if (!finite(p[i])) return false; return true; }
+template <size_t N> bool finite(const float (&a)[N]) { return finite(a, N); }
+inline bool finite(std::initializer_list<float> v) { return finite(v.begin(), v.size()); }
+
 // Bump allocator over a workspace.  A layout is ONE function that takes a Bump and the shape and fills its pointer struct; run on a Bump
 // without a base it only advances `off` (the pointers come back null), and that is the layout's byte count -- so the size a workspace is
 // grown to and the walk that carves it cannot differ.

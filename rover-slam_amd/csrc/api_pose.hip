@@ -37,11 +37,8 @@ extern "C" int rfe_pose_optimization(rfe_ctx* c, const rfe_pose_params* P, const
     if (!c) return RFE_ERR_INVALID;
     int rc = pose_check(c, P, pose0, kpts, xw, has_mp, B, N, pose, outlier, stats);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
-    bool ok = fin(P->fx) && fin(P->fy) && fin(P->cx) && fin(P->cy) && fin(P->bf);
-    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->inv_level_sigma2[l]);
-    for (int k = 0; k < B * 7; ++k) ok = ok && fin(pose0[k]);
-    if (!ok) return fail(c, RFE_ERR_INVALID, "pose_optimization: non-finite argument");
+    if (!(finite({P->fx, P->fy, P->cx, P->cy, P->bf}) && finite(P->inv_level_sigma2, P->nlevels) && finite(pose0, (size_t)B * 7)))
+        return fail(c, RFE_ERR_INVALID, "pose_optimization: non-finite argument");
     if (B == 0) return 0;
     RFE_HIP(c, hipSetDevice(c->device));
     const size_t f = (size_t)B * N;

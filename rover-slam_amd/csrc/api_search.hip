@@ -2,6 +2,7 @@
 // scan, SearchByProjection1, the Sim3 SearchByProjection overloads, SearchLocalPoints, distinctive descriptors).
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 #include "api_internal.h"
 
 using namespace rfe;
@@ -111,8 +112,12 @@ extern "C" int rfe_search_candidates(rfe_ctx* c, const float* q, int Nq, const f
     return io.download();
 }
 
-// SPmatcher::SearchByProjection1, left-camera branch (src/Matchers/SPmatcher.cc:1190-1283), device resident: grid, candidate lists, scan and
-// the sequential assignment (proj_search.hip).  Four kernels on the ctx stream, nothing read back.
+// =====================================================================================
+// The projection searches: SearchByProjection1, the Sim3 SearchByProjection overloads (6e), SearchLocalPoints (6f).  Behind
+// its front each of them is the same search, written once here (6d, "The back end"): ps_check holds the shape rules, ps_run the workspace,
+// the front and the grid -> count -> fill -> resolve sequence of the device forms, ps_sized the slot sizing of the host forms.  An entry is
+// its own checks, its own staging and one call into these.
+// =====================================================================================
 // ws_ps: the grid (cell starts, items, positions), the segment offsets and cand_cap (index, distance) slots -- one element at least of each
 struct PsBuffers { int32_t *cell_start, *cell_items, *seg_off, *cand_idx; float *fxy, *cand_dist; };
 static void ps_layout(Bump& a, int Nq, int Nf, int cand_cap, PsBuffers& b) {
@@ -121,15 +126,109 @@ static void ps_layout(Bump& a, int Nq, int Nf, int cand_cap, PsBuffers& b) {
     b.seg_off = a.take<int32_t>((size_t)Nq + 1); b.cand_idx = a.take<int32_t>(cap1); b.cand_dist = a.take<float>(cap1);
 }
 
-static int ps_check(rfe_ctx* c, const void* q, const void* proj, const void* radius, int Nq, const void* f, const void* kpts, const void* kxy,
-                    int Nf, float min_x, float min_y, float max_x, float max_y, int cand_cap, const void* assign) {
-    if (Nq < 0 || Nq > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nq outside 0..16384");
-    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_by_projection: Nf outside 0..4096");
-    if (!(max_x > min_x) || !(max_y > min_y)) return fail(c, RFE_ERR_INVALID, "search_by_projection: empty image bounds");
-    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_by_projection: negative cand_cap");
-    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pass exactly one of kpts and kxy");
-    if ((Nq > 0 && (!q || !proj || !radius)) || (Nf > 0 && (!f || !assign))) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
+// The shape rules of every projection search, in the order the refusals are tested: `count` is what the entry calls its map-point count
+// (Nq or Np), `own` the entry's rules that come between the bounds and cand_cap, `null_required` whether a required pointer is null.
+template <typename Own>
+static int ps_check(rfe_ctx* c, const char* entry, const char* count, int Nq, int Nf, float min_x, float min_y, float max_x, float max_y,
+                    int cand_cap, const void* kpts, const void* kxy, bool null_required, Own&& own) {
+    const auto refuse = [&](const std::string& what) { return fail(c, RFE_ERR_INVALID, std::string(entry) + ": " + what); };
+    if (Nq < 0 || Nq > 16384) return refuse(std::string(count) + " outside 0..16384");
+    if (Nf < 0 || Nf > 4096) return refuse("Nf outside 0..4096");
+    if (!(max_x > min_x) || !(max_y > min_y)) return refuse("empty image bounds");
+    if (int rc = own()) return rc;
+    if (cand_cap < 0) return refuse("negative cand_cap");
+    if ((kpts != nullptr) == (kxy != nullptr)) return refuse("pass exactly one of kpts and kxy");
+    if (null_required) return refuse("null pointer");
     return RFE_OK;
+}
+// the pyramid rules that the entries with a PredictScale front share
+static int ps_check_levels(rfe_ctx* c, const char* entry, int nlevels, float log_scale_factor) {
+    if (nlevels < 1 || nlevels > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, std::string(entry) + ": nlevels outside 1..16");
+    if (nlevels > 1 && !(log_scale_factor > 0.f)) return fail(c, RFE_ERR_INVALID, std::string(entry) + ": log_scale_factor must be positive");
+    return RFE_OK;
+}
+
+// One search, device resident.  Without a front proj / radius / pred_level are the caller's; with one they are ignored, the front writes
+// them into ws_ps and proj_out / radius_out / level_out (each may be null) receive copies; level_gate: proj_count reads the front's level.
+struct PsProblem {
+    const float* q; int Nq;                                                            // map points: descriptors
+    const float* proj; const float* radius; const int32_t* pred_level; const uint8_t* observed;
+    const float* f; const float* kpts; const int32_t* kxy; const int32_t* octave; const uint8_t* skip; int Nf; const int32_t* nf_dev;   // features
+    float min_x, min_y, max_x, max_y;
+    float th; bool trunc; int cand_cap;                                                // acceptance threshold, truncated distances (6e), slots
+    int32_t *assign, *best_idx; float *best_dist, *second_dist; int32_t* stats;
+    bool level_gate; float *proj_out, *radius_out; int32_t* level_out;
+};
+// Front: nullptr, or a callable (wproj, wradius, wlevel) that launches the front kernel, which runs under the profile stage `front_stage`.
+// Workspace: ps_layout, then behind it the front's proj [Nq,2], radius [Nq], level [Nq].  Four or five kernels on the ctx stream, nothing
+// read back.
+template <typename Front>
+static int ps_run(rfe_ctx* c, const PsProblem& p, const char* front_stage, Front&& front) {
+    constexpr bool has_front = !std::is_same<typename std::decay<Front>::type, std::nullptr_t>::value;
+    RFE_HIP(c, hipSetDevice(c->device));
+    PsBuffers b; float *wproj = nullptr, *wradius = nullptr; int32_t* wlevel = nullptr;
+    int rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
+        ps_layout(a, p.Nq, p.Nf, p.cand_cap, b);
+        if (has_front) {
+            const size_t np1 = (size_t)std::max(p.Nq, 1);
+            wproj = a.take<float>(np1 * 2); wradius = a.take<float>(np1); wlevel = a.take<int32_t>(np1);
+        }
+    });
+    if (rc) return rc;
+    const float inv_w = 32.f / (p.max_x - p.min_x), inv_h = 24.f / (p.max_y - p.min_y);   // mfGridElementWidthInv / HeightInv of the Frame or KeyFrame
+    const float *proj = p.proj, *radius = p.radius; const int32_t* pred_level = p.pred_level;
+    hipStream_t s = c->stream;
+    if constexpr (has_front) {
+        RFE_HIP(c, hipMemsetAsync(p.stats + 4, 0, 16, s));
+        { ProfScope ps(c, front_stage); front(wproj, wradius, wlevel); }
+        proj = wproj; radius = wradius; pred_level = p.level_gate ? wlevel : nullptr;
+    }
+    { ProfScope ps(c, "ps_grid");
+      launch_proj_grid(s, p.kpts, p.kxy, p.Nf, p.nf_dev, p.min_x, p.min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
+    { ProfScope ps(c, "ps_count");
+      launch_proj_count(s, proj, radius, pred_level, p.Nq, b.cell_start, b.cell_items, b.fxy, p.octave, p.min_x, p.min_y, inv_w, inv_h, p.cand_cap,
+                        b.seg_off, b.cand_idx, p.stats); }
+    { ProfScope ps(c, "ps_fill");
+      if (p.trunc) launch_proj_fill_trunc(s, p.q, p.Nq, p.f, p.Nf, b.seg_off, b.cand_idx, p.skip, b.cand_dist);
+      else launch_proj_fill(s, p.q, p.Nq, p.f, p.Nf, b.seg_off, b.cand_idx, p.skip, b.cand_dist); }
+    { ProfScope ps(c, "ps_resolve");
+      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, p.observed, p.Nq, p.Nf, p.th, p.assign, p.best_idx, p.best_dist, p.second_dist,
+                          p.stats); }
+    if (has_front && p.Nq > 0) {
+        if (p.proj_out) RFE_HIP(c, hipMemcpyAsync(p.proj_out, wproj, (size_t)p.Nq * 8, hipMemcpyDeviceToDevice, s));
+        if (p.radius_out) RFE_HIP(c, hipMemcpyAsync(p.radius_out, wradius, (size_t)p.Nq * 4, hipMemcpyDeviceToDevice, s));
+        if (p.level_out) RFE_HIP(c, hipMemcpyAsync(p.level_out, wlevel, (size_t)p.Nq * 4, hipMemcpyDeviceToDevice, s));
+    }
+    RFE_HIP(c, hipGetLastError());
+    return RFE_OK;
+}
+
+// Slot sizing of the host forms.  The candidate total is known on the device only: `run(cap)` (the entry's device form on the staged arrays,
+// stats at dst) goes with the largest slot count used so far (at least 16 per map point) and, when the lists need more, once again with
+// exactly what they need.  Then the download, the n_stats ints for the caller, and the number of matches.
+template <typename Run>
+static int ps_sized(rfe_ctx* c, const char* entry, int Nq, int Nf, HostIo& io, const int32_t* dst, int n_stats, int32_t* stats, Run&& run) {
+    int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int rc, cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Nq, 1)), (long long)Nq * Nf);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = run(cap))) return rc;
+        RFE_HIP(c, hipMemcpyAsync(st, dst, (size_t)n_stats * 4, hipMemcpyDeviceToHost, c->stream));
+        RFE_HIP(c, hipStreamSynchronize(c->stream));
+        if (!st[3]) break;
+        cap = st[1];
+    }
+    if (st[3]) return fail(c, RFE_ERR_HIP, std::string(entry) + ": candidate lists still overflow");
+    c->ps_cap = std::max(c->ps_cap, cap);
+    if ((rc = io.download())) return rc;
+    if (stats) memcpy(stats, st, (size_t)n_stats * 4);
+    return st[0];
+}
+
+// SPmatcher::SearchByProjection1, left-camera branch (src/Matchers/SPmatcher.cc:1190-1283): no front, the caller projects.
+static int sbp_check(rfe_ctx* c, const void* q, const void* proj, const void* radius, int Nq, const void* f, const void* kpts, const void* kxy,
+                    int Nf, float min_x, float min_y, float max_x, float max_y, int cand_cap, const void* assign) {
+    return ps_check(c, "search_by_projection", "Nq", Nq, Nf, min_x, min_y, max_x, max_y, cand_cap, kpts, kxy,
+                    (Nq > 0 && (!q || !proj || !radius)) || (Nf > 0 && (!f || !assign)), [] { return RFE_OK; });
 }
 
 extern "C" int rfe_search_by_projection_dev(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
@@ -138,24 +237,12 @@ extern "C" int rfe_search_by_projection_dev(rfe_ctx* c, const float* q, const fl
                                             float min_y, float max_x, float max_y, float th_high, int cand_cap, int32_t* assign,
                                             int32_t* best_idx, float* best_dist, float* second_dist, int32_t* stats) {
     if (!c) return RFE_ERR_INVALID;
-    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, cand_cap, assign);
+    int rc = sbp_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, cand_cap, assign);
     if (rc) return rc;
     if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection: null pointer");
-    RFE_HIP(c, hipSetDevice(c->device));
-    PsBuffers b;
-    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) { ps_layout(a, Nq, Nf, cand_cap, b); });
-    if (rc) return rc;
-    const float inv_w = 32.f / (max_x - min_x), inv_h = 24.f / (max_y - min_y);      // Frame::mfGridElementWidthInv / HeightInv
-    hipStream_t s = c->stream;
-    { ProfScope ps(c, "ps_grid"); launch_proj_grid(s, kpts, kxy, Nf, nf_dev, min_x, min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
-    { ProfScope ps(c, "ps_count");
-      launch_proj_count(s, proj, radius, pred_level, Nq, b.cell_start, b.cell_items, b.fxy, octave, min_x, min_y, inv_w, inv_h, cand_cap, b.seg_off,
-                        b.cand_idx, stats); }
-    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Nq, f, Nf, b.seg_off, b.cand_idx, skip, b.cand_dist); }
-    { ProfScope ps(c, "ps_resolve");
-      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, observed, Nq, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
-    RFE_HIP(c, hipGetLastError());
-    return RFE_OK;
+    return ps_run(c, PsProblem{q, Nq, proj, radius, pred_level, observed, f, kpts, kxy, octave, skip, Nf, nf_dev, min_x, min_y, max_x, max_y,
+                               th_high, false, cand_cap, assign, best_idx, best_dist, second_dist, stats, false, nullptr, nullptr, nullptr},
+                  nullptr, nullptr);
 }
 
 extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float* proj, const float* radius, const int32_t* pred_level,
@@ -164,16 +251,14 @@ extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float*
                                         float max_y, float th_high, int32_t* assign, int32_t* best_idx, float* best_dist,
                                         float* second_dist, int32_t* stats) {
     if (!c) return RFE_ERR_INVALID;
-    int rc = ps_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, 0, assign);
+    int rc = sbp_check(c, q, proj, radius, Nq, f, kpts, kxy, Nf, min_x, min_y, max_x, max_y, 0, assign);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
-    if (!fin(min_x) || !fin(min_y) || !fin(max_x) || !fin(max_y) || !fin(th_high))
-        return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite argument");
+    if (!finite({min_x, min_y, max_x, max_y, th_high})) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite argument");
     for (int i = 0; i < Nq; ++i) {
-        if (!fin(proj[2 * i]) || !fin(proj[2 * i + 1]) || !fin(radius[i])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite projection or radius");
+        if (!finite(proj + 2 * i, 2) || !finite(radius[i])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite projection or radius");
         if (pred_level && (pred_level[i] < 0 || pred_level[i] >= RFE_MAX_LEVELS)) return fail(c, RFE_ERR_INVALID, "search_by_projection: pred_level outside 0..15");
     }
-    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite keypoint");
+    if (kpts && !finite(kpts, 2 * (size_t)Nf)) return fail(c, RFE_ERR_INVALID, "search_by_projection: non-finite keypoint");
     RFE_HIP(c, hipSetDevice(c->device));
     float *dq, *dproj, *drad, *df, *dbd, *dsd; int32_t *dlev, *doct, *dasg, *dbi, *dst; uint8_t *dobs, *dsk; float* dkp; int32_t* dkx;
     HostIo io(c, HostIo::DIRECT);
@@ -181,45 +266,26 @@ extern "C" int rfe_search_by_projection(rfe_ctx* c, const float* q, const float*
     io.in(df, f, (size_t)Nf * 256); io.in_opt(dkp, kpts, (size_t)Nf * 2); io.in_opt(dkx, kxy, (size_t)Nf * 2); io.in_opt(doct, octave, Nf); io.in_opt(dsk, skip, Nf);
     io.out(dasg, assign, Nf); io.out(dbi, best_idx, Nq); io.out(dbd, best_dist, Nq); io.out(dsd, second_dist, Nq); io.scratch(dst, 4);
     if ((rc = io.upload())) return rc;
-    hipStream_t s = c->stream;
-    // the candidate total is known on the device only: run with the largest slot count used so far (at least 16 per map point) and,
-    // when the lists need more, once again with exactly what they need
-    int32_t st[4] = {0, 0, 0, 0};
-    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Nq, 1)), (long long)Nq * Nf);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if ((rc = rfe_search_by_projection_dev(c, dq, dproj, drad, dlev, dobs, Nq, df, dkp, dkx, doct, dsk, Nf, nullptr, min_x, min_y, max_x, max_y,
-                                               th_high, cap, dasg, dbi, dbd, dsd, dst))) return rc;
-        RFE_HIP(c, hipMemcpyAsync(st, dst, 16, hipMemcpyDeviceToHost, s));
-        RFE_HIP(c, hipStreamSynchronize(s));
-        if (!st[3]) break;
-        cap = st[1];
-    }
-    if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection: candidate lists still overflow");
-    c->ps_cap = std::max(c->ps_cap, cap);
-    if ((rc = io.download())) return rc;
-    if (stats) memcpy(stats, st, 16);
-    return st[0];
+    return ps_sized(c, "search_by_projection", Nq, Nf, io, dst, 4, stats, [&](int cap) {
+        return rfe_search_by_projection_dev(c, dq, dproj, drad, dlev, dobs, Nq, df, dkp, dkx, doct, dsk, Nf, nullptr, min_x, min_y, max_x, max_y, th_high,
+                                            cap, dasg, dbi, dbd, dsd, dst);
+    });
 }
 
-// The Sim3 SearchByProjection overloads of loop closing (src/Matchers/SPmatcher.cc:1558-1669, 2076-2182): sim3_project_kernel
-// (proj_sim3.hip) writes proj / radius / level into ws_ps, behind the layout of rfe_search_by_projection_dev, and the grid, count, fill and
-// resolve kernels of 6d run on them with no octave gate and every map point observed.
+// The Sim3 SearchByProjection overloads of loop closing (src/Matchers/SPmatcher.cc:1558-1669, 2076-2182): the front is
+// sim3_project_kernel (proj_sim3.hip); the search runs with no octave gate and every map point observed.
 static int s3_check(rfe_ctx* c, const rfe_sim3_params* P, const void* q, const void* pw, const void* normal, const void* min_dist,
                     const void* max_dist, const void* scale_dist, int Np, const void* f, const void* kpts, const void* kxy, int Nf, int cand_cap,
                     const void* matched) {
+    const char* entry = "search_by_projection_sim3";
     if (!P) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
-    if (Np < 0 || Np > 16384) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: Np outside 0..16384");
-    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: Nf outside 0..4096");
-    if (!(P->max_x > P->min_x) || !(P->max_y > P->min_y)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: empty image bounds");
-    if (P->nlevels < 1 || P->nlevels > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: nlevels outside 1..16");
-    if (P->nlevels > 1 && !(P->log_scale_factor > 0.f)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: log_scale_factor must be positive");
-    if (P->proj_mode != RFE_PROJ_INVZ && P->proj_mode != RFE_PROJ_DIV) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown proj_mode");
-    if (P->dist_mode != RFE_DIST_FLOAT && P->dist_mode != RFE_DIST_TRUNC) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown dist_mode");
-    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: negative cand_cap");
-    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: pass exactly one of kpts and kxy");
-    if ((Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !matched)))
-        return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
-    return RFE_OK;
+    return ps_check(c, entry, "Np", Np, Nf, P->min_x, P->min_y, P->max_x, P->max_y, cand_cap, kpts, kxy,
+                    (Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !matched)), [&] {
+        if (int rc = ps_check_levels(c, entry, P->nlevels, P->log_scale_factor)) return rc;
+        if (P->proj_mode != RFE_PROJ_INVZ && P->proj_mode != RFE_PROJ_DIV) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown proj_mode");
+        if (P->dist_mode != RFE_DIST_FLOAT && P->dist_mode != RFE_DIST_TRUNC) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: unknown dist_mode");
+        return (int)RFE_OK;
+    });
 }
 
 extern "C" int rfe_search_by_projection_sim3_dev(rfe_ctx* c, const rfe_sim3_params* P, const float* q, const float* pw, const float* normal,
@@ -233,35 +299,12 @@ extern "C" int rfe_search_by_projection_sim3_dev(rfe_ctx* c, const rfe_sim3_para
     int rc = s3_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, cand_cap, matched);
     if (rc) return rc;
     if (!stats) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: null pointer");
-    RFE_HIP(c, hipSetDevice(c->device));
-    PsBuffers b; float *wproj, *wradius; int32_t* wlevel;
-    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
-        ps_layout(a, Np, Nf, cand_cap, b);
-        const size_t np1 = (size_t)std::max(Np, 1);
-        wproj = a.take<float>(np1 * 2); wradius = a.take<float>(np1); wlevel = a.take<int32_t>(np1);
+    return ps_run(c, PsProblem{q, Np, nullptr, nullptr, nullptr, nullptr, f, kpts, kxy, nullptr, matched_in, Nf, nf_dev, P->min_x, P->min_y, P->max_x,
+                               P->max_y, th_accept, P->dist_mode == RFE_DIST_TRUNC, cand_cap, matched, best_idx, best_dist, second_dist, stats, false,
+                               proj, radius, level},
+                  "s3_project", [&](float* wproj, float* wradius, int32_t* wlevel) {
+        launch_sim3_project(c->stream, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, reject, stats);
     });
-    if (rc) return rc;
-    const float inv_w = 32.f / (P->max_x - P->min_x), inv_h = 24.f / (P->max_y - P->min_y);   // KeyFrame::mfGridElementWidthInv / HeightInv
-    hipStream_t s = c->stream;
-    RFE_HIP(c, hipMemsetAsync(stats + 4, 0, 16, s));
-    { ProfScope ps(c, "s3_project"); launch_sim3_project(s, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, reject, stats); }
-    { ProfScope ps(c, "ps_grid");
-      launch_proj_grid(s, kpts, kxy, Nf, nf_dev, P->min_x, P->min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
-    { ProfScope ps(c, "ps_count");
-      launch_proj_count(s, wproj, wradius, nullptr, Np, b.cell_start, b.cell_items, b.fxy, nullptr, P->min_x, P->min_y, inv_w, inv_h, cand_cap,
-                        b.seg_off, b.cand_idx, stats); }
-    { ProfScope ps(c, "ps_fill");
-      if (P->dist_mode == RFE_DIST_TRUNC) launch_proj_fill_trunc(s, q, Np, f, Nf, b.seg_off, b.cand_idx, matched_in, b.cand_dist);
-      else launch_proj_fill(s, q, Np, f, Nf, b.seg_off, b.cand_idx, matched_in, b.cand_dist); }
-    { ProfScope ps(c, "ps_resolve");
-      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, nullptr, Np, Nf, th_accept, matched, best_idx, best_dist, second_dist, stats); }
-    if (Np > 0) {
-        if (proj) RFE_HIP(c, hipMemcpyAsync(proj, wproj, (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
-        if (radius) RFE_HIP(c, hipMemcpyAsync(radius, wradius, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
-        if (level) RFE_HIP(c, hipMemcpyAsync(level, wlevel, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
-    }
-    RFE_HIP(c, hipGetLastError());
-    return RFE_OK;
 }
 
 extern "C" int rfe_search_by_projection_sim3(rfe_ctx* c, const rfe_sim3_params* P, const float* q, const float* pw, const float* normal,
@@ -273,15 +316,10 @@ extern "C" int rfe_search_by_projection_sim3(rfe_ctx* c, const rfe_sim3_params* 
     if (!c) return RFE_ERR_INVALID;
     int rc = s3_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, 0, matched);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
-    bool ok = fin(th_accept) && fin(P->log_scale_factor);
-    for (float v : P->quat) ok = ok && fin(v);
-    for (float v : P->t) ok = ok && fin(v);
-    for (float v : P->ow) ok = ok && fin(v);
-    for (float v : {P->fx, P->fy, P->cx, P->cy, P->min_x, P->min_y, P->max_x, P->max_y}) ok = ok && fin(v);
-    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->scale_factors[l]);
-    if (!ok) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite argument");
-    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite keypoint");
+    if (!(finite({th_accept, P->log_scale_factor, P->fx, P->fy, P->cx, P->cy, P->min_x, P->min_y, P->max_x, P->max_y}) && finite(P->quat) &&
+          finite(P->t) && finite(P->ow) && finite(P->scale_factors, P->nlevels)))
+        return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite argument");
+    if (kpts && !finite(kpts, 2 * (size_t)Nf)) return fail(c, RFE_ERR_INVALID, "search_by_projection_sim3: non-finite keypoint");
     RFE_HIP(c, hipSetDevice(c->device));
     float *dq, *dpw, *dn, *dmin, *dmax, *dsc, *df, *dkp, *dbd, *dsd, *dproj, *drad; int32_t *dkx, *dm, *dbi, *dlev, *drej, *dst; uint8_t *dval, *dmi;
     HostIo io(c, HostIo::DIRECT);
@@ -292,43 +330,26 @@ extern "C" int rfe_search_by_projection_sim3(rfe_ctx* c, const rfe_sim3_params* 
     io.out_opt(dproj, proj, (size_t)Np * 2); io.out_opt(drad, radius, Np); io.out_opt(dlev, level, Np); io.out_opt(drej, reject, Np);
     io.scratch(dst, 8);
     if ((rc = io.upload())) return rc;
-    hipStream_t s = c->stream;
-    // the slots: as rfe_search_by_projection -- the largest count used so far (at least 16 per map point), then once more with what is needed
-    int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Np, 1)), (long long)Np * Nf);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if ((rc = rfe_search_by_projection_sim3_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, Np, df, dkp, dkx, dmi, Nf, nullptr, th_accept, cap, dm,
-                                                    dbi, dbd, dsd, dproj, drad, dlev, drej, dst))) return rc;
-        RFE_HIP(c, hipMemcpyAsync(st, dst, 32, hipMemcpyDeviceToHost, s));
-        RFE_HIP(c, hipStreamSynchronize(s));
-        if (!st[3]) break;
-        cap = st[1];
-    }
-    if (st[3]) return fail(c, RFE_ERR_HIP, "search_by_projection_sim3: candidate lists still overflow");
-    c->ps_cap = std::max(c->ps_cap, cap);
-    if ((rc = io.download())) return rc;
-    if (stats) memcpy(stats, st, 32);
-    return st[0];
+    return ps_sized(c, "search_by_projection_sim3", Np, Nf, io, dst, 8, stats, [&](int cap) {
+        return rfe_search_by_projection_sim3_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, Np, df, dkp, dkx, dmi, Nf, nullptr, th_accept, cap, dm, dbi, dbd,
+                                                 dsd, dproj, drad, dlev, drej, dst);
+    });
 }
 
-// Steps 2 and 3 of Tracking::SearchLocalPoints (src/Tracking.cc:4124-4180): frustum_project_kernel (proj_frustum.hip) writes
-// proj / radius / level into ws_ps, behind the layout of rfe_search_by_projection_dev, and what else isInFrustum leaves in a map point
-// straight into the caller's arrays; the grid, count, fill and resolve kernels of 6d run on them as they are.
+// Steps 2 and 3 of Tracking::SearchLocalPoints (src/Tracking.cc:4124-4180): the front is frustum_project_kernel
+// (proj_frustum.hip), which also writes what else isInFrustum leaves in a map point straight into the caller's arrays; the search runs on
+// its proj / radius / level as they are.
 static int lp_check(rfe_ctx* c, const rfe_frustum_params* P, const void* q, const void* pw, const void* normal, const void* min_dist,
                     const void* max_dist, const void* scale_dist, int Np, const void* f, const void* kpts, const void* kxy, int Nf, int cand_cap,
                     const void* assign) {
+    const char* entry = "search_local_points";
     if (!P) return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
-    if (Np < 0 || Np > 16384) return fail(c, RFE_ERR_INVALID, "search_local_points: Np outside 0..16384");
-    if (Nf < 0 || Nf > 4096) return fail(c, RFE_ERR_INVALID, "search_local_points: Nf outside 0..4096");
-    if (!(P->max_x > P->min_x) || !(P->max_y > P->min_y)) return fail(c, RFE_ERR_INVALID, "search_local_points: empty image bounds");
-    if (P->nlevels < 1 || P->nlevels > RFE_MAX_LEVELS) return fail(c, RFE_ERR_INVALID, "search_local_points: nlevels outside 1..16");
-    if (P->nlevels > 1 && !(P->log_scale_factor > 0.f)) return fail(c, RFE_ERR_INVALID, "search_local_points: log_scale_factor must be positive");
-    if (P->level_mode != RFE_LEVEL_ZERO && P->level_mode != RFE_LEVEL_PREDICTED) return fail(c, RFE_ERR_INVALID, "search_local_points: unknown level_mode");
-    if (cand_cap < 0) return fail(c, RFE_ERR_INVALID, "search_local_points: negative cand_cap");
-    if ((kpts != nullptr) == (kxy != nullptr)) return fail(c, RFE_ERR_INVALID, "search_local_points: pass exactly one of kpts and kxy");
-    if ((Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !assign)))
-        return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
-    return RFE_OK;
+    return ps_check(c, entry, "Np", Np, Nf, P->min_x, P->min_y, P->max_x, P->max_y, cand_cap, kpts, kxy,
+                    (Np > 0 && (!q || !pw || !normal || !min_dist || !max_dist || !scale_dist)) || (Nf > 0 && (!f || !assign)), [&] {
+        if (int rc = ps_check_levels(c, entry, P->nlevels, P->log_scale_factor)) return rc;
+        if (P->level_mode != RFE_LEVEL_ZERO && P->level_mode != RFE_LEVEL_PREDICTED) return fail(c, RFE_ERR_INVALID, "search_local_points: unknown level_mode");
+        return (int)RFE_OK;
+    });
 }
 
 extern "C" int rfe_search_local_points_dev(rfe_ctx* c, const rfe_frustum_params* P, const float* q, const float* pw, const float* normal,
@@ -341,36 +362,14 @@ extern "C" int rfe_search_local_points_dev(rfe_ctx* c, const rfe_frustum_params*
     int rc = lp_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, cand_cap, assign);
     if (rc) return rc;
     if (!stats) return fail(c, RFE_ERR_INVALID, "search_local_points: null pointer");
-    RFE_HIP(c, hipSetDevice(c->device));
-    PsBuffers b; float *wproj, *wradius; int32_t* wlevel;
-    rc = ws_carve(c, &c->ws_ps, &c->ws_ps_bytes, [&](Bump& a) {
-        ps_layout(a, Np, Nf, cand_cap, b);
-        const size_t np1 = (size_t)std::max(Np, 1);
-        wproj = a.take<float>(np1 * 2); wradius = a.take<float>(np1); wlevel = a.take<int32_t>(np1);
+    // level_gate: a rejected point has level -1 and radius 0, an empty list either way
+    return ps_run(c, PsProblem{q, Np, nullptr, nullptr, nullptr, observed, f, kpts, kxy, octave, skip, Nf, nf_dev, P->min_x, P->min_y, P->max_x,
+                               P->max_y, th_high, false, cand_cap, assign, best_idx, best_dist, second_dist, stats,
+                               P->level_mode == RFE_LEVEL_PREDICTED, proj, nullptr, level},
+                  "lp_frustum", [&](float* wproj, float* wradius, int32_t* wlevel) {
+        launch_frustum_project(c->stream, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, proj_xr, depth, view_cos,
+                               reject, stats);
     });
-    if (rc) return rc;
-    const float inv_w = 32.f / (P->max_x - P->min_x), inv_h = 24.f / (P->max_y - P->min_y);   // Frame::mfGridElementWidthInv / HeightInv
-    // a rejected point has level -1 and radius 0: an empty list either way
-    const int32_t* pred_level = P->level_mode == RFE_LEVEL_PREDICTED ? wlevel : nullptr;
-    hipStream_t s = c->stream;
-    RFE_HIP(c, hipMemsetAsync(stats + 4, 0, 16, s));
-    { ProfScope ps(c, "lp_frustum");
-      launch_frustum_project(s, *P, pw, normal, min_dist, max_dist, scale_dist, valid, Np, wproj, wradius, wlevel, proj_xr, depth, view_cos, reject,
-                             stats); }
-    { ProfScope ps(c, "ps_grid");
-      launch_proj_grid(s, kpts, kxy, Nf, nf_dev, P->min_x, P->min_y, inv_w, inv_h, b.cell_start, b.cell_items, b.fxy); }
-    { ProfScope ps(c, "ps_count");
-      launch_proj_count(s, wproj, wradius, pred_level, Np, b.cell_start, b.cell_items, b.fxy, octave, P->min_x, P->min_y, inv_w, inv_h, cand_cap,
-                        b.seg_off, b.cand_idx, stats); }
-    { ProfScope ps(c, "ps_fill"); launch_proj_fill(s, q, Np, f, Nf, b.seg_off, b.cand_idx, skip, b.cand_dist); }
-    { ProfScope ps(c, "ps_resolve");
-      launch_proj_resolve(s, b.seg_off, b.cand_idx, b.cand_dist, observed, Np, Nf, th_high, assign, best_idx, best_dist, second_dist, stats); }
-    if (Np > 0) {
-        if (proj) RFE_HIP(c, hipMemcpyAsync(proj, wproj, (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
-        if (level) RFE_HIP(c, hipMemcpyAsync(level, wlevel, (size_t)Np * 4, hipMemcpyDeviceToDevice, s));
-    }
-    RFE_HIP(c, hipGetLastError());
-    return RFE_OK;
 }
 
 extern "C" int rfe_search_local_points(rfe_ctx* c, const rfe_frustum_params* P, const float* q, const float* pw, const float* normal,
@@ -382,15 +381,10 @@ extern "C" int rfe_search_local_points(rfe_ctx* c, const rfe_frustum_params* P, 
     if (!c) return RFE_ERR_INVALID;
     int rc = lp_check(c, P, q, pw, normal, min_dist, max_dist, scale_dist, Np, f, kpts, kxy, Nf, 0, assign);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
-    bool ok = fin(th_high) && fin(P->log_scale_factor) && fin(P->th) && fin(P->view_cos_limit) && (!P->far_points || fin(P->th_far));
-    for (float v : P->rcw) ok = ok && fin(v);
-    for (float v : P->tcw) ok = ok && fin(v);
-    for (float v : P->ow) ok = ok && fin(v);
-    for (float v : {P->fx, P->fy, P->cx, P->cy, P->mbf, P->min_x, P->min_y, P->max_x, P->max_y}) ok = ok && fin(v);
-    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->scale_factors[l]);
-    if (!ok) return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite argument");
-    if (kpts) for (int k = 0; k < 2 * Nf; ++k) if (!fin(kpts[k])) return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite keypoint");
+    if (!(finite({th_high, P->log_scale_factor, P->th, P->view_cos_limit, P->fx, P->fy, P->cx, P->cy, P->mbf, P->min_x, P->min_y, P->max_x, P->max_y}) &&
+          (!P->far_points || finite(P->th_far)) && finite(P->rcw) && finite(P->tcw) && finite(P->ow) && finite(P->scale_factors, P->nlevels)))
+        return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite argument");
+    if (kpts && !finite(kpts, 2 * (size_t)Nf)) return fail(c, RFE_ERR_INVALID, "search_local_points: non-finite keypoint");
     RFE_HIP(c, hipSetDevice(c->device));
     float *dq, *dpw, *dn, *dmin, *dmax, *dsc, *df, *dkp, *dbd, *dsd, *dproj, *dxr, *ddep, *dvc; int32_t *dkx, *doct, *dasg, *dbi, *dlev, *drej, *dst;
     uint8_t *dval, *dobs, *dsk;
@@ -404,23 +398,10 @@ extern "C" int rfe_search_local_points(rfe_ctx* c, const rfe_frustum_params* P, 
     io.out_opt(dlev, level, Np); io.out_opt(drej, reject, Np);
     io.scratch(dst, 8);
     if ((rc = io.upload())) return rc;
-    hipStream_t s = c->stream;
-    // the slots: as rfe_search_by_projection -- the largest count used so far (at least 16 per map point), then once more with what is needed
-    int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int cap = (int)std::min<long long>(std::max<long long>(c->ps_cap, 16LL * std::max(Np, 1)), (long long)Np * Nf);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if ((rc = rfe_search_local_points_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, dobs, Np, df, dkp, dkx, doct, dsk, Nf, nullptr, th_high, cap,
-                                              dasg, dbi, dbd, dsd, dproj, dxr, ddep, dvc, dlev, drej, dst))) return rc;
-        RFE_HIP(c, hipMemcpyAsync(st, dst, 32, hipMemcpyDeviceToHost, s));
-        RFE_HIP(c, hipStreamSynchronize(s));
-        if (!st[3]) break;
-        cap = st[1];
-    }
-    if (st[3]) return fail(c, RFE_ERR_HIP, "search_local_points: candidate lists still overflow");
-    c->ps_cap = std::max(c->ps_cap, cap);
-    if ((rc = io.download())) return rc;
-    if (stats) memcpy(stats, st, 32);
-    return st[0];
+    return ps_sized(c, "search_local_points", Np, Nf, io, dst, 8, stats, [&](int cap) {
+        return rfe_search_local_points_dev(c, P, dq, dpw, dn, dmin, dmax, dsc, dval, dobs, Np, df, dkp, dkx, doct, dsk, Nf, nullptr, th_high, cap, dasg, dbi,
+                                           dbd, dsd, dproj, dxr, ddep, dvc, dlev, drej, dst);
+    });
 }
 
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:438-530) for Np map points whose observed descriptors and CSR

@@ -55,17 +55,14 @@ extern "C" int rfe_sim3_ransac(rfe_ctx* c, const rfe_sim3_solver_params* P, cons
     if (!c) return RFE_ERR_INVALID;
     int rc = sim3_check(c, P, xw1, xw2, s1, s2, draws, B, N, H, T12, stats);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
     for (int b = 0; b < B; ++b) {
         const rfe_sim3_solver_params& p = P[b];
-        bool ok = fin(p.fx1) && fin(p.fy1) && fin(p.cx1) && fin(p.cy1) && fin(p.fx2) && fin(p.fy2) && fin(p.cx2) && fin(p.cy2);
-        for (int k = 0; k < 9; ++k) ok = ok && fin(p.rcw1[k]) && fin(p.rcw2[k]);
-        for (int k = 0; k < 3; ++k) ok = ok && fin(p.tcw1[k]) && fin(p.tcw2[k]);
-        if (!ok) return fail(c, RFE_ERR_INVALID, "sim3_ransac: non-finite pose or intrinsic");
+        if (!(finite({p.fx1, p.fy1, p.cx1, p.cy1, p.fx2, p.fy2, p.cx2, p.cy2}) && finite(p.rcw1) && finite(p.rcw2) && finite(p.tcw1) && finite(p.tcw2)))
+            return fail(c, RFE_ERR_INVALID, "sim3_ransac: non-finite pose or intrinsic");
         const int n = p.n < 0 ? 0 : (p.n > N ? N : p.n);
         for (int i = 0; i < n; ++i) {
             const float a = s1[(size_t)b * N + i], d = s2[(size_t)b * N + i];
-            if (!(fin(a) && fin(d) && a >= 0.f && d >= 0.f)) return fail(c, RFE_ERR_INVALID, "sim3_ransac: negative or non-finite sigma2");
+            if (!(finite(a) && finite(d) && a >= 0.f && d >= 0.f)) return fail(c, RFE_ERR_INVALID, "sim3_ransac: negative or non-finite sigma2");
         }
     }
     if (B == 0) return 0;

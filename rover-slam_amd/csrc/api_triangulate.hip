@@ -56,13 +56,7 @@ extern "C" int rfe_triangulate_neighbours_dev(rfe_ctx* c, const rfe_tri_params* 
 }
 
 static bool tri_view_finite(const rfe_tri_view& v) {
-    auto fin = [](float x) { return x - x == 0.f; };
-    bool ok = true;
-    for (float x : v.rcw) ok = ok && fin(x);
-    for (float x : v.tcw) ok = ok && fin(x);
-    for (float x : v.ow) ok = ok && fin(x);
-    for (float x : {v.fx, v.fy, v.cx, v.cy, v.invfx, v.invfy, v.mb, v.mbf}) ok = ok && fin(x);
-    return ok;
+    return finite(v.rcw) && finite(v.tcw) && finite(v.ow) && finite({v.fx, v.fy, v.cx, v.cy, v.invfx, v.invfy, v.mb, v.mbf});
 }
 
 extern "C" int rfe_triangulate_neighbours(rfe_ctx* c, const rfe_tri_params* P, const rfe_tri_view* view1, const float* kpts1,
@@ -77,9 +71,7 @@ extern "C" int rfe_triangulate_neighbours(rfe_ctx* c, const rfe_tri_params* P, c
     int rc = tri_check(c, P, view1, kpts1, octave1, uright1, depth1, has_mp1, N1, views2, kpts2, octave2, uright2, depth2, has_mp2, n2, Nn, N2max, S,
                        pairs, Kmax, stats);
     if (rc) return rc;
-    auto fin = [](float v) { return v - v == 0.f; };
-    bool ok = fin(P->th_far) && fin(P->ratio_factor) && tri_view_finite(*view1);
-    for (int l = 0; l < P->nlevels; ++l) ok = ok && fin(P->scale_factors[l]) && fin(P->level_sigma2[l]);
+    bool ok = finite({P->th_far, P->ratio_factor}) && tri_view_finite(*view1) && finite(P->scale_factors, P->nlevels) && finite(P->level_sigma2, P->nlevels);
     for (int n = 0; n < Nn; ++n) ok = ok && tri_view_finite(views2[n]);
     if (!ok) return fail(c, RFE_ERR_INVALID, "triangulate_neighbours: non-finite argument");
     RFE_HIP(c, hipSetDevice(c->device));

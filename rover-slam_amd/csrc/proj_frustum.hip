@@ -47,16 +47,12 @@ __global__ __launch_bounds__(256) void frustum_project_kernel(const rfe_frustum_
                     const float cosv = ((ox * normal[3 * i] + oy * normal[3 * i + 1]) + oz * normal[3 * i + 2]) / dist;
                     rej = 5;
                     if (!(cosv < P.view_cos_limit)) {
-                        const float c = ceilf(logf(scale_dist[i] / dist) / P.log_scale_factor);
-                        lv = !(c > 0.f) ? 0 : (c >= (float)P.nlevels ? P.nlevels - 1 : (int)c);   // clamped as a float; NaN is level 0
+                        lv = predict_scale_level(scale_dist[i], dist, P.log_scale_factor, P.nlevels);
                         xr = u - P.mbf * invz; dep = pc_dist; vc = cosv;
                         rej = (P.far_points && pc_dist > P.th_far) ? 6 : 0;                       // SPmatcher.cc:1184
                         if (rej == 0) {
                             const int L = P.level_mode == RFE_LEVEL_PREDICTED ? lv : 0;           // :1193 as written: nPredictedLevel = 0
-                            float sf = P.scale_factors[0];
-#pragma unroll
-                            for (int l = 1; l < RFE_MAX_LEVELS; ++l) sf = L == l ? P.scale_factors[l] : sf;   // no per-lane index into the arguments
-                            r = ((cosv >= FR_VIEWCOS_NEAR ? 2.5f : 4.0f) * P.th) * sf;
+                            r = ((cosv >= FR_VIEWCOS_NEAR ? 2.5f : 4.0f) * P.th) * level_table(P.scale_factors, L);
                         }
                     }
                 }

@@ -47,12 +47,8 @@ __global__ __launch_bounds__(256) void sim3_project_kernel(const rfe_sim3_params
                     rej = 5;
                     if (!((ox * normal[3 * i] + oy * normal[3 * i + 1]) + oz * normal[3 * i + 2] < 0.5f * dist)) {
                         rej = 0;
-                        const float c = ceilf(logf(scale_dist[i] / dist) / P.log_scale_factor);
-                        lv = !(c > 0.f) ? 0 : (c >= (float)P.nlevels ? P.nlevels - 1 : (int)c);   // clamped as a float; NaN is level 0
-                        float sf = P.scale_factors[0];
-#pragma unroll
-                        for (int l = 1; l < RFE_MAX_LEVELS; ++l) sf = lv == l ? P.scale_factors[l] : sf;   // no per-lane index into the arguments
-                        r = (float)P.th * sf;
+                        lv = predict_scale_level(scale_dist[i], dist, P.log_scale_factor, P.nlevels);
+                        r = (float)P.th * level_table(P.scale_factors, lv);
                     }
                 }
             }

@@ -338,6 +338,23 @@ __device__ __forceinline__ float desc_dist_wave(const float4 a, const float4 b) 
     return (float)sqrt(p);
 }
 
+// t[level] of a per-level table that is a kernel argument, as a select chain: no per-lane index into the arguments.  Level 0 is the start
+// value, so a level out of range reads level 0.
+__device__ __forceinline__ float level_table(const float (&t)[RFE_MAX_LEVELS], int level) {
+    float v = t[0];
+#pragma unroll
+    for (int l = 1; l < RFE_MAX_LEVELS; ++l) v = level == l ? t[l] : v;
+    return v;
+}
+// MapPoint::PredictScale (src/MapPoint.cc:689-707, 716-732): ceil(log(scale_dist / dist) / log_scale_factor), one rounding per written
+// operation, clamped to 0..nlevels - 1 as a float; NaN is level 0
+__device__ __forceinline__ int predict_scale_level(float scale_dist, float dist, float log_scale_factor, int nlevels) {
+    const float c = ceilf(logf(scale_dist / dist) / log_scale_factor);
+    if (!(c > 0.f)) return 0;
+    if (c >= (float)nlevels) return nlevels - 1;
+    return (int)c;
+}
+
 // proj_search.hip: SearchByProjection1 on the device.  cell_start [770], cell_items [Nf], fxy [Nf,2], seg_off [Nq+1],
 // cand_idx / cand_dist [cand_cap]
 void launch_proj_grid(hipStream_t s, const float* kpts, const int32_t* kxy, int Nf, const int32_t* nf_dev, float min_x, float min_y,

@@ -22,12 +22,6 @@ static_assert(0x1.ffcb92p-1f == 0.9996f && (double)0x1.ffcb92p-1f < 0.9996 && (d
 constexpr int TRI_SWEEPS = 6;                 // decisions and points settle at 4 sweeps on the test generators, plus two
 constexpr int TRI_CLAIMED = 16;
 
-__device__ __forceinline__ float tri_level(const float (&t)[RFE_MAX_LEVELS], int o) {
-    float v = t[0];
-#pragma unroll
-    for (int l = 1; l < RFE_MAX_LEVELS; ++l) v = o == l ? t[l] : v;       // no per-lane index into the arguments; out of range reads level 0
-    return v;
-}
 __device__ __forceinline__ float tri_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 __device__ __forceinline__ float tri_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 // cos(2 atan2(mb / 2, depth)) as (d d - h h) / (d d + h h)
@@ -183,9 +177,9 @@ __global__ __launch_bounds__(256) void tri_eval_kernel(const rfe_tri_params P, c
         if (z2 <= 0.f) break;
         const int o1 = oct1[i], o2 = oct2[f2];
         code = st1 ? 10 : 9;
-        if (tri_reproj_fails(V1, X, Y, Z, z1, k1x, k1y, kp1_ur, st1, V1.mbf, tri_level(P.level_sigma2, o1))) break;
+        if (tri_reproj_fails(V1, X, Y, Z, z1, k1x, k1y, kp1_ur, st1, V1.mbf, level_table(P.level_sigma2, o1))) break;
         code = st2 ? 12 : 11;
-        if (tri_reproj_fails(V2, X, Y, Z, z2, k2x, k2y, kp2_ur, st2, V1.mbf, tri_level(P.level_sigma2, o2))) break;
+        if (tri_reproj_fails(V2, X, Y, Z, z2, k2x, k2y, kp2_ur, st2, V1.mbf, level_table(P.level_sigma2, o2))) break;
         const float dist1 = tri_norm3(X - V1.ow[0], Y - V1.ow[1], Z - V1.ow[2]);
         const float dist2 = tri_norm3(X - V2.ow[0], Y - V2.ow[1], Z - V2.ow[2]);
         code = 13;
@@ -193,7 +187,7 @@ __global__ __launch_bounds__(256) void tri_eval_kernel(const rfe_tri_params P, c
         code = 14;
         if (P.far_points && (dist1 >= P.th_far || dist2 >= P.th_far)) break;
         const float ratio_dist = dist2 / dist1;
-        const float ratio_octave = tri_level(P.scale_factors, o1) / tri_level(P.scale_factors, o2);
+        const float ratio_octave = level_table(P.scale_factors, o1) / level_table(P.scale_factors, o2);
         code = 15;
         if (ratio_dist * P.ratio_factor < ratio_octave || ratio_dist > ratio_octave * P.ratio_factor) break;
         code = 0;

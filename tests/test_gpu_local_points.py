@@ -195,6 +195,31 @@ def test_one_ctx_across_cases_is_bit_for_bit(oracle):
         c0.close()
 
 
+def test_host_form_takes_its_second_attempt(oracle):
+    """A fresh ctx has ps_cap = 0, so the host form first runs with 16 slots per map point.  At th = 20 the lists of 64 points over 300
+    features need more than twice that: the first attempt overflows, the second runs with exactly stats[1] slots.  The second call on
+    the same ctx starts from the remembered slot count and gives the same bits in one attempt."""
+    from rover_slam_amd import capi
+    base, c = LP.make_case(0, W=160, H=120, Nf=300, Np=64)
+    P = LP.P(base, 20, True, LEVEL_ZERO)
+    ref = LP.search(oracle, P, c)
+    Np, Nf = len(c["pw"]), len(c["desc"])
+    print(f"candidates {ref['candidates']}, first guess {16 * Np}, ceiling {Np * Nf}, nmatches {ref['nmatches']}")
+    assert 16 * Np < ref["candidates"] <= Np * Nf
+    c0 = capi.Context(0)
+    try:
+        first = host(c0, P, c)
+        same(first, ref)
+        check_stats(first["stats"], ref)
+        assert first["stats"][1] == ref["candidates"] and first["stats"][3] == 0 and first["stats"][0] == ref["nmatches"]
+        again = host(c0, P, c)
+        for k in LP.KEYS + ("stats",):
+            assert np.array_equal(again[k], first[k], equal_nan=True), k
+        assert again["nmatches"] == first["nmatches"]
+    finally:
+        c0.close()
+
+
 # ---------------------------------------------------------------- 4. refusals and profile stages
 def test_refusals(ctx, oracle):
     from rover_slam_amd import capi

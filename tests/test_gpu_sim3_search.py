@@ -177,6 +177,29 @@ def test_one_ctx_across_cases_is_bit_for_bit(oracle):
         c0.close()
 
 
+def test_host_form_takes_its_second_attempt(oracle):
+    """A fresh ctx has ps_cap = 0, so the host form first runs with 16 slots per map point.  At th = 40 the lists of 64 points over 300
+    features need about three times that: the first attempt overflows, the second runs with exactly stats[1] slots.  The second call on
+    the same ctx starts from the remembered slot count and gives the same bits in one attempt."""
+    P, c = S3.make_case(0, W=160, H=120, Nf=300, Np=64, th=40)
+    ref = S3.search(oracle, P, c, S3.DIST_FLOAT)
+    Np, Nf = len(c["pw"]), len(c["kpts"])
+    print(f"candidates {ref['candidates']}, first guess {16 * Np}, ceiling {Np * Nf}, nmatches {ref['nmatches']}")
+    assert 16 * Np < ref["candidates"] <= Np * Nf
+    c0 = capi.Context(0)
+    try:
+        first = host(c0, P, c, S3.DIST_FLOAT)
+        same(first, ref)
+        check_stats(first["stats"], ref)
+        assert first["stats"][1] == ref["candidates"] and first["stats"][3] == 0 and first["stats"][0] == ref["nmatches"]
+        again = host(c0, P, c, S3.DIST_FLOAT)
+        for k in S3.KEYS + ("stats",):
+            assert np.array_equal(again[k], first[k], equal_nan=True), k
+        assert again["nmatches"] == first["nmatches"]
+    finally:
+        c0.close()
+
+
 # ---------------------------------------------------------------- 4. refusals and profile stages
 def test_refusals(ctx, oracle):
     P, c, ref = solved(oracle, "planted")
