@@ -20,8 +20,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
-#include "../rover_fe.h"
-#include "cv_compat.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 
@@ -38,19 +37,13 @@ int SearchLocalPoints_rfe(rfe_ctx* ctx, FrameT& F, const std::vector<MapPointT*>
     if ((int)F.mvScaleFactors.size() < F.mnScaleLevels || (int)F.mvpMapPoints.size() < Nf) return RFE_ERR_INVALID;
     rfe_frustum_params P = rfe_frustum_params();
     const auto Tcw = F.GetPose();
-    const auto Rcw = Tcw.rotationMatrix();
-    const auto tcw = Tcw.translation();
-    const auto Ow = F.GetOw();
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) P.rcw[3 * r + k] = Rcw(r, k);
-        P.tcw[r] = tcw(r); P.ow[r] = Ow(r);
-    }
+    rfe_detail::copy_rotation(Tcw.rotationMatrix(), P.rcw); rfe_detail::copy_vec3(Tcw.translation(), P.tcw); rfe_detail::copy_vec3(F.GetOw(), P.ow);
     P.fx = F.fx; P.fy = F.fy; P.cx = F.cx; P.cy = F.cy; P.mbf = F.mbf;
     P.min_x = F.mnMinX; P.min_y = F.mnMinY; P.max_x = F.mnMaxX; P.max_y = F.mnMaxY;
     P.view_cos_limit = 0.5f;                                         // Tracking.cc:4136
     P.th = th; P.far_points = bFarPoints ? 1 : 0; P.th_far = thFarPoints;
     P.nlevels = F.mnScaleLevels; P.log_scale_factor = F.mfLogScaleFactor;
-    for (int l = 0; l < P.nlevels && l < RFE_MAX_LEVELS; ++l) P.scale_factors[l] = F.mvScaleFactors[l];
+    rfe_detail::copy_levels(F.mvScaleFactors, P.nlevels, P.scale_factors);
 #if defined(RFE_SP_PYRAMID) && RFE_SP_PYRAMID
     P.level_mode = RFE_LEVEL_PREDICTED;
 #else
@@ -60,27 +53,14 @@ int SearchLocalPoints_rfe(rfe_ctx* ctx, FrameT& F, const std::vector<MapPointT*>
     const size_t np = (size_t)Np, nf = (size_t)Nf;
     std::vector<float> q(np * 256), pw(np * 3), normal(np * 3), min_dist(np), max_dist(np), scale_dist(np);
     std::vector<uint8_t> valid(np), observed(np), skip(nf);
-    for (int i = 0; i < Np; ++i) {
-        MapPointT* pMP = vpLocalMapPoints[i];
-        valid[i] = pMP->mnLastFrameSeen != F.mnId && !pMP->isBad();       // :4129-4133
-        observed[i] = pMP->Observations() > 0;
-        const auto p3Dw = pMP->GetWorldPos();
-        const auto Pn = pMP->GetNormal();
-        for (int k = 0; k < 3; ++k) { pw[3 * (size_t)i + k] = p3Dw(k); normal[3 * (size_t)i + k] = Pn(k); }
-        min_dist[i] = pMP->GetMinDistanceInvariance(); max_dist[i] = pMP->GetMaxDistanceInvariance();
-        scale_dist[i] = pMP->GetMaxDistance();                        // what PredictScale divides, not the gate's 1.2f * mfMaxDistance
-        const cv::Mat d = pMP->GetDescriptor();
-        const float* s = d.template ptr<float>(0);
-        std::copy(s, s + 256, q.begin() + (size_t)i * 256);
-    }
+    const auto flags = [&](size_t i, MapPointT* pMP) {                // :4129-4133
+        valid[i] = pMP->mnLastFrameSeen != F.mnId && !pMP->isBad(); observed[i] = pMP->Observations() > 0;
+    };
+    rfe_detail::gather_map_points(vpLocalMapPoints, q.data(), pw.data(), normal.data(), min_dist.data(), max_dist.data(), scale_dist.data(), flags);
     std::vector<float> f(nf * 256), kpts(std::max<size_t>(nf, 1) * 2);   // a frame without features still passes "one of kpts and kxy"
     std::vector<int32_t> octave(nf), assign(nf, -1);
-    for (int j = 0; j < Nf; ++j) {
-        kpts[2 * j] = F.mvKeysUn[j].pt.x; kpts[2 * j + 1] = F.mvKeysUn[j].pt.y; octave[j] = F.mvKeysUn[j].octave;
-        skip[j] = F.mvpMapPoints[j] && F.mvpMapPoints[j]->Observations() > 0;
-        const float* s = F.mDescriptors.template ptr<float>(j);
-        std::copy(s, s + 256, f.begin() + (size_t)j * 256);
-    }
+    rfe_detail::gather_features(F.mvKeysUn, F.mDescriptors, nf, kpts.data(), octave.data(), f.data());
+    rfe_detail::gather_skip(F.mvpMapPoints, nf, skip.data());
     std::vector<float> proj(np * 2), proj_xr(np), depth(np), view_cos(np);
     std::vector<int32_t> level(np), reject(np), stats(8);
     const int n = rfe_search_local_points(ctx, &P, q.data(), pw.data(), normal.data(), min_dist.data(), max_dist.data(), scale_dist.data(),

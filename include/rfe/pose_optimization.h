@@ -15,7 +15,7 @@
 #include <cstdint>
 #include <type_traits>
 #include <vector>
-#include "../rover_fe.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 
@@ -28,7 +28,7 @@ int PoseOptimization_rfe(rfe_ctx* ctx, FrameT* pFrame, int32_t* stats_out = null
     rfe_pose_params P = rfe_pose_params();
     P.fx = pFrame->fx; P.fy = pFrame->fy; P.cx = pFrame->cx; P.cy = pFrame->cy; P.bf = pFrame->mbf;
     P.nlevels = (int32_t)pFrame->mvInvLevelSigma2.size();
-    for (int l = 0; l < P.nlevels; ++l) P.inv_level_sigma2[l] = pFrame->mvInvLevelSigma2[l];
+    rfe_detail::copy_levels(pFrame->mvInvLevelSigma2, P.nlevels, P.inv_level_sigma2);
     const auto Tcw = pFrame->GetPose();
     const auto q0 = Tcw.unit_quaternion();
     const auto t0 = Tcw.translation();
@@ -42,8 +42,7 @@ int PoseOptimization_rfe(rfe_ctx* ctx, FrameT* pFrame, int32_t* stats_out = null
         outlier[i] = pFrame->mvbOutlier[i] ? 1 : 0;
         if (pFrame->mvpMapPoints[i]) {
             has_mp[i] = 1;
-            const auto X = pFrame->mvpMapPoints[i]->GetWorldPos();
-            xw[3 * i] = X(0); xw[3 * i + 1] = X(1); xw[3 * i + 2] = X(2);
+            rfe_detail::copy_vec3(pFrame->mvpMapPoints[i]->GetWorldPos(), &xw[3 * i]);
         }
     }
     double pose[7]; float pose_f32[7]; int32_t stats[8];

@@ -11,8 +11,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
-#include "../rover_fe.h"
-#include "cv_compat.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 
@@ -45,18 +44,12 @@ int SearchByProjection1_rfe(rfe_ctx* ctx, FrameT& F, const std::vector<MapPointT
         radius[k] = r * F.mvScaleFactors[0];        // nPredictedLevel is 0 as the reference is written (:1193)
         proj[2 * k] = pMP->mTrackProjX; proj[2 * k + 1] = pMP->mTrackProjY;
         observed[k] = pMP->Observations() > 0;
-        const cv::Mat d = pMP->GetDescriptor();
-        const float* s = d.template ptr<float>(0);
-        std::copy(s, s + 256, q.begin() + (size_t)k * 256);
+        rfe_detail::copy_descriptor(pMP->GetDescriptor(), 0, &q[(size_t)k * 256]);
     }
     std::vector<float> f((size_t)Nf * 256), kpts((size_t)Nf * 2);
     std::vector<int32_t> octave((size_t)Nf), assign((size_t)Nf, -1);
-    for (int j = 0; j < Nf; ++j) {
-        kpts[2 * j] = F.mvKeysUn[j].pt.x; kpts[2 * j + 1] = F.mvKeysUn[j].pt.y; octave[j] = F.mvKeysUn[j].octave;
-        skip[j] = F.mvpMapPoints[j] && F.mvpMapPoints[j]->Observations() > 0;
-        const float* s = F.mDescriptors.template ptr<float>(j);
-        std::copy(s, s + 256, f.begin() + (size_t)j * 256);
-    }
+    rfe_detail::gather_features(F.mvKeysUn, F.mDescriptors, (size_t)Nf, kpts.data(), octave.data(), f.data());
+    rfe_detail::gather_skip(F.mvpMapPoints, (size_t)Nf, skip.data());
     const int n = rfe_search_by_projection(ctx, q.data(), proj.data(), radius.data(), nullptr, observed.data(), Nq, f.data(), kpts.data(),
                                            nullptr, octave.data(), skip.data(), Nf, F.mnMinX, F.mnMinY, F.mnMaxX, F.mnMaxY, th_high,
                                            assign.data(), nullptr, nullptr, nullptr, nullptr);

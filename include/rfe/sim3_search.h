@@ -26,8 +26,7 @@
 #include <cstdint>
 #include <set>
 #include <vector>
-#include "../rover_fe.h"
-#include "cv_compat.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 namespace rfe_detail {
@@ -42,15 +41,13 @@ int SearchSim3(rfe_ctx* ctx, KeyFrameT* pKF, Sim3T& Scw, const std::vector<MapPo
     if ((int)vpMatched.size() < Nf || (int)pKF->mvScaleFactors.size() < pKF->mnScaleLevels) return RFE_ERR_INVALID;
     const SE3T Tcw(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
     const auto quat = Tcw.unit_quaternion();
-    const auto t = Tcw.translation();
-    const auto Ow = Tcw.inverse().translation();
     rfe_sim3_params P = rfe_sim3_params();
     P.quat[0] = quat.x(); P.quat[1] = quat.y(); P.quat[2] = quat.z(); P.quat[3] = quat.w();
-    for (int k = 0; k < 3; ++k) { P.t[k] = t(k); P.ow[k] = Ow(k); }
+    copy_vec3(Tcw.translation(), P.t); copy_vec3(Tcw.inverse().translation(), P.ow);
     P.fx = pKF->fx; P.fy = pKF->fy; P.cx = pKF->cx; P.cy = pKF->cy;
     P.min_x = pKF->mnMinX; P.min_y = pKF->mnMinY; P.max_x = pKF->mnMaxX; P.max_y = pKF->mnMaxY;
     P.th = th; P.nlevels = pKF->mnScaleLevels; P.log_scale_factor = pKF->mfLogScaleFactor;
-    for (int l = 0; l < P.nlevels && l < RFE_MAX_LEVELS; ++l) P.scale_factors[l] = pKF->mvScaleFactors[l];
+    copy_levels(pKF->mvScaleFactors, P.nlevels, P.scale_factors);
     P.proj_mode = proj_mode; P.dist_mode = dist_mode;
 
     std::set<MapPointT*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
@@ -58,25 +55,11 @@ int SearchSim3(rfe_ctx* ctx, KeyFrameT* pKF, Sim3T& Scw, const std::vector<MapPo
     std::vector<float> q((size_t)Np * 256), pw((size_t)Np * 3), normal((size_t)Np * 3), min_dist((size_t)Np), max_dist((size_t)Np),
         scale_dist((size_t)Np);
     std::vector<uint8_t> valid((size_t)Np), matched_in((size_t)Nf);
-    for (int i = 0; i < Np; ++i) {
-        MapPointT* pMP = vpPoints[i];
-        valid[i] = !pMP->isBad() && !spAlreadyFound.count(pMP);
-        const auto p3Dw = pMP->GetWorldPos();
-        const auto Pn = pMP->GetNormal();
-        for (int k = 0; k < 3; ++k) { pw[3 * (size_t)i + k] = p3Dw(k); normal[3 * (size_t)i + k] = Pn(k); }
-        min_dist[i] = pMP->GetMinDistanceInvariance(); max_dist[i] = pMP->GetMaxDistanceInvariance();
-        scale_dist[i] = pMP->GetMaxDistance();                    // what PredictScale divides, not the gate's 1.2f * mfMaxDistance
-        const cv::Mat d = pMP->GetDescriptor();
-        const float* s = d.template ptr<float>(0);
-        std::copy(s, s + 256, q.begin() + (size_t)i * 256);
-    }
+    gather_map_points(vpPoints, q.data(), pw.data(), normal.data(), min_dist.data(), max_dist.data(), scale_dist.data(),
+                      [&](size_t i, MapPointT* pMP) { valid[i] = !pMP->isBad() && !spAlreadyFound.count(pMP); });
     std::vector<float> f((size_t)Nf * 256), kpts((size_t)Nf * 2);
-    for (int j = 0; j < Nf; ++j) {
-        kpts[2 * j] = pKF->mvKeysUn[j].pt.x; kpts[2 * j + 1] = pKF->mvKeysUn[j].pt.y;
-        matched_in[j] = vpMatched[j] != nullptr;
-        const float* s = pKF->mDescriptors.template ptr<float>(j);
-        std::copy(s, s + 256, f.begin() + (size_t)j * 256);
-    }
+    gather_features(pKF->mvKeysUn, pKF->mDescriptors, (size_t)Nf, kpts.data(), nullptr, f.data());
+    for (int j = 0; j < Nf; ++j) matched_in[j] = vpMatched[j] != nullptr;
     return rfe_search_by_projection_sim3(ctx, &P, q.data(), pw.data(), normal.data(), min_dist.data(), max_dist.data(), scale_dist.data(),
                                          valid.data(), Np, f.data(), kpts.data(), nullptr, matched_in.data(), Nf, th_accept, accepted.data(),
                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);

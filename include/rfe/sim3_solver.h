@@ -22,7 +22,7 @@
 #include <functional>
 #include <tuple>
 #include <vector>
-#include "../rover_fe.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 
@@ -44,12 +44,8 @@ public:
         if (pKF1->mpCamera->GetType() != 0 || pKF2->mpCamera->GetType() != 0 /*GeometricCamera::CAM_PINHOLE*/) status_ = -1;
         const std::vector<MapPointT*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
         mN1 = (int)vpMatched12.size();
-        const auto Rcw1 = pKF1->GetRotation(); const auto tcw1 = pKF1->GetTranslation();
-        const auto Rcw2 = pKF2->GetRotation(); const auto tcw2 = pKF2->GetTranslation();
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) { P_.rcw1[3 * r + c] = Rcw1(r, c); P_.rcw2[3 * r + c] = Rcw2(r, c); }
-            P_.tcw1[r] = tcw1(r); P_.tcw2[r] = tcw2(r);
-        }
+        rfe_detail::copy_rotation(pKF1->GetRotation(), P_.rcw1); rfe_detail::copy_vec3(pKF1->GetTranslation(), P_.tcw1);
+        rfe_detail::copy_rotation(pKF2->GetRotation(), P_.rcw2); rfe_detail::copy_vec3(pKF2->GetTranslation(), P_.tcw2);
         P_.fx1 = pKF1->fx; P_.fy1 = pKF1->fy; P_.cx1 = pKF1->cx; P_.cy1 = pKF1->cy;
         P_.fx2 = pKF2->fx; P_.fy2 = pKF2->fy; P_.cx2 = pKF2->cx; P_.cy2 = pKF2->cy;
         P_.fix_scale = bFixScale ? 1 : 0;

@@ -17,8 +17,7 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
-#include "../rover_fe.h"
-#include "cv_compat.h"
+#include "dropin_detail.h"
 
 namespace ORB_SLAM3 {
 
@@ -50,13 +49,7 @@ inline bool one_pinhole(KeyFrameT* kf) { return kf->NLeft == -1 && !kf->mpCamera
 template <class KeyFrameT>
 inline void fill_view(KeyFrameT* kf, rfe_tri_view& v) {
     const auto Tcw = kf->GetPose();
-    const auto R = Tcw.rotationMatrix();
-    const auto t = Tcw.translation();
-    const auto Ow = kf->GetCameraCenter();
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k) v.rcw[3 * r + k] = R(r, k);
-        v.tcw[r] = t(r); v.ow[r] = Ow(r);
-    }
+    rfe_detail::copy_rotation(Tcw.rotationMatrix(), v.rcw); rfe_detail::copy_vec3(Tcw.translation(), v.tcw); rfe_detail::copy_vec3(kf->GetCameraCenter(), v.ow);
     v.fx = kf->fx; v.fy = kf->fy; v.cx = kf->cx; v.cy = kf->cy; v.invfx = kf->invfx; v.invfy = kf->invfy; v.mb = kf->mb; v.mbf = kf->mbf;
 }
 // one device allocation, carved in 256-byte steps
@@ -87,7 +80,7 @@ int TriangulateMatches_rfe(rfe_ctx* ctx, KeyFrameT* pKF1, const std::vector<KeyF
     P.inertial = prm.bInertial ? 1 : 0; P.far_points = prm.bFarPoints ? 1 : 0; P.th_far = prm.thFarPoints;
     P.ratio_factor = 1.5f * pKF1->mfScaleFactor;                       // :566
     P.nlevels = pKF1->mnScaleLevels;
-    for (int l = 0; l < P.nlevels && l < RFE_MAX_LEVELS; ++l) { P.scale_factors[l] = pKF1->mvScaleFactors[l]; P.level_sigma2[l] = pKF1->mvLevelSigma2[l]; }
+    rfe_detail::copy_levels(pKF1->mvScaleFactors, P.nlevels, P.scale_factors); rfe_detail::copy_levels(pKF1->mvLevelSigma2, P.nlevels, P.level_sigma2);
     rfe_tri_view v1;
     fill_view(pKF1, v1);
     int N2max = 0;
@@ -97,11 +90,9 @@ int TriangulateMatches_rfe(rfe_ctx* ctx, KeyFrameT* pKF1, const std::vector<KeyF
     std::vector<int32_t> o1(n1), o2(f2), n2((size_t)Nn);
     std::vector<uint8_t> m1(n1), m2(f2), valid((size_t)Nn);
     std::vector<rfe_tri_view> v2((size_t)Nn);
-    for (int i = 0; i < N1; ++i) {
-        k1[2 * i] = pKF1->mvKeysUn[i].pt.x; k1[2 * i + 1] = pKF1->mvKeysUn[i].pt.y; o1[i] = pKF1->mvKeysUn[i].octave;
-        r1[2 * i] = pKF1->mvKeys[i].pt.x; r1[2 * i + 1] = pKF1->mvKeys[i].pt.y;
-        u1[i] = pKF1->mvuRight[i]; d1[i] = pKF1->mvDepth[i]; m1[i] = pKF1->GetMapPoint(i) != nullptr;
-    }
+    rfe_detail::gather_keypoints(pKF1->mvKeysUn, n1, k1.data(), o1.data());
+    rfe_detail::gather_keypoints(pKF1->mvKeys, n1, r1.data());
+    for (int i = 0; i < N1; ++i) { u1[i] = pKF1->mvuRight[i]; d1[i] = pKF1->mvDepth[i]; m1[i] = pKF1->GetMapPoint(i) != nullptr; }
     for (int n = 0; n < Nn; ++n) {
         KeyFrameT* kf = vpNeighKFs[n];
         fill_view(kf, v2[n]);
@@ -117,11 +108,9 @@ int TriangulateMatches_rfe(rfe_ctx* ctx, KeyFrameT* pKF1, const std::vector<KeyF
         const int cnt = (int)kf->mvKeysUn.size();
         n2[n] = cnt;
         const size_t b = (size_t)n * N2max;
-        for (int j = 0; j < cnt; ++j) {
-            k2[2 * (b + j)] = kf->mvKeysUn[j].pt.x; k2[2 * (b + j) + 1] = kf->mvKeysUn[j].pt.y; o2[b + j] = kf->mvKeysUn[j].octave;
-            r2[2 * (b + j)] = kf->mvKeys[j].pt.x; r2[2 * (b + j) + 1] = kf->mvKeys[j].pt.y;
-            u2[b + j] = kf->mvuRight[j]; d2[b + j] = kf->mvDepth[j]; m2[b + j] = kf->GetMapPoint(j) != nullptr;
-        }
+        rfe_detail::gather_keypoints(kf->mvKeysUn, (size_t)cnt, k2.data() + 2 * b, o2.data() + b);
+        rfe_detail::gather_keypoints(kf->mvKeys, (size_t)cnt, r2.data() + 2 * b);
+        for (int j = 0; j < cnt; ++j) { u2[b + j] = kf->mvuRight[j]; d2[b + j] = kf->mvDepth[j]; m2[b + j] = kf->GetMapPoint(j) != nullptr; }
     }
     DevBlock D(ctx);
     const size_t ok1 = D.reserve<float>(n1 * 2), or1 = D.reserve<float>(n1 * 2), oo1 = D.reserve<int32_t>(n1), ou1 = D.reserve<float>(n1),
@@ -193,14 +182,12 @@ int CreateNewMapPoints_rfe(rfe_ctx* ctx, KeyFrameT* pKF1, const std::vector<KeyF
         KeyFrameT* kf = vpNeighKFs[p];
         for (int i = 0; i < N1; ++i) {
             norm(pKF1->mvKeys[i], &k0[2 * ((size_t)p * N1 + i)]);
-            const float* s = pKF1->mDescriptors.template ptr<float>(i);
-            std::copy(s, s + 256, d0.begin() + ((size_t)p * N1 + i) * 256);
+            rfe_detail::copy_descriptor(pKF1->mDescriptors, i, &d0[((size_t)p * N1 + i) * 256]);
         }
         n[p] = (int)kf->mvKeys.size();
         for (int j = 0; j < n[p]; ++j) {
             norm(kf->mvKeys[j], &k1[2 * ((size_t)p * N2max + j)]);
-            const float* s = kf->mDescriptors.template ptr<float>(j);
-            std::copy(s, s + 256, d1.begin() + ((size_t)p * N2max + j) * 256);
+            rfe_detail::copy_descriptor(kf->mDescriptors, j, &d1[((size_t)p * N2max + j) * 256]);
         }
     }
     DevBlock D(ctx);

@@ -12,35 +12,15 @@
 //           GetMaxDistanceInvariance | Np x f32 mfMaxDistance | Np x 256 f32 descriptor | Nf x (x, y) f32 | Nf x 256 f32 descriptor
 // out.bin:  i32 return value, nToMatch | Nf x i32 F.mvpMapPoints (index into the list, or the prior code) | the fields after the call, laid out
 //           as before it
-#include <cstdio>
-#include <cstdlib>
 #include <map>
-#include <vector>
+#include "driver_common.h"
 #include "rfe/local_points_search.h"
-
-struct Vec3 {
-    float v[3];
-    float operator()(int i) const { return v[i]; }
-};
-struct Mat3 {
-    float m[9];
-    float operator()(int r, int c) const { return m[3 * r + c]; }
-};
-struct MiniSE3 {
-    Mat3 R; Vec3 t;
-    Mat3 rotationMatrix() const { return R; }
-    Vec3 translation() const { return t; }
-};
-struct MockCamera {
-    unsigned int type = 0;
-    unsigned int GetType() { return type; }
-};
 
 struct MockMapPoint {                   // members Tracking::SearchLocalPoints, Frame::isInFrustum and SearchByProjection1 read or write
     long unsigned int mnId = 0, mnLastFrameSeen = 0;
     bool bad = false, observed = true;
     int mnVisible = 1;
-    Vec3 pos{{0, 0, 0}}, nrm{{0, 0, 0}};
+    Vec3 pos, nrm;
     float dmin = 0, dmax = 0, maxd = 0;
     cv::Mat desc;
     bool mbTrackInView = false;
@@ -75,17 +55,12 @@ struct MockFrame {
     Vec3 GetOw() const { return Ow; }
 };
 
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T>
-static void put(FILE* f, const std::vector<T>& v) { if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f); }
-
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[6]; float fl[27];
-    if (fread(hd, 4, 6, fi) != 6 || fread(fl, 4, 27, fi) != 27) return 2;
+    if (fread(hd, 4, 6, fi) != 6 || fread(fl, 4, 27, fi) != 27) return EXIT_BAD_CASE;
     const int Np = hd[0], Nf = hd[1], nlevels = hd[3];
     std::vector<float> sf, px, py, pxr, dep, vc, pw, nr, dmin, dmax, maxd, qd, kp, fd;
     std::vector<uint8_t> bad, obs, inview; std::vector<int32_t> seen, lev, vis, prior, oct;
@@ -93,7 +68,7 @@ int main(int argc, char** argv) {
         !get(fi, py, Np) || !get(fi, pxr, Np) || !get(fi, dep, Np) || !get(fi, lev, Np) || !get(fi, vc, Np) || !get(fi, vis, Np) ||
         !get(fi, prior, Nf) || !get(fi, oct, Nf) || !get(fi, pw, (size_t)Np * 3) || !get(fi, nr, (size_t)Np * 3) || !get(fi, dmin, Np) ||
         !get(fi, dmax, Np) || !get(fi, maxd, Np) || !get(fi, qd, (size_t)Np * 256) || !get(fi, kp, (size_t)Nf * 2) ||
-        !get(fi, fd, (size_t)Nf * 256)) { fprintf(stderr, "short case file\n"); return 2; }
+        !get(fi, fd, (size_t)Nf * 256)) return short_case();
     fclose(fi);
     std::vector<MockMapPoint> mps((size_t)Np);
     MockMapPoint other_observed, other_unobserved;
@@ -126,8 +101,8 @@ int main(int argc, char** argv) {
         F.mvKeysUn[j].pt = cv::Point2f(kp[2 * j], kp[2 * j + 1]); F.mvKeysUn[j].octave = oct[j];
         F.mvpMapPoints[j] = prior[j] == -2 ? &other_observed : (prior[j] == -3 ? &other_unobserved : nullptr);
     }
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     int nToMatch = -7;
     const int32_t ret = ORB_SLAM3::SearchLocalPoints_rfe(ctx, F, vp, th, hd[4] != 0, thFarPoints, &nToMatch);
     rfe_destroy(ctx);
@@ -144,7 +119,7 @@ int main(int argc, char** argv) {
     }
     if (ret >= 0 && (int)F.mmProjectPoints.size() > in_view) { fprintf(stderr, "mmProjectPoints holds too much\n"); return 4; }
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     std::vector<int32_t> who((size_t)Nf);
     for (int j = 0; j < Nf; ++j) {
         MockMapPoint* p = F.mvpMapPoints[j];

@@ -7,18 +7,9 @@
 //           N x u8 mvbOutlier before the call
 // out.bin:  i32 return value, SetPose calls, N | i32 stats[8] | f32 the pose as SetPose received it (the frame's own when it was not called) |
 //           N x u8 mvbOutlier
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#include "rfe/cv_compat.h"
+#include "driver_common.h"
 #include "rfe/pose_optimization.h"
 
-struct Vec3 {
-    float v[3];
-    Vec3() : v{0, 0, 0} {}
-    Vec3(float x, float y, float z) : v{x, y, z} {}
-    float operator()(int i) const { return v[i]; }
-};
 struct Quat {
     float qx, qy, qz, qw;
     Quat() : qx(0), qy(0), qz(0), qw(1) {}
@@ -28,10 +19,10 @@ struct Quat {
     float z() const { return qz; }
     float w() const { return qw; }
 };
-struct MiniSE3 {                         // keeps what it is given: the test compares the values the drop-in hands over
+struct QuatSE3 {                         // keeps what it is given: the test compares the values the drop-in hands over
     Quat q; Vec3 t;
-    MiniSE3() {}
-    MiniSE3(const Quat& q_, const Vec3& t_) : q(q_), t(t_) {}
+    QuatSE3() {}
+    QuatSE3(const Quat& q_, const Vec3& t_) : q(q_), t(t_) {}
     Quat unit_quaternion() const { return q; }
     Vec3 translation() const { return t; }
 };
@@ -39,7 +30,6 @@ struct MockMapPoint {
     Vec3 pos;
     Vec3 GetWorldPos() const { return pos; }
 };
-struct MockCamera {};
 struct MockFrame {                       // the members Optimizer::PoseOptimization reads and writes
     int N = 0;
     std::vector<cv::KeyPoint> mvKeysUn;
@@ -48,28 +38,25 @@ struct MockFrame {                       // the members Optimizer::PoseOptimizat
     std::vector<bool> mvbOutlier;
     float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
     MockCamera rig; MockCamera* mpCamera2 = nullptr;
-    MiniSE3 Tcw; int set_pose_calls = 0;
-    MiniSE3 GetPose() const { return Tcw; }
-    void SetPose(const MiniSE3& T) { Tcw = T; ++set_pose_calls; }
+    QuatSE3 Tcw; int set_pose_calls = 0;
+    QuatSE3 GetPose() const { return Tcw; }
+    void SetPose(const QuatSE3& T) { Tcw = T; ++set_pose_calls; }
 };
-
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
 
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[3]; float cam[5], pose[7];
-    if (fread(hd, 4, 3, fi) != 3 || fread(cam, 4, 5, fi) != 5 || hd[0] < 0 || hd[1] < 0) return 2;
+    if (fread(hd, 4, 3, fi) != 3 || fread(cam, 4, 5, fi) != 5 || hd[0] < 0 || hd[1] < 0) return EXIT_BAD_CASE;
     const size_t N = (size_t)hd[0];
     MockFrame F;
     std::vector<float> kp, xw; std::vector<int32_t> oct; std::vector<uint8_t> mp, outl;
     if (!get(fi, F.mvInvLevelSigma2, (size_t)hd[1]) || fread(pose, 4, 7, fi) != 7 || !get(fi, kp, N * 2) || !get(fi, oct, N) ||
-        !get(fi, F.mvuRight, N) || !get(fi, xw, N * 3) || !get(fi, mp, N) || !get(fi, outl, N)) { fprintf(stderr, "short case file\n"); return 2; }
+        !get(fi, F.mvuRight, N) || !get(fi, xw, N * 3) || !get(fi, mp, N) || !get(fi, outl, N)) return short_case();
     fclose(fi);
     F.N = (int)N; F.fx = cam[0]; F.fy = cam[1]; F.cx = cam[2]; F.cy = cam[3]; F.mbf = cam[4];
-    F.Tcw = MiniSE3(Quat(pose[3], pose[0], pose[1], pose[2]), Vec3(pose[4], pose[5], pose[6]));
+    F.Tcw = QuatSE3(Quat(pose[3], pose[0], pose[1], pose[2]), Vec3(pose[4], pose[5], pose[6]));
     if (hd[2]) F.mpCamera2 = &F.rig;
     std::vector<MockMapPoint> points(N);
     F.mvKeysUn.resize(N); F.mvpMapPoints.resize(N); F.mvbOutlier.resize(N);
@@ -79,14 +66,14 @@ int main(int argc, char** argv) {
         F.mvpMapPoints[i] = mp[i] ? &points[i] : nullptr;
         F.mvbOutlier[i] = outl[i] != 0;
     }
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     int32_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int32_t ret = ORB_SLAM3::PoseOptimization_rfe(ctx, &F, stats);
     if (ret < -1) fprintf(stderr, "drop-in: %d %s\n", ret, rfe_last_error(ctx));
     rfe_destroy(ctx);
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     const int32_t head[3] = {ret, F.set_pose_calls, (int32_t)N};
     fwrite(head, 4, 3, fo);
     fwrite(stats, 4, 8, fo);
@@ -94,7 +81,7 @@ int main(int argc, char** argv) {
     fwrite(got, 4, 7, fo);
     std::vector<uint8_t> o(N);
     for (size_t i = 0; i < N; ++i) o[i] = F.mvbOutlier[i] ? 1 : 0;
-    if (N) fwrite(o.data(), 1, N, fo);
+    put(fo, o);
     fclose(fo);
     return 0;
 }

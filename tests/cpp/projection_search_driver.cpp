@@ -8,9 +8,7 @@
 //           | Nf x (x, y) f32 | Nf x i32 octave | Nf x i32 prior (-1: mvpMapPoints[j] is NULL, n >= 0: a map point with n observations)
 //           | Nf x 256 f32 descriptor
 // out.bin:  i32 return value | Nf x i32 owner (index into vpMapPoints, -1 = NULL, -2 = the map point the feature had before the call)
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "driver_common.h"
 #include "rfe/projection_search.h"
 
 struct MockMapPoint {                   // members SearchByProjection1 reads (src/Matchers/SPmatcher.cc:1178-1211)
@@ -33,20 +31,17 @@ struct MockFrame {                      // members SearchByProjection1 / GetFeat
 };
 float MockFrame::mnMinX = 0, MockFrame::mnMinY = 0, MockFrame::mnMaxX = 0, MockFrame::mnMaxY = 0;
 
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[3]; float th; int32_t far; float fl[6];
-    if (fread(hd, 4, 3, fi) != 3 || fread(&th, 4, 1, fi) != 1 || fread(&far, 4, 1, fi) != 1 || fread(fl, 4, 6, fi) != 6) return 2;
+    if (fread(hd, 4, 3, fi) != 3 || fread(&th, 4, 1, fi) != 1 || fread(&far, 4, 1, fi) != 1 || fread(fl, 4, 6, fi) != 6) return EXIT_BAD_CASE;
     const int Nm = hd[0], Nf = hd[1];
     std::vector<uint8_t> inview, bad; std::vector<int32_t> nobs, octave, prior; std::vector<float> depth, vcos, proj, qd, kp, fd;
     if (!get(fi, inview, Nm) || !get(fi, bad, Nm) || !get(fi, nobs, Nm) || !get(fi, depth, Nm) || !get(fi, vcos, Nm) ||
         !get(fi, proj, (size_t)Nm * 2) || !get(fi, qd, (size_t)Nm * 256) || !get(fi, kp, (size_t)Nf * 2) || !get(fi, octave, Nf) ||
-        !get(fi, prior, Nf) || !get(fi, fd, (size_t)Nf * 256)) { fprintf(stderr, "short case file\n"); return 2; }
+        !get(fi, prior, Nf) || !get(fi, fd, (size_t)Nf * 256)) return short_case();
     fclose(fi);
     std::vector<MockMapPoint> mps((size_t)Nm), old((size_t)Nf);
     std::vector<MockMapPoint*> vp((size_t)Nm);
@@ -68,8 +63,8 @@ int main(int argc, char** argv) {
         F.mvKeysUn[j].pt = cv::Point2f(kp[2 * j], kp[2 * j + 1]); F.mvKeysUn[j].octave = octave[j];
         if (prior[j] >= 0) { old[j].nobs = prior[j]; F.mvpMapPoints[j] = &old[j]; }
     }
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     const int32_t ret = ORB_SLAM3::SearchByProjection1_rfe(ctx, F, vp, th, far != 0, fl[0]);
     std::vector<int32_t> owner((size_t)Nf, -1);
     for (int j = 0; j < Nf; ++j) {
@@ -80,9 +75,9 @@ int main(int argc, char** argv) {
     }
     rfe_destroy(ctx);
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     fwrite(&ret, 4, 1, fo);
-    fwrite(owner.data(), 4, owner.size(), fo);
+    put(fo, owner);
     fclose(fo);
     return 0;
 }

@@ -11,16 +11,10 @@
 //           | Nf x (x, y) f32 | Nf x 256 f32 descriptor
 // out.bin:  per overload (first :1558, then :2076): i32 return value | Nf x i32 vpMatched (index into vpPoints, -1 = NULL, -2 = the other
 //           map point) | Nf x i32 vpMatchedKF (index of the keyframe, -1 = NULL; all -1 for the second overload, which has none)
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "driver_common.h"
 #include "rfe/sim3_search.h"
 
-struct Vec3 {
-    float v[3];
-    float operator()(int i) const { return v[i]; }
-    Vec3 operator/(float s) const { return Vec3{{v[0] / s, v[1] / s, v[2] / s}}; }
-};
+static Vec3 operator/(const Vec3& a, float s) { return Vec3(a(0) / s, a(1) / s, a(2) / s); }      // Scw.translation() / Scw.scale()
 struct Quat {
     float qx, qy, qz, qw;
     float x() const { return qx; } float y() const { return qy; } float z() const { return qz; } float w() const { return qw; }
@@ -28,25 +22,25 @@ struct Quat {
 struct Rotation { Quat q; };            // what rotationMatrix() hands to the SE3 constructor: here the unit quaternion itself
 
 static Vec3 cross(const Vec3& a, const Vec3& b) {
-    return Vec3{{a(1) * b(2) - a(2) * b(1), a(2) * b(0) - a(0) * b(2), a(0) * b(1) - a(1) * b(0)}};
+    return Vec3(a(1) * b(2) - a(2) * b(1), a(2) * b(0) - a(0) * b(2), a(0) * b(1) - a(1) * b(0));
 }
 static Vec3 rotate(const Quat& q, const Vec3& p) {       // uv = qv x p; uv += uv; p + qw * uv + qv x uv
-    const Vec3 qv{{q.qx, q.qy, q.qz}};
+    const Vec3 qv(q.qx, q.qy, q.qz);
     Vec3 uv = cross(qv, p);
     for (float& c : uv.v) c = c + c;
     const Vec3 w = cross(qv, uv);
-    return Vec3{{(p(0) + q.qw * uv(0)) + w(0), (p(1) + q.qw * uv(1)) + w(1), (p(2) + q.qw * uv(2)) + w(2)}};
+    return Vec3((p(0) + q.qw * uv(0)) + w(0), (p(1) + q.qw * uv(1)) + w(1), (p(2) + q.qw * uv(2)) + w(2));
 }
 
-struct MiniSE3 {
+struct QuatSE3 {                        // quaternion-backed on purpose: the drop-in reads unit_quaternion() and inverse()
     Quat q; Vec3 t;
-    MiniSE3(const Rotation& R, const Vec3& tr) : q(R.q), t(tr) {}
+    QuatSE3(const Rotation& R, const Vec3& tr) : q(R.q), t(tr) {}
     Quat unit_quaternion() const { return q; }
     Vec3 translation() const { return t; }
-    MiniSE3 inverse() const {
+    QuatSE3 inverse() const {
         const Quat c{-q.qx, -q.qy, -q.qz, q.qw};
         const Vec3 r = rotate(c, t);
-        return MiniSE3(Rotation{c}, Vec3{{-r(0), -r(1), -r(2)}});
+        return QuatSE3(Rotation{c}, Vec3(-r(0), -r(1), -r(2)));
     }
 };
 struct MiniSim3 {
@@ -58,7 +52,7 @@ struct MiniSim3 {
 
 struct MockMapPoint {                   // members the Sim3 SearchByProjection overloads read (src/Matchers/SPmatcher.cc:1578-1633)
     bool bad = false;
-    Vec3 pos{{0, 0, 0}}, nrm{{0, 0, 0}};
+    Vec3 pos, nrm;
     float dmin = 0, dmax = 0, maxd = 0;
     cv::Mat desc;
     bool isBad() const { return bad; }
@@ -81,22 +75,19 @@ struct MockKeyFrame {
     cv::Mat mDescriptors;
 };
 
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[5]; float fl[18];
-    if (fread(hd, 4, 5, fi) != 5 || fread(fl, 4, 18, fi) != 18) return 2;
+    if (fread(hd, 4, 5, fi) != 5 || fread(fl, 4, 18, fi) != 18) return EXIT_BAD_CASE;
     const int Np = hd[0], Nf = hd[1], th = hd[3], nlevels = hd[4];
     std::vector<float> sf, pw, nr, dmin, dmax, maxd, qd, kp, fd; std::vector<uint8_t> bad; std::vector<int32_t> prior;
     if (!get(fi, sf, nlevels) || !get(fi, bad, Np) || !get(fi, prior, Nf) || !get(fi, pw, (size_t)Np * 3) || !get(fi, nr, (size_t)Np * 3) ||
         !get(fi, dmin, Np) || !get(fi, dmax, Np) || !get(fi, maxd, Np) || !get(fi, qd, (size_t)Np * 256) || !get(fi, kp, (size_t)Nf * 2) ||
-        !get(fi, fd, (size_t)Nf * 256)) { fprintf(stderr, "short case file\n"); return 2; }
+        !get(fi, fd, (size_t)Nf * 256)) return short_case();
     fclose(fi);
-    MiniSim3 Scw{Quat{fl[0], fl[1], fl[2], fl[3]}, Vec3{{fl[4], fl[5], fl[6]}}, fl[7]};
+    MiniSim3 Scw{Quat{fl[0], fl[1], fl[2], fl[3]}, Vec3(fl[4], fl[5], fl[6]), fl[7]};
     const float ratioHamming = fl[17];
     std::vector<MockMapPoint> mps((size_t)Np);
     MockMapPoint other;
@@ -118,25 +109,24 @@ int main(int argc, char** argv) {
     KF.mvKeysUn.resize((size_t)Nf);
     KF.mDescriptors = cv::Mat(Nf, 256, CV_32F, fd.data());
     for (int j = 0; j < Nf; ++j) KF.mvKeysUn[j].pt = cv::Point2f(kp[2 * j], kp[2 * j + 1]);
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     for (int overload = 0; overload < 2; ++overload) {
         std::vector<MockMapPoint*> vpMatched((size_t)Nf, nullptr);
         std::vector<MockKeyFrame*> vpMatchedKF((size_t)Nf, nullptr);
         for (int j = 0; j < Nf; ++j) vpMatched[j] = prior[j] == -1 ? nullptr : (prior[j] == -2 ? &other : &mps[prior[j]]);
         const int32_t ret = overload == 0
-            ? ORB_SLAM3::SearchByProjectionSim3_rfe<MiniSE3>(ctx, &KF, Scw, vp, vpKFs, vpMatched, vpMatchedKF, th, ratioHamming)
-            : ORB_SLAM3::SearchByProjectionSim3_rfe<MiniSE3>(ctx, &KF, Scw, vp, vpMatched, th, ratioHamming);
+            ? ORB_SLAM3::SearchByProjectionSim3_rfe<QuatSE3>(ctx, &KF, Scw, vp, vpKFs, vpMatched, vpMatchedKF, th, ratioHamming)
+            : ORB_SLAM3::SearchByProjectionSim3_rfe<QuatSE3>(ctx, &KF, Scw, vp, vpMatched, th, ratioHamming);
         std::vector<int32_t> who((size_t)Nf), kf((size_t)Nf);
         for (int j = 0; j < Nf; ++j) {
             who[j] = !vpMatched[j] ? -1 : (vpMatched[j] == &other ? -2 : (int32_t)(vpMatched[j] - mps.data()));
             kf[j] = vpMatchedKF[j] ? (int32_t)(vpMatchedKF[j] - kfs.data()) : -1;
         }
         fwrite(&ret, 4, 1, fo);
-        fwrite(who.data(), 4, who.size(), fo);
-        fwrite(kf.data(), 4, kf.size(), fo);
+        put(fo, who); put(fo, kf);
     }
     fclose(fo);
     rfe_destroy(ctx);

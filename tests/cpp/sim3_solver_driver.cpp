@@ -11,27 +11,11 @@
 // out.bin:  i32 status, bConverge, bNoMore, nInliers, calls of iterate, draws taken, mN1, correspondences, iterations, a draw was asked
 //               for with other bounds than (0, N - 1 - k) | i32 stats[8] | f32 the returned matrix [16], GetEstimatedTransformation [16],
 //               Rotation [9], Translation [3], Scale | mN1 x u8 vbInliers
-#include <cstdio>
-#include <cstdlib>
 #include <map>
 #include <tuple>
-#include <vector>
-#include "rfe/cv_compat.h"
+#include "driver_common.h"
 #include "rfe/sim3_solver.h"
 
-struct Vec3 {
-    float v[3];
-    Vec3() : v{0, 0, 0} {}
-    float operator()(int i) const { return v[i]; }
-};
-struct Mat3 {
-    float m[9];
-    float operator()(int r, int c) const { return m[3 * r + c]; }
-};
-struct MockCamera {
-    int type = 0;
-    int GetType() const { return type; }
-};
 struct MockKeyFrame;
 struct MockMapPoint {
     Vec3 pos; bool bad = false;
@@ -55,23 +39,20 @@ struct MockKeyFrame {
     Vec3 GetTranslation() const { return tcw; }
 };
 
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[10]; double prob; float pose[24], cam[8];
     if (fread(hd, 4, 10, fi) != 10 || fread(&prob, 8, 1, fi) != 1 || fread(pose, 4, 24, fi) != 24 || fread(cam, 4, 8, fi) != 8 || hd[0] < 0 ||
-        hd[1] < 1 || hd[2] < 1 || hd[8] < 0) return 2;
+        hd[1] < 1 || hd[2] < 1 || hd[8] < 0) return EXIT_BAD_CASE;
     const size_t M = (size_t)hd[0];
     MockKeyFrame K1, K2, K3;
     std::vector<int32_t> draws;
     struct Slot { int32_t kind, oct1, oct2, idx2; float x1[3], x2[3]; };
     std::vector<Slot> slots;
     if (!get(fi, K1.mvLevelSigma2, (size_t)hd[1]) || !get(fi, K2.mvLevelSigma2, (size_t)hd[2]) || !get(fi, slots, M) ||
-        !get(fi, draws, (size_t)hd[8])) { fprintf(stderr, "short case file\n"); return 2; }
+        !get(fi, draws, (size_t)hd[8])) return short_case();
     fclose(fi);
     for (int k = 0; k < 9; ++k) { K1.Rcw.m[k] = pose[k]; K2.Rcw.m[k] = pose[12 + k]; }
     for (int k = 0; k < 3; ++k) { K1.tcw.v[k] = pose[9 + k]; K2.tcw.v[k] = pose[21 + k]; }
@@ -83,7 +64,7 @@ int main(int argc, char** argv) {
     K1.mvKeysUn.resize(M); K2.mvKeysUn.resize(M); K1.points.assign(M, nullptr);
     for (size_t i = 0; i < M; ++i) {
         const Slot& s = slots[i];
-        if (s.idx2 < 0 || (size_t)s.idx2 >= M) return 2;
+        if (s.idx2 < 0 || (size_t)s.idx2 >= M) return EXIT_BAD_CASE;
         for (int k = 0; k < 3; ++k) { p1[i].pos.v[k] = s.x1[k]; p2[i].pos.v[k] = s.x2[k]; }
         K1.mvKeysUn[i].octave = s.oct1; K2.mvKeysUn[s.idx2].octave = s.oct2;
         if (s.kind != 5) p1[i].index[&K1] = (int)i;
@@ -92,8 +73,8 @@ int main(int argc, char** argv) {
         K1.points[i] = s.kind == 2 ? nullptr : &p1[i];
         matched[i] = s.kind == 1 ? nullptr : &p2[i];
     }
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     size_t taken = 0; int bad_bounds = 0, expect_hi = -1, k3 = 0;
     auto random_int = [&](int lo, int hi) {
         if (k3 == 0) expect_hi = hi;                                     // the first draw of an iteration tells N - 1
@@ -123,12 +104,12 @@ int main(int argc, char** argv) {
                               solver.iterations(), bad_bounds};
     rfe_destroy(ctx);
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     fwrite(head, 4, 10, fo); fwrite(stats, 4, 8, fo);
     fwrite(T.data(), 4, 16, fo); fwrite(Tb.data(), 4, 16, fo); fwrite(Rb.data(), 4, 9, fo); fwrite(tb.data(), 4, 3, fo); fwrite(&sb, 4, 1, fo);
     std::vector<uint8_t> o(vbInliers.size());
     for (size_t i = 0; i < o.size(); ++i) o[i] = vbInliers[i] ? 1 : 0;
-    if (!o.empty()) fwrite(o.data(), 1, o.size(), fo);
+    put(fo, o);
     fclose(fo);
     return 0;
 }

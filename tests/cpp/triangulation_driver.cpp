@@ -12,28 +12,9 @@
 //           which the first n2 -- the i32 in front -- are features)
 // out.bin:  i32 return value, Nn, Kmax, points | f32 matchsum | i32 matches[Nn] | i32 stats[8] | points x (i32 neighbour, idx1, idx2, stereo) |
 //           points x 3 f32 | i32 S[Nn], pairs[Nn,Kmax,2] (with weights only)
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "driver_common.h"
 #include "rfe/triangulation.h"
 
-struct Vec3 {
-    float v[3];
-    float operator()(int i) const { return v[i]; }
-};
-struct Mat3 {
-    float m[9];
-    float operator()(int r, int c) const { return m[3 * r + c]; }
-};
-struct MiniSE3 {
-    Mat3 R; Vec3 t;
-    Mat3 rotationMatrix() const { return R; }
-    Vec3 translation() const { return t; }
-};
-struct MockCamera {
-    unsigned int type = 0;
-    unsigned int GetType() { return type; }
-};
 struct MockMapPoint {};
 
 struct MockKeyFrame {                   // members LocalMapping::CreateNewMapPoints and SearchForTriangulation read
@@ -53,11 +34,6 @@ struct MockKeyFrame {                   // members LocalMapping::CreateNewMapPoi
     MockMapPoint* GetMapPoint(size_t i) { return has_mp[i] ? &some : nullptr; }
     float ComputeSceneMedianDepth(int) const { return median; }
 };
-
-template <class T>
-static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T>
-static void put(FILE* f, const std::vector<T>& v) { if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f); }
 
 static bool read_keyframe(FILE* f, MockKeyFrame& kf, int rows, const std::vector<float>& sf, const std::vector<float>& sg, float scale) {
     float fl[24]; int32_t n;
@@ -80,24 +56,24 @@ static bool read_keyframe(FILE* f, MockKeyFrame& kf, int rows, const std::vector
 
 int main(int argc, char** argv) {
     if (argc < 3) return 0;
-    FILE* fi = fopen(argv[1], "rb");
-    if (!fi) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    FILE* fi = open_case(argv[1]);
+    if (!fi) return EXIT_BAD_CASE;
     int32_t hd[10]; float fl[2];
-    if (fread(hd, 4, 10, fi) != 10 || fread(fl, 4, 2, fi) != 2) return 2;
+    if (fread(hd, 4, 10, fi) != 10 || fread(fl, 4, 2, fi) != 2) return EXIT_BAD_CASE;
     const int Nn = hd[0], N1 = hd[1], N2max = hd[2], Kmax = hd[3], nlevels = hd[4];
     std::vector<float> sf, sg;
-    if (!get(fi, sf, nlevels) || !get(fi, sg, nlevels)) return 2;
+    if (!get(fi, sf, nlevels) || !get(fi, sg, nlevels)) return EXIT_BAD_CASE;
     MockKeyFrame cur;
     std::vector<MockKeyFrame> neigh((size_t)Nn);
-    if (!read_keyframe(fi, cur, N1, sf, sg, fl[1])) { fprintf(stderr, "short case file\n"); return 2; }
-    for (MockKeyFrame& kf : neigh) if (!read_keyframe(fi, kf, N2max, sf, sg, fl[1])) { fprintf(stderr, "short case file\n"); return 2; }
+    if (!read_keyframe(fi, cur, N1, sf, sg, fl[1])) return short_case();
+    for (MockKeyFrame& kf : neigh) if (!read_keyframe(fi, kf, N2max, sf, sg, fl[1])) return short_case();
     std::vector<int32_t> S, pairs;
-    if (!get(fi, S, Nn) || !get(fi, pairs, (size_t)Nn * Kmax * 2)) { fprintf(stderr, "short case file\n"); return 2; }
+    if (!get(fi, S, Nn) || !get(fi, pairs, (size_t)Nn * Kmax * 2)) return short_case();
     if (hd[9]) {
-        if (!get(fi, cur.desc, (size_t)N1 * 256)) return 2;
+        if (!get(fi, cur.desc, (size_t)N1 * 256)) return EXIT_BAD_CASE;
         cur.mDescriptors = cv::Mat(N1, 256, CV_32F, cur.desc.data());
         for (MockKeyFrame& kf : neigh) {
-            if (!get(fi, kf.desc, (size_t)N2max * 256)) return 2;
+            if (!get(fi, kf.desc, (size_t)N2max * 256)) return EXIT_BAD_CASE;
             kf.mDescriptors = cv::Mat(N2max, 256, CV_32F, kf.desc.data());
         }
     }
@@ -108,31 +84,31 @@ int main(int argc, char** argv) {
     cur.mpCamera = &cur.cam;
     ORB_SLAM3::CreateNewMapPointsParams_rfe prm;
     prm.bMonocular = hd[5] != 0; prm.bInertial = hd[6] != 0; prm.bFarPoints = hd[7] != 0; prm.thFarPoints = fl[0];
-    rfe_ctx* ctx = nullptr;
-    if (rfe_init(0, &ctx) != RFE_OK) { fprintf(stderr, "rfe_init: %s\n", rfe_last_error(nullptr)); return 3; }
+    rfe_ctx* ctx = make_context();
+    if (!ctx) return EXIT_LIBRARY;
     ORB_SLAM3::CreateNewMapPointsOut_rfe out;
     int32_t ret;
     if (argc > 3) {
         FILE* fw = fopen(argv[3], "rb");
         std::vector<float> blob;
         const int64_t count = rfe_weight_count(RFE_KIND_LIGHTGLUE);
-        if (!fw || !get(fw, blob, (size_t)count)) { fprintf(stderr, "cannot read %s\n", argv[3]); return 2; }
+        if (!fw || !get(fw, blob, (size_t)count)) { fprintf(stderr, "cannot read %s\n", argv[3]); return EXIT_BAD_CASE; }
         fclose(fw);
-        if (rfe_set_weights(ctx, RFE_KIND_LIGHTGLUE, blob.data(), count) != RFE_OK) { fprintf(stderr, "weights: %s\n", rfe_last_error(ctx)); return 3; }
+        if (rfe_set_weights(ctx, RFE_KIND_LIGHTGLUE, blob.data(), count) != RFE_OK) { fprintf(stderr, "weights: %s\n", rfe_last_error(ctx)); return EXIT_LIBRARY; }
         prm.keep_matches = true;
         ret = ORB_SLAM3::CreateNewMapPoints_rfe(ctx, &cur, vp, prm, out);
     } else {
         int32_t *dS = nullptr, *dp = nullptr;
-        if (rfe_malloc(ctx, S.size() * 4 + 4, (void**)&dS) || rfe_malloc(ctx, pairs.size() * 4 + 4, (void**)&dp)) return 3;
+        if (rfe_malloc(ctx, S.size() * 4 + 4, (void**)&dS) || rfe_malloc(ctx, pairs.size() * 4 + 4, (void**)&dp)) return EXIT_LIBRARY;
         if ((!S.empty() && rfe_memcpy_h2d(ctx, dS, S.data(), S.size() * 4)) || (!pairs.empty() && rfe_memcpy_h2d(ctx, dp, pairs.data(), pairs.size() * 4)))
-            return 3;
+            return EXIT_LIBRARY;
         ret = ORB_SLAM3::TriangulateMatches_rfe(ctx, &cur, vp, prm, dS, dp, Kmax, out);
         rfe_free(ctx, dS); rfe_free(ctx, dp);
     }
     if (ret < -1) fprintf(stderr, "drop-in: %d %s\n", ret, rfe_last_error(ctx));
     rfe_destroy(ctx);
     FILE* fo = fopen(argv[2], "wb");
-    if (!fo) return 5;
+    if (!fo) return EXIT_OUTPUT;
     const int32_t head[4] = {ret, Nn, out.Kmax, (int32_t)out.points.size()};
     fwrite(head, 4, 4, fo);
     fwrite(&out.matchsum, 4, 1, fo);

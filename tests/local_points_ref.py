@@ -3,15 +3,10 @@ Frame::isInFrustum (src/Frame.cc:711-794, one pinhole camera) and the head of SP
 1178-1206) for every local map point as single np.float32 operations in the order the contract writes them, then GetFeaturesInArea, the scan
 and the loop's sequential assignment from projection_search_ref (6d).  Shared by test_local_points_ref.py (CPU) and
 test_gpu_local_points.py; holds the case generators."""
-import os
-import subprocess
-
 import numpy as np
 
 import projection_search_ref as PS
 import sim3_search_ref as S3
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 F32 = np.float32
 TH_HIGH = PS.TH_HIGH
@@ -339,14 +334,3 @@ def read_driver_out(path, Np, Nf):
         got[k] = raw[o:o + 4 * Np].view(dt); o += 4 * Np
     assert o == len(raw)
     return int(hd[0]), int(hd[1]), who, got
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "local_points_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "local_points_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe

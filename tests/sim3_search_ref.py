@@ -3,14 +3,9 @@
 radius) as single np.float32 operations in the order the reference writes them, then KeyFrame::GetFeaturesInArea, the scan and the loop's
 sequential assignment from projection_search_ref (6d) with every map point observed.  Shared by test_sim3_search_ref.py (CPU) and
 test_gpu_sim3_search.py."""
-import os
-import subprocess
-
 import numpy as np
 
 import projection_search_ref as PS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 F32 = np.float32
 TH_LOW = F32(1.2)                      # SPmatcher::TH_LOW
@@ -313,14 +308,3 @@ def write_driver_case(path, P, c, nleft=-1):
         for k in ("pw", "normal", "min_dist", "max_dist", "scale_dist", "q", "kpts", "desc"):
             c[k].astype(np.float32).tofile(f)
     return Pd, prior
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "sim3_search_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "sim3_search_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe

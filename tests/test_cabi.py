@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import dropin_driver as DD
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -62,14 +64,27 @@ def test_weight_container_roundtrip(tmp_path):
 def test_shim_headers_compile_and_link(tmp_path):
     """include/Extractors/SPextractor.h, include/Matchers/SPmatcher.h, include/SuperPoint.h and
     include/super_glue.h build without OpenCV / onnxruntime and link against librover_fe.so."""
-    exe = str(tmp_path / "shim_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),   # the reference builds -std=c++14 (CMakeLists.txt:12)
-           os.path.join(ROOT, "tests", "cpp", "shim_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert os.path.exists(exe)
+    assert os.path.exists(DD.build(tmp_path, "shim_driver"))
+
+
+# the drivers of tests/cpp that document NO_DEVICE, with the macros each is built with
+NO_DEVICE = "without arguments: compile / link check only"
+NO_DEVICE_DRIVERS = [("projection_search_driver", ()), ("sim3_search_driver", ()), ("local_points_driver", ()),
+                     ("local_points_driver", ("RFE_SP_PYRAMID=1",)), ("triangulation_driver", ()), ("pose_opt_driver", ()),
+                     ("sim3_solver_driver", ()), ("bow_driver", ())]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+@pytest.mark.parametrize("name,macros", NO_DEVICE_DRIVERS, ids=["-".join((n,) + m) for n, m in NO_DEVICE_DRIVERS])
+def test_drop_in_driver_compiles_links_and_runs_without_arguments(tmp_path, name, macros):
+    """every drop-in header of include/rfe with its driver, -std=c++14 -Wall -Werror; the run without arguments touches no device"""
+    DD.run(DD.build(tmp_path, name, macros))
+
+
+def test_every_driver_with_a_no_device_run_is_listed():
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    documented = {f[:-4] for f in os.listdir(cpp) if f.endswith(".cpp") and NO_DEVICE in open(os.path.join(cpp, f)).read()}
+    assert documented == {name for name, _ in NO_DEVICE_DRIVERS}
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
@@ -95,9 +110,12 @@ def test_spmatcher_in_tree_mode_cxx14(tmp_path):
                         "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    # the stand-alone header in a second translation unit next to the first: no duplicate definitions in C++14 either
+    # the stand-alone header, and the rfe drop-ins with rfe/dropin_detail.h, in a second translation unit next to the first: no duplicate
+    # definitions in C++14 either
     for i in (1, 2):
-        (tmp_path / f"tu{i}.cc").write_text('#include "Matchers/SPmatcher.h"\nfloat tu%d() { return ORB_SLAM3::SPmatcher::TH_HIGH; }\n' % i)
+        (tmp_path / f"tu{i}.cc").write_text('#include "Matchers/SPmatcher.h"\n#include "rfe/projection_search.h"\n#include "rfe/local_points_search.h"\n#include "rfe/sim3_search.h"\n'
+                                            '#include "rfe/triangulation.h"\n#include "rfe/pose_optimization.h"\n#include "rfe/sim3_solver.h"\n'
+                                            'float tu%d() { return ORB_SLAM3::SPmatcher::TH_HIGH; }\n' % i)
     (tmp_path / "tumain.cc").write_text("float tu1(); float tu2(); int main() { return tu1() == tu2() ? 0 : 1; }\n")
     r = subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(tmp_path / "tu1.cc"), str(tmp_path / "tu2.cc"),
                         str(tmp_path / "tumain.cc"), "-o", str(tmp_path / "tu"), "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe",

@@ -1,28 +1,15 @@
 """GPU: the drop-ins of include/rfe/bow.h (ComputeBoW3_rfe, AddKeyFrame_rfe, ScoreKeyFrames_rfe) over mock DBoW3 classes and plain std::map
 (tests/cpp/bow_driver.cpp, -std=c++14 -Wall -Werror) against the restatement tests/bow_ref.py: the two maps bit for bit, and the
 (entry, (float)score) list of the two Detect... functions."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import bow_ref as B
+import dropin_driver as DD
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "bow_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "bow_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def write_case(path, v, frames, levelsup, exclude):
@@ -65,9 +52,7 @@ def read_out(path):
 
 def run_and_compare(exe, tmp_path, v, frames, levelsup, exclude, stream=None):
     write_case(str(tmp_path / "case.bin"), v, frames, levelsup, exclude)
-    cmd = [exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")] + ([stream] if stream else [])
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"), *([stream] if stream else []))
     got = read_out(str(tmp_path / "out.bin"))
     u8 = [B.binarize(d) if d.dtype == np.float32 else d for d in frames]
     ref = B.transform(v, u8[0], levelsup)
@@ -88,7 +73,7 @@ def run_and_compare(exe, tmp_path, v, frames, levelsup, exclude, stream=None):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in_bow_and_scores(tmp_path):
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "bow_driver")
     rng = np.random.default_rng(3)
     # SuperPoint-like float descriptors, D = 256, the vocabulary handed over as arrays
     v = B.make_vocab(6, 3, 256, seed=4, stop_every=11)

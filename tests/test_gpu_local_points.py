@@ -3,13 +3,13 @@ contract of DESIGN.md 6f restated in tests/local_points_ref.py.  Every compariso
 and device form."""
 import ctypes
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import local_points_ref as LP
-from local_points_ref import LEVEL_PREDICTED, LEVEL_ZERO, build_driver, read_driver_out, solved, to_capi, write_driver_case
+from local_points_ref import LEVEL_PREDICTED, LEVEL_ZERO, read_driver_out, solved, to_capi, write_driver_case
 
 pytestmark = pytest.mark.gpu
 OUT = {"assign": np.int32, "best_idx": np.int32, "best_dist": np.float32, "second_dist": np.float32, "proj": np.float32, "proj_xr": np.float32,
@@ -290,13 +290,12 @@ def test_profile_names_every_kernel(ctx, oracle):
 # ---------------------------------------------------------------- 5. the drop-in helper
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in_helper(tmp_path, oracle):
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "local_points_driver")
     for name, th in (("main", 6), ("planted", 1)):
         P, c, ref = solved(oracle, name, th, True, LEVEL_ZERO)
         Np, Nf = len(c["pw"]), len(c["kpts"])
         before, prior = write_driver_case(str(tmp_path / "case.bin"), P, c)
-        r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
         ret, n_to_match, who, got = read_driver_out(str(tmp_path / "out.bin"), Np, Nf)
         assert ret == ref["nmatches"] > 0 and n_to_match == ref["in_frustum"]
         assert np.array_equal(who, np.where(ref["assign"] >= 0, ref["assign"], prior))        # what was there before stays
@@ -306,8 +305,7 @@ def test_drop_in_helper(tmp_path, oracle):
         assert (want["proj_x"] == -1).sum() > 2 and (want["in_view"] != before["in_view"]).any()
         # a two-camera frame is refused, nothing is touched
         write_driver_case(str(tmp_path / "rig.bin"), P, c, nleft=500)
-        r = subprocess.run([exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        DD.run(exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin"))
         ret, n_to_match, who, got = read_driver_out(str(tmp_path / "rig_out.bin"), Np, Nf)
         assert ret == -1 and n_to_match == 0 and np.array_equal(who, prior)
         for k in LP.FIELDS:

@@ -1,29 +1,16 @@
 """GPU: the drop-in of include/rfe/pose_optimization.h (PoseOptimization_rfe) over a mock Frame (tests/cpp/pose_opt_driver.cpp) against the
 restatement tests/pose_opt_ref.py: the return value, mvbOutlier and the pose handed to SetPose."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import pose_opt_ref as R
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 SENTINEL_OUTLIER = 1                      # mvbOutlier before the call: true everywhere, so a feature the call leaves alone shows
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "pose_opt_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "pose_opt_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def write_case(path, c, camera2=False):
@@ -47,14 +34,13 @@ def read_out(path):
 
 def run(exe, tmp_path, c, **kw):
     write_case(str(tmp_path / "case.bin"), c, **kw)
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
     return read_out(str(tmp_path / "out.bin"))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in(tmp_path):
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "pose_opt_driver")
     for kind in ("mono", "stereo", "mixed"):
         c = R.scene(90, 500, kind)
         ref = R.solve(c, outlier=np.full(500, SENTINEL_OUTLIER, np.uint8))

@@ -1,13 +1,13 @@
 """GPU: SearchByProjection1 on the device (rfe_search_by_projection / _dev, SearchByProjection1_rfe) against the contract of DESIGN.md 6d
 restated in tests/projection_search_ref.py.  Every comparison is exact (np.array_equal on every output)."""
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import projection_search_ref as PS
-from test_projection_search_ref import build_driver, chain_case, solved, solved_big, solved_levels, write_driver_case
+from test_projection_search_ref import chain_case, solved, solved_big, solved_levels, write_driver_case
 from rover_slam_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -240,10 +240,9 @@ def test_profile_names_every_kernel(ctx, oracle):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in_helper(tmp_path, oracle):
     c, lists, seq, _, _ = solved(oracle, 0)
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "projection_search_driver")
     sel, prior = write_driver_case(str(tmp_path / "case.bin"), c)
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
     out = np.fromfile(str(tmp_path / "out.bin"), np.int32)
     assert out[0] == seq["nmatches"] and len(out) == 1 + len(c["kxy"])
     want = np.where(seq["assign"] >= 0, sel[np.maximum(seq["assign"], 0)], np.where(prior >= 0, -2, -1))
@@ -252,8 +251,7 @@ def test_drop_in_helper(tmp_path, oracle):
     assert ((out[1:] >= 0) & (prior == 0)).any()             # one without observations is overwritten
     # a two-camera rig is refused, nothing is touched
     write_driver_case(str(tmp_path / "rig.bin"), c, nleft=150)
-    r = subprocess.run([exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin"))
     out = np.fromfile(str(tmp_path / "rig_out.bin"), np.int32)
     assert out[0] == -1 and np.array_equal(out[1:], np.where(prior >= 0, -2, -1))
 
@@ -353,10 +351,9 @@ def test_big_unobserved_map_points_equal_search_candidates(ctx, oracle):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_big_drop_in_helper(tmp_path, oracle):
     c, lists, seq, _, _ = solved_big(oracle, "B")
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "projection_search_driver")
     sel, prior = write_driver_case(str(tmp_path / "case.bin"), c)
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
     out = np.fromfile(str(tmp_path / "out.bin"), np.int32)
     assert out[0] == seq["nmatches"] and len(out) == 1 + len(c["kpts"])
     want = np.where(seq["assign"] >= 0, sel[np.maximum(seq["assign"], 0)], np.where(prior >= 0, -2, -1))

@@ -4,17 +4,16 @@ GPU-vs-GPU agreement with rfe_extract_u8 per level, the refusals, and the drop-i
 import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import pyramid_ref as P
 from tolerances import LG_SCORE_TOL
 from rover_slam_amd import capi, weights as Wt, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FPL_1000 = [217, 181, 151, 126, 105, 87, 73, 60]
 
 
@@ -254,15 +253,6 @@ def test_refusals(ctx):
 
 
 # ---------------------------------------------------------------- 8. the drop-in class
-def build_driver(tmp_path, macro):
-    exe = str(tmp_path / ("pyramid_driver" + ("_on" if macro else "_off")))
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + (["-DRFE_SP_PYRAMID=1"] if macro else [])
-    subprocess.check_call(cmd + [os.path.join(ROOT, "tests", "cpp", "pyramid_driver.cpp"), "-o", exe,
-                                 "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                                 "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def read_driver(path):
     buf = open(path, "rb").read()
     off = 0
@@ -293,10 +283,9 @@ def test_spextractor_pyramid_opt_in(tmp_path, ctx, wsp, oracle):
     assert_same(api, ref, 1, 8)
     results = {}
     for macro in (True, False):
-        exe = build_driver(tmp_path, macro)
+        exe = DD.build(tmp_path, "pyramid_driver", ("RFE_SP_PYRAMID=1",) if macro else ())
         out = str(tmp_path / ("out_on.bin" if macro else "out_off.bin"))
-        r = subprocess.run([exe, str(tmp_path / "frame.u8"), str(H), str(W), out], env=env, capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        DD.run(exe, str(tmp_path / "frame.u8"), H, W, out, env=env)
         results[macro] = read_driver(out)
     n, kp, octave, desc, levels, st, unset = results[True]
     N = int(api["n"][0])

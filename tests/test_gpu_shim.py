@@ -9,20 +9,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 from rover_slam_amd import weights as Wt, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 @pytest.mark.parametrize("H,W", [(120, 160), (480, 752)])   # small case, and the EuRoC stereo size of BASELINE config 5
 def test_cpp_shims_match_oracle(tmp_path, oracle, H, W):
-    exe = str(tmp_path / "shim_driver")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),   # the reference builds -std=c++14 (CMakeLists.txt:12)
-                           os.path.join(ROOT, "tests", "cpp", "shim_driver.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = DD.build(tmp_path, "shim_driver")
     wsp, wlg = Wt.make_superpoint(seed=7), Wt.make_lightglue(seed=11)
     # the keypoint budget reaches the shims the way it reaches the reference: as a constant of the model file (RFEW v2 header), not as
     # configuration (the reference reads K off the output tensor's shape, src/Extractors/superpoint_onnx.cc:169-181)
@@ -31,9 +27,7 @@ def test_cpp_shims_match_oracle(tmp_path, oracle, H, W):
     frames, _ = synth.make_frames(2, H, W, seed=42)
     frames.tofile(str(tmp_path / "frames.u8"))
     env = dict(os.environ, RFE_SP_WEIGHTS=str(tmp_path / "sp.rfew"), RFE_LG_WEIGHTS=str(tmp_path / "lg.rfew"))
-    r = subprocess.run([exe, str(tmp_path / "frames.u8"), str(H), str(W), str(tmp_path / "out.bin")], env=env,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "frames.u8"), H, W, str(tmp_path / "out.bin"), env=env)
     buf = open(str(tmp_path / "out.bin"), "rb").read()
     off = 0
     ext = []
@@ -77,11 +71,7 @@ def test_cpp_shims_take_the_references_onnx_paths_unedited(tmp_path, oracle):
     torch = pytest.importorskip("torch")  # noqa: F841
     import onnx_export as X
     H, W = 120, 160
-    exe = str(tmp_path / "shim_driver")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "shim_driver.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = DD.build(tmp_path, "shim_driver")
     (tmp_path / "onnxmodel").mkdir()
     try:
         _, wsp = X.export_sp(str(tmp_path / "onnxmodel"), X.SETTINGS[1], seed=7, desc_center="auto")
@@ -91,9 +81,7 @@ def test_cpp_shims_take_the_references_onnx_paths_unedited(tmp_path, oracle):
     frames, _ = synth.make_frames(2, H, W, seed=20240314, max_shift=16, shift_step=8)
     frames.tofile(str(tmp_path / "frames.u8"))
     env = {k: v for k, v in os.environ.items() if k not in ("RFE_SP_WEIGHTS", "RFE_LG_WEIGHTS")}
-    r = subprocess.run([exe, str(tmp_path / "frames.u8"), str(H), str(W), str(tmp_path / "out.bin")], env=env, cwd=str(tmp_path),
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "frames.u8"), H, W, str(tmp_path / "out.bin"), env=env, cwd=str(tmp_path))
     buf = open(str(tmp_path / "out.bin"), "rb").read()
     off, ext = 0, []
     for i in range(2):

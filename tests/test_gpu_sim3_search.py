@@ -2,13 +2,13 @@
 SearchByProjectionSim3_rfe) against the contract of DESIGN.md 6e restated in tests/sim3_search_ref.py.  Every comparison is exact
 (np.array_equal on every output), in host and device form."""
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import sim3_search_ref as S3
-from sim3_search_ref import MODES, RATIO_HAMMING, build_driver, solved, to_capi, write_driver_case
+from sim3_search_ref import MODES, RATIO_HAMMING, solved, to_capi, write_driver_case
 from rover_slam_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -264,10 +264,9 @@ def test_profile_names_every_kernel(ctx, oracle):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in_helpers(tmp_path, oracle):
     P, c, _ = solved(oracle, "main")
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "sim3_search_driver")
     Pd, prior = write_driver_case(str(tmp_path / "case.bin"), P, c)
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
     Nf = len(c["kpts"])
     out = np.fromfile(str(tmp_path / "out.bin"), np.int32).reshape(2, 1 + 2 * Nf)
     for k, (proj_mode, dist_mode, th_accept) in enumerate(((S3.PROJ_INVZ, S3.DIST_FLOAT, S3.TH_LOW),
@@ -281,8 +280,7 @@ def test_drop_in_helpers(tmp_path, oracle):
     assert not np.array_equal(out[0, 1:1 + Nf], out[1, 1:1 + Nf])
     # a two-camera keyframe is refused, nothing is touched
     write_driver_case(str(tmp_path / "rig.bin"), P, c, nleft=500)
-    r = subprocess.run([exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin"))
     out = np.fromfile(str(tmp_path / "rig_out.bin"), np.int32).reshape(2, 1 + 2 * Nf)
     for k in range(2):
         assert out[k, 0] == -1 and np.array_equal(out[k, 1:1 + Nf], prior) and (out[k, 1 + Nf:] == -1).all()

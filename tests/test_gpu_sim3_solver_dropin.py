@@ -1,31 +1,18 @@
 """GPU: the drop-in of include/rfe/sim3_solver.h (Sim3Solver_rfe) over mock KeyFrame / MapPoint types (tests/cpp/sim3_solver_driver.cpp)
 against the restatement tests/sim3_solver_ref.py: the constructor's five skip conditions and the scattering through mvnIndices1, the loop
 while(!bConverge && !bNoMore) iterate(20, ..), and find()."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import sim3_solver_ref as R
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 SIGMA2 = (1.0, 1.44, 2.0736)
 SKIPS = (1, 2, 3, 4, 5, 6)      # vpMatched12 NULL; no pMP1; pMP1 bad; pMP2 bad; pMP1 not in pKF1; pMP2 not in pKF2
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "sim3_solver_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "sim3_solver_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def slots_of(c, seed):
@@ -70,8 +57,7 @@ def read_out(path):
 def run(exe, tmp_path, c, probability=0.99, max_its=300, seed=0, **kw):
     kind, where = slots_of(c, seed)
     write_case(str(tmp_path / "case.bin"), c, kind, where, probability, max_its, seed=seed, **kw)
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
     return read_out(str(tmp_path / "out.bin")), where
 
 
@@ -83,7 +69,7 @@ def expected(c, probability, max_its):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in(tmp_path):
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "sim3_solver_driver")
     # 1. the loop converges: planted scene, 40 % outliers
     c0 = R.scene(5, 150, outliers=0.4, H=300)
     c, ref = expected(c0, 0.99, 300)

@@ -3,11 +3,11 @@ against the contract of DESIGN.md 6c restated in tests/stereo_pyramid_ref.py.  C
 import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import pyramid_ref as PR
 import stereo_pyramid_ref as SR
 from test_stereo_pyramid_ref import MB, MBF, check_constructed, constructed_case, shifted_pair
@@ -15,7 +15,6 @@ from tolerances import LG_SCORE_TOL
 from rover_slam_amd import capi, weights as Wt, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FPL_1000 = [217, 181, 151, 126, 105, 87, 73, 60]
 
 
@@ -347,16 +346,10 @@ def test_drop_in_helper(tmp_path, ctx, wsp):
     left, right = shifted_pair(H, W, disp, seed=disp)
     left.tofile(str(tmp_path / "left.u8")); right.tofile(str(tmp_path / "right.u8"))
     env = dict(os.environ, RFE_SP_WEIGHTS=str(tmp_path / "sp.rfew"))
-    exe = str(tmp_path / "stereo_pyramid_driver")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-DRFE_SP_PYRAMID=1", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "stereo_pyramid_driver.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    exe = DD.build(tmp_path, "stereo_pyramid_driver", ("RFE_SP_PYRAMID=1",))
     for L in (8, 1):
         out = str(tmp_path / f"out{L}.bin")
-        r = subprocess.run([exe, str(tmp_path / "left.u8"), str(tmp_path / "right.u8"), str(H), str(W), str(L), out], env=env,
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        DD.run(exe, str(tmp_path / "left.u8"), str(tmp_path / "right.u8"), H, W, L, out, env=env)
         Ld, (vl, vr), res = read_driver(out)
         assert Ld == L and len(vl[0]) > 100 and len(vr[0]) > 100
         assert np.array_equal(vl[3][0], left) and np.array_equal(vr[3][0], right)

@@ -1,28 +1,15 @@
 """GPU: the drop-ins of include/rfe/triangulation.h (TriangulateMatches_rfe, CreateNewMapPoints_rfe) over mock keyframe classes
 (tests/cpp/triangulation_driver.cpp) against the restatement tests/triangulation_ref.py: the returned list, matchsum and the statistics."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import triangulation_ref as T
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
-
-
-def build_driver(tmp_path):
-    exe = str(tmp_path / "triangulation_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "triangulation_driver.cpp"), "-o", exe,
-           "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 def write_case(path, P, c, nleft=-1, desc=None):
@@ -81,19 +68,17 @@ def same(got, ref):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_drop_in_on_resident_matches(tmp_path):
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "triangulation_driver")
     for name, far, inertial in (("main", True, False), ("planted", True, True), ("posed", False, False)):
         P, c, ref = T.solved(name, far, inertial)
         write_case(str(tmp_path / "case.bin"), P, c)
-        r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"))
         got = read_out(str(tmp_path / "out.bin"))
         assert ref["created"] > 5
         same(got, ref)
     # a two-camera neighbour is refused, nothing is computed
     write_case(str(tmp_path / "rig.bin"), P, c, nleft=200)
-    r = subprocess.run([exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "rig.bin"), str(tmp_path / "rig_out.bin"))
     got = read_out(str(tmp_path / "rig_out.bin"))
     assert got["ret"] == -1 and len(got["out_n"]) == 0 and (got["stats"] == 0).all()
 
@@ -103,7 +88,7 @@ def test_drop_in_with_lightglue_in_front(tmp_path):
     """CreateNewMapPoints_rfe: LightGlue (synthetic weights) matches all neighbours in one call; whatever it matched, the list is the
     restatement's on those matches"""
     from rover_slam_amd import weights as Wt
-    exe = build_driver(tmp_path)
+    exe = DD.build(tmp_path, "triangulation_driver")
     P, c, _ = T.solved("posed", True, False)
     rng = np.random.default_rng(11)
     N1, Nn, N2max = len(c["kpts1"]), len(c["views2"]), c["kpts2"].shape[1]
@@ -116,8 +101,7 @@ def test_drop_in_with_lightglue_in_front(tmp_path):
         d2[n, j] = unit(d1[i] + 0.02 * rng.standard_normal((len(i), 256)))
     Wt.make_lightglue(seed=11).astype(F32).tofile(str(tmp_path / "lg.bin"))
     write_case(str(tmp_path / "case.bin"), P, c, desc=[d1] + list(d2))
-    r = subprocess.run([exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"), str(tmp_path / "lg.bin")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    DD.run(exe, str(tmp_path / "case.bin"), str(tmp_path / "out.bin"), str(tmp_path / "lg.bin"))
     got = read_out(str(tmp_path / "out.bin"), with_matches=True)
     assert got["Kmax"] == min(N1, N2max) and got["S"].shape == (Nn,) and (got["S"] >= 0).all() and (got["S"] <= got["Kmax"]).all()
     print("LightGlue matches per neighbour:", got["S"].tolist(), "points:", got["ret"])

@@ -1,11 +1,8 @@
 """CPU: the restatement of Tracking::SearchLocalPoints' steps 2 and 3 that the GPU tests compare against (tests/local_points_ref.py,
 DESIGN.md 6f) is held to a scalar, per-point transcription of the reference text (src/Frame.cc:711-794, src/Matchers/SPmatcher.cc:1178-1283)
 on np.float32 scalars and to a float64 evaluation of the projection; the generated cases meet the conditions that make them worth running;
-the planted points land on the gates' edges; the binding refuses what it can refuse without a device; the drop-in header compiles and
-links."""
+the planted points land on the gates' edges; the binding refuses what it can refuse without a device."""
 import ctypes
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +10,7 @@ import pytest
 import local_points_ref as LP
 import projection_search_ref as PS
 import sim3_search_ref as S3
-from local_points_ref import LEVEL_PREDICTED, LEVEL_ZERO, build_driver, case_of, solved, to_capi
+from local_points_ref import LEVEL_PREDICTED, LEVEL_ZERO, case_of, solved, to_capi
 
 F32 = np.float32
 CONFIGS = [("main", 1, True, LEVEL_ZERO), ("main", 6, False, LEVEL_ZERO), ("main", 6, True, LEVEL_PREDICTED), ("main8", 1, True, LEVEL_PREDICTED),
@@ -280,13 +277,7 @@ def test_capi_binding_without_a_device():
                                            *([None] * 9), z) == -1
 
 
-# ---------------------------------------------------------------- the drop-in header
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_drop_in_header_compiles_and_links(tmp_path):
-    exe = build_driver(tmp_path)
-    assert subprocess.run([exe]).returncode == 0             # no arguments: nothing touches a device
-
-
+# ---------------------------------------------------------------- the drop-in driver's case
 def test_driver_case_round_trip(tmp_path, oracle):
     """the file the C++ driver reads keeps the problem: validity survives the translation into isBad() / mnLastFrameSeen, skip into the map
     point a feature holds"""

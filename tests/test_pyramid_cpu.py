@@ -2,14 +2,12 @@
 rfe_pyramid_geometry against it (a pure function: no device needed), its refusals, and the drop-in headers with the RFE_SP_PYRAMID opt-in."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import pyramid_ref as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_constant_image_stays_constant():
@@ -65,11 +63,4 @@ def test_library_geometry_refusals():
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 @pytest.mark.parametrize("macro", [None, "1"])
 def test_shim_headers_build_with_pyramid_opt_in(tmp_path, macro):
-    exe = str(tmp_path / "pyramid_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")]
-    if macro:
-        cmd.append("-DRFE_SP_PYRAMID=" + macro)
-    subprocess.check_call(cmd + [os.path.join(ROOT, "tests", "cpp", "pyramid_driver.cpp"), "-o", exe,
-                                 "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                                 "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    assert os.path.exists(exe)
+    assert os.path.exists(DD.build(tmp_path, "pyramid_driver", ("RFE_SP_PYRAMID=" + macro,) if macro else ()))

@@ -1,18 +1,16 @@
 """CPU: the restatement of the two Sim3 SearchByProjection overloads that the GPU tests compare against (tests/sim3_search_ref.py,
 DESIGN.md 6e) holds its own definitions -- the vectorised front against a plain per-point loop of the reference text, the truncated scan
-against the loop with `int dist` -- the main case is not vacuous, the planted points land on the gates' edges, the binding refuses what
-it can refuse without a device, and the drop-in header compiles and links."""
+against the loop with `int dist` -- the main case is not vacuous, the planted points land on the gates' edges, and the binding refuses what
+it can refuse without a device."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import projection_search_ref as PS
 import sim3_search_ref as S3
-from sim3_search_ref import MODES, build_driver, main_case, solved, to_capi, write_driver_case
+from sim3_search_ref import MODES, main_case, solved, to_capi, write_driver_case
 
 F32 = np.float32
 # ---------------------------------------------------------------- the front against the reference text, one map point at a time
@@ -175,13 +173,7 @@ def test_capi_binding_without_a_device():
                                                  *([None] * 7), z) == -1
 
 
-# ---------------------------------------------------------------- the drop-in header
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-def test_drop_in_header_compiles_and_links(tmp_path):
-    exe = build_driver(tmp_path)
-    assert subprocess.run([exe]).returncode == 0             # no arguments: nothing touches a device
-
-
+# ---------------------------------------------------------------- the drop-in driver's case
 def test_driver_case_keeps_the_problem(tmp_path):
     """t * s / s is not t in general: the driver's pose is its own, and the case is written so that validity survives the translation
     into isBad() / vpMatched"""

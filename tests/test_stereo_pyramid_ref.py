@@ -3,16 +3,15 @@ oracle -- equal to oracle.stereo_match at one level, descriptor distance equal t
 case with a known answer that exercises each octave rule once; plus the link-level checks of the new C ABI entries."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin_driver as DD
 import pyramid_ref as PR
 import stereo_pyramid_ref as SR
 from rover_slam_amd import weights as Wt, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MB, MBF = 0.11, 0.11 * 435.0
 
 
@@ -135,9 +134,4 @@ def test_exports_hold_the_new_entries():
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 @pytest.mark.parametrize("macro", [True, False])
 def test_driver_compiles_and_links(tmp_path, macro):
-    exe = str(tmp_path / "stereo_pyramid_driver")
-    cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + (["-DRFE_SP_PYRAMID=1"] if macro else [])
-    subprocess.check_call(cmd + [os.path.join(ROOT, "tests", "cpp", "stereo_pyramid_driver.cpp"), "-o", exe,
-                                 "-L" + os.path.join(ROOT, "rover-slam_amd"), "-lrover_fe", "-L/opt/rocm/lib", "-lamdhip64",
-                                 "-Wl,-rpath," + os.path.join(ROOT, "rover-slam_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    assert os.path.exists(exe)
+    assert os.path.exists(DD.build(tmp_path, "stereo_pyramid_driver", ("RFE_SP_PYRAMID=1",) if macro else ()))
