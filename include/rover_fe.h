@@ -698,7 +698,7 @@ int rfe_pose_optimization(rfe_ctx* ctx, const rfe_pose_params* params, const flo
  * rfe_sim3_ransac_iterations is SetRansacParameters' arithmetic (:137-147) on the host's libm: epsilon = (float)min_inliers / n, 1 when
  *   min_inliers == n, otherwise ceil(log(1 - probability) / log(1 - pow(epsilon, 3))), a quotient that is NaN or outside int converting
  *   to INT_MIN as on x86-64, then max(1, min(., max_its)).
- * Out of scope: KannalaBrandt8 cameras, OptimizeSim3, the descriptor matching in front, a device-side random generator. */
+ * Out of scope: KannalaBrandt8 cameras, the descriptor matching in front, a device-side random generator (OptimizeSim3: 6k, below). */
 typedef struct rfe_sim3_solver_params {
     float rcw1[9], tcw1[3], rcw2[9], tcw2[3];   /* row-major */
     float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
@@ -712,6 +712,65 @@ int rfe_sim3_ransac(rfe_ctx* ctx, const rfe_sim3_solver_params* params, const fl
                     const float* sigma2_2, const int32_t* draws, int B, int N, int H, float* T12, float* R, float* t, float* s,
                     uint8_t* inliers, uint8_t* best_inliers, int32_t* counts, float* hyps, int32_t* stats);
 int rfe_sim3_ransac_iterations(double probability, int min_inliers, int n, int max_its);
+
+/* ---- Optimizer::OptimizeSim3 on the device: the Sim3 refinement of a loop-closing candidate ----
+ * src/Optimizer.cc:4195-4494 over g2o's OptimizationAlgorithmLevenberg: one free 7-DoF VertexSim3Expmap and, per matched map-point pair,
+ * an EdgeSim3ProjectXYZ (pMP2 through S12 into KF1's image) and an EdgeInverseSim3ProjectXYZ (pMP1 through S12^-1 into KF2's), both
+ * linearised by g2o's NUMERIC central differences (delta 1e-9).  B problems per call, one workgroup each; the robust round, the chi2
+ * check, the plain round and the final classification run inside the kernel.  Double precision throughout; every sum over pairs in one
+ * fixed order, so the outputs equal the restatement tests/optimize_sim3_ref.py bit for bit (6k states the arithmetic and its four
+ * departures from the reference's own build).
+ * params [B] is a HOST array in both forms.  Per problem, of N rows the first n (clamped to 0..N) are rows of vpMatches1 and of N2 rows
+ * the first n2 are KF2's keypoints:
+ *   params[b]      rcw1 / rcw2 row-major and tcw1 / tcw2: GetRotation() / GetTranslation() of pKF1 and pKF2; fx fy cx cy of each Pinhole
+ *                  camera; nlevels and mvInvLevelSigma2 of each keyframe; th2; fix_scale; all_points; n; n2; iterations[3]: round 1, round 2
+ *                  when round 1 removed no pair, round 2 otherwise (0 = the reference's 5, 5, 10); max_trials (0 = g2o's 10)
+ *   s12_0 [8]      g2oS12 as qx qy qz qw tx ty tz s (doubles), taken as given: nothing is normalised
+ *   xw1, xw2 [N,3] GetWorldPos() of pMP1 = pKF1's map point i and of pMP2 = vpMatches1[i];  valid [N] != 0: both exist and neither isBad()
+ *   kpts1 [N,2]    pKF1->mvKeysUn[i].pt;  octave1 [N] its octave (NULL = 0; outside 0..nlevels1-1 reads level 0)
+ *   idx2 [N]       get<0>(pMP2->GetIndexInKeyFrame(pKF2)): < 0 not in KF2 -- the row is skipped unless all_points, and observes the
+ *                  NORMALISED float coordinates of pMP2 in KF2 at level 0, as the reference does (its own "BUG" comment, :4371-4382);
+ *                  at or above n2: treated the same and flag 8
+ *   kpts2 [N2,2], octave2 [N2]   pKF2->mvKeysUn[.].pt and octave (octave2 NULL = 0)
+ * A row carries an edge pair iff valid, (all_points or idx2 >= 0) and not (z of pMP2 in KF2's frame < 0).
+ * Outputs per problem: s12 [8] doubles, the estimate after round 2 -- the input when the return value is 0 through the early exit (:4457
+ *   returns before g2oS12 is written); s12_f32 [8] its plain cast (the Sim3f the caller composes mScw from; rfe_search_by_projection_sim3 takes its transform in
+ *   a HOST structure, so the chain into it costs one 32-byte read until that entry grows a device-side form); keep [N] in/out: cleared
+ *   exactly where the reference nulls vpMatches1[i], every other byte left alone; chi2 [N,2] the doubles (e12, e21) the last
+ *   classification of the row compared, rows without a pair left alone; trace [2,8] per round: LM iterations, trials, the final lambda,
+ *   the final currentChi, surviving pairs, 0, 0, 0; stats [8]: 0 the return value (nIn, or 0), 1 nCorrespondences, 2 nBad, 3 rounds run,
+ *   4 LM iterations, 5 trials, 6 rejected trials, 7 flags: 1 a round ended on a rejected trial (round 1's check then used the errors of
+ *   the rejected estimate, as the reference's does), 2 a solve found the system not positive, 4 a trial or the final estimate was not
+ *   finite, 8 an idx2 at or above n2, 16 the early exit (fewer than 10 pairs after round 1; with no pair at all no round runs).
+ *   mAcumHessian is only ever zeroed by the reference (:4465): the device produces nothing for it.
+ * The _dev form is asynchronous on the ctx stream: no host synchronisation, no host read of device data, no workspace; one launch per 8
+ * problems.  The host form stages its arrays (keep and chi2 go in and out) and returns stats[0] of problem 0 (0 when B = 0).
+ * s12_f32, chi2, trace, octave1, octave2 may be NULL; kpts2 when N2 = 0.
+ * Refused (RFE_ERR_INVALID): B outside 0..64; N or N2 outside 0..4096; nlevels1 / nlevels2 outside 1..RFE_MAX_LEVELS; a negative
+ *   iterations[] or max_trials; a NULL required pointer (params, s12_0, s12, keep, stats; xw1, xw2, valid, kpts1, idx2 when B N > 0; kpts2
+ *   when B N2 > 0); host form only: a non-finite pose, intrinsic, inv_level_sigma2 or th2.  The per-row arrays are not checked: a NaN
+ *   world position runs through as in the reference and raises flag 4.
+ * Out of scope: KannalaBrandt8 and two-camera rigs, SearchByBoW in front, composing mScw = gScm gSmw, everything else in Optimizer. */
+typedef struct rfe_optimize_sim3_params {
+    float rcw1[9], tcw1[3], rcw2[9], tcw2[3];   /* row-major */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    int32_t nlevels1;                           /* 1..RFE_MAX_LEVELS */
+    float inv_level_sigma2_1[RFE_MAX_LEVELS];   /* pKF1->mvInvLevelSigma2 */
+    int32_t nlevels2;
+    float inv_level_sigma2_2[RFE_MAX_LEVELS];   /* pKF2->mvInvLevelSigma2 */
+    float th2;
+    int32_t fix_scale, all_points, n, n2;
+    int32_t iterations[3];                      /* 0 = the reference's 5, 5, 10 */
+    int32_t max_trials;                         /* 0 = g2o's 10 */
+} rfe_optimize_sim3_params;
+int rfe_optimize_sim3_dev(rfe_ctx* ctx, const rfe_optimize_sim3_params* params, const double* s12_0_dev, const float* xw1_dev,
+                          const float* xw2_dev, const uint8_t* valid_dev, const float* kpts1_dev, const int32_t* octave1_dev,
+                          const int32_t* idx2_dev, const float* kpts2_dev, const int32_t* octave2_dev, int B, int N, int N2, double* s12_dev,
+                          float* s12_f32_dev, uint8_t* keep_dev, double* chi2_dev, double* trace_dev, int32_t* stats_dev);
+int rfe_optimize_sim3(rfe_ctx* ctx, const rfe_optimize_sim3_params* params, const double* s12_0, const float* xw1, const float* xw2,
+                      const uint8_t* valid, const float* kpts1, const int32_t* octave1, const int32_t* idx2, const float* kpts2,
+                      const int32_t* octave2, int B, int N, int N2, double* s12, float* s12_f32, uint8_t* keep, double* chi2, double* trace,
+                      int32_t* stats);
 
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform

@@ -26,7 +26,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -279,6 +279,45 @@ lib.rfe_sim3_ransac_iterations.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int
 def sim3_ransac_iterations(probability, min_inliers, n, max_its):
     """SetRansacParameters' mRansacMaxIts (rfe_sim3_ransac_iterations; needs no device)"""
     return int(lib.rfe_sim3_ransac_iterations(float(probability), int(min_inliers), int(n), int(max_its)))
+class OptimizeSim3Params(C.Structure):
+    """include/rover_fe.h: rfe_optimize_sim3_params -- both keyframes' poses, cameras and level tables, th2, the flags, n / n2 and the LM
+    schedule of one OptimizeSim3 problem."""
+    _fields_ = [("rcw1", C.c_float * 9), ("tcw1", C.c_float * 3), ("rcw2", C.c_float * 9), ("tcw2", C.c_float * 3),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("nlevels1", C.c_int32), ("inv_level_sigma2_1", C.c_float * MAX_LEVELS),
+                ("nlevels2", C.c_int32), ("inv_level_sigma2_2", C.c_float * MAX_LEVELS), ("th2", C.c_float),
+                ("fix_scale", C.c_int32), ("all_points", C.c_int32), ("n", C.c_int32), ("n2", C.c_int32),
+                ("iterations", C.c_int32 * 3), ("max_trials", C.c_int32)]
+
+
+def optimize_sim3_params(problems):
+    """an rfe_optimize_sim3_params array from dicts with rcw1, tcw1, rcw2, tcw2, cam1 / cam2 = (fx, fy, cx, cy), inv1 / inv2
+    (mvInvLevelSigma2 of each keyframe), th2, fix_scale, all_points, n, n2 and optionally iterations (3), max_trials, nlevels1, nlevels2"""
+    arr = (OptimizeSim3Params * max(len(problems), 1))()
+    for p, d in zip(arr, problems):
+        for k in ("rcw1", "tcw1", "rcw2", "tcw2"):
+            getattr(p, k)[:] = [float(v) for v in np.asarray(d[k], np.float32).reshape(-1)]
+        p.fx1, p.fy1, p.cx1, p.cy1 = (float(v) for v in d["cam1"])
+        p.fx2, p.fy2, p.cx2, p.cy2 = (float(v) for v in d["cam2"])
+        for side in ("1", "2"):
+            inv = list(np.asarray(d["inv" + side], np.float32).reshape(-1))
+            setattr(p, "nlevels" + side, int(d.get("nlevels" + side, len(inv))))
+            for l, v in enumerate(inv[:MAX_LEVELS]):
+                getattr(p, "inv_level_sigma2_" + side)[l] = float(v)
+        p.th2 = float(d["th2"])
+        p.fix_scale, p.all_points, p.n, p.n2 = int(d["fix_scale"]), int(d["all_points"]), int(d["n"]), int(d["n2"])
+        p.iterations[:] = [int(v) for v in d.get("iterations", (0, 0, 0))]
+        p.max_trials = int(d.get("max_trials", 0))
+    return arr
+
+
+OPTIMIZE_SIM3_OUTPUTS = ("s12_f32", "chi2", "trace")
+_os3 = [C.c_void_p, C.c_void_p, _vp, _fp, _fp, _u8p, _fp, _ip, _ip, _fp, _ip, C.c_int, C.c_int, C.c_int, _vp, _fp, _u8p, _vp, _vp, _ip]
+lib.rfe_optimize_sim3.argtypes = _os3
+lib.rfe_optimize_sim3_dev.argtypes = _os3
+
+
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
 BOW_MAX_N = 4096
@@ -1162,6 +1201,54 @@ class Context:
         P = problems if isinstance(problems, C.Array) else sim3_solver_params(problems)
         self._chk(lib.rfe_sim3_ransac_dev(self.h, C.addressof(P), a(xw1), a(xw2), a(sigma2_1), a(sigma2_2), a(draws), int(B), int(N), int(H),
                                           a(T12), a(R), a(t), a(s), a(inliers), a(best_inliers), a(counts), a(hyps), a(stats)))
+
+    def optimize_sim3(self, problems, s12_0, xw1, xw2, valid, kpts1, idx2, kpts2, octave1=None, octave2=None, keep=None, chi2=None,
+                      outputs=OPTIMIZE_SIM3_OUTPUTS):
+        """Optimizer::OptimizeSim3 for B problems (rfe_optimize_sim3, host arrays; DESIGN.md 6k).  problems: B dicts
+        (optimize_sim3_params()) or the ctypes array; s12_0 [B,8] float64 qx qy qz qw tx ty tz s; xw1 / xw2 [B,N,3], valid / octave1 / idx2
+        [B,N], kpts1 [B,N,2], kpts2 [B,N2,2], octave2 [B,N2].  keep / chi2: what those arrays hold where the call does not write (default 1 /
+        0).  outputs: the optional arrays to ask for (the others are passed as NULL).  Returns a dict: s12 [B,8] float64, keep [B,N], stats
+        [B,8], ret, and s12_f32 / chi2 [B,N,2] / trace [B,2,8] as asked."""
+        P = problems if isinstance(problems, C.Array) else optimize_sim3_params(problems)
+        s0 = np.ascontiguousarray(s12_0, np.float64).reshape(-1, 8)
+        B = s0.shape[0]                            # not len(problems): a prepared array of no problems still has one element
+        assert len(P) >= B
+        v = np.ascontiguousarray(valid, np.uint8)
+        N = v.size // B if B else 0
+        k2 = np.ascontiguousarray(kpts2, np.float32)
+        N2 = k2.size // (2 * B) if B else 0
+        f, g = B * N, B * N2
+        x1, x2, k1, i2 = _opt(xw1, np.float32), _opt(xw2, np.float32), _opt(kpts1, np.float32), _opt(idx2, np.int32)
+        o1, o2 = _opt(octave1, np.int32), _opt(octave2, np.int32)
+        assert len(x1) == len(x2) == f * 3 and len(k1) == f * 2 and len(i2) == f
+        assert (o1 is None or len(o1) == f) and (o2 is None or len(o2) == g)
+        b1, f1 = max(B, 1), max(f, 1)
+        kp = np.ones((f1,), np.uint8)
+        c2 = np.zeros((f1, 2), np.float64)
+        if keep is not None:
+            kp[:f] = np.asarray(keep, np.uint8).reshape(-1)
+        if chi2 is not None:
+            c2[:f] = np.asarray(chi2, np.float64).reshape(-1, 2)
+        s12, sf = np.zeros((b1, 8), np.float64), np.zeros((b1, 8), np.float32)
+        tr, st = np.zeros((b1, 2, 8), np.float64), np.zeros((b1, 8), np.int32)
+        opt = {"s12_f32": sf, "chi2": c2, "trace": tr}
+        ret = self._chk(lib.rfe_optimize_sim3(self.h, C.addressof(P), s0.ctypes.data, _addr(x1), _addr(x2), _addr(v.reshape(-1)), _addr(k1),
+                                              _addr(o1), _addr(i2), _addr(k2.reshape(-1)) if g else None, _addr(o2), B, N, N2, s12.ctypes.data,
+                                              sf.ctypes.data if "s12_f32" in outputs else None, kp.ctypes.data,
+                                              c2.ctypes.data if "chi2" in outputs else None, tr.ctypes.data if "trace" in outputs else None,
+                                              st.ctypes.data))
+        r = {"s12": s12[:B], "keep": kp[:f].reshape(B, N), "stats": st[:B], "ret": ret}
+        r.update({key: (a[:f].reshape(B, N, 2) if key == "chi2" else a[:B]) for key, a in opt.items() if key in outputs})
+        return r
+
+    def optimize_sim3_dev(self, problems, s12_0, xw1, xw2, valid, kpts1, idx2, kpts2, B, N, N2, s12, keep, stats, octave1=None, octave2=None,
+                          s12_f32=None, chi2=None, trace=None):
+        """rfe_optimize_sim3_dev: problems is a HOST array (optimize_sim3_params()), every other array a DevBuf (or a raw device address /
+        torch tensor); asynchronous on the ctx stream."""
+        a = _dev
+        P = problems if isinstance(problems, C.Array) else optimize_sim3_params(problems)
+        self._chk(lib.rfe_optimize_sim3_dev(self.h, C.addressof(P), a(s12_0), a(xw1), a(xw2), a(valid), a(kpts1), a(octave1), a(idx2), a(kpts2),
+                                            a(octave2), int(B), int(N), int(N2), a(s12), a(s12_f32), a(keep), a(chi2), a(trace), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

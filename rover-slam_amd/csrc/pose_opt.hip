@@ -7,6 +7,7 @@
 // rounding per operation (-ffp-contract=off); tests/pose_opt_ref.py restates it operation by operation.
 #include <float.h>
 #include "rfe_internal.h"
+#include "lm_device.h"
 
 namespace rfe {
 namespace {
@@ -29,49 +30,6 @@ struct PoseProblem {
     int N;
 };
 
-// ---------------------------------------------------------------- departure (b): sin and cos of theta >= 0
-__device__ void po_sincos(double theta, double& s, double& c) {
-    const double k = floor(theta * 0x1.45f306dc9c883p-1 + 0.5);
-    double r = (((theta - k * 0x1.921fb544p+0) - k * 0x1.0b4611a6p-34) - k * 0x1.3198a2ep-69) - k * 0x1.b839a252049c1p-104;
-    if (!(fabs(r) <= 0.79)) r = 0.0;
-    const int q = isfinite(k) ? (int)(k - 4.0 * floor(k * 0.25)) : 0;
-    const double z = r * r;
-    double ps = 0x1.5d93a5acfd57cp-33;
-    ps = -0x1.ae5e68a2b9cebp-26 + z * ps;
-    ps = 0x1.71de357b1fe7dp-19 + z * ps;
-    ps = -0x1.a01a019c161d5p-13 + z * ps;
-    ps = 0x1.111111110f8a6p-7 + z * ps;
-    ps = -0x1.5555555555549p-3 + z * ps;
-    double sn = r + (r * z) * ps;
-    double pc = -0x1.8fae9be8838d4p-37;
-    pc = 0x1.1ee9ebdb4b1c4p-29 + z * pc;
-    pc = -0x1.27e4f809c52adp-22 + z * pc;
-    pc = 0x1.a01a019cb159p-16 + z * pc;
-    pc = -0x1.6c16c16c15177p-10 + z * pc;
-    pc = 0x1.555555555554cp-5 + z * pc;
-    double cs = (1.0 - 0.5 * z) + (z * z) * pc;
-    if (q == 1) { const double t = sn; sn = cs; cs = -t; }
-    else if (q == 2) { sn = -sn; cs = -cs; }
-    else if (q == 3) { const double t = sn; sn = -cs; cs = t; }
-    s = fmin(fmax(sn, -1.0), 1.0);
-    c = fmin(fmax(cs, -1.0), 1.0);
-}
-
-// ---------------------------------------------------------------- SE3 (q = x y z w)
-__device__ void po_normalize(double* q) {
-    double x = q[0], y = q[1], z = q[2], w = q[3];
-    if (w < 0) { x = -x; y = -y; z = -z; w = -w; }
-    const double n = sqrt(((x * x + y * y) + z * z) + w * w);
-    q[0] = x / n; q[1] = y / n; q[2] = z / n; q[3] = w / n;
-}
-// Eigen's quaternion * vector: uv = 2 (v x X); X + w uv + v x uv
-__device__ void po_rotate(const double* q, double X0, double X1, double X2, double& o0, double& o1, double& o2) {
-    double u0 = q[1] * X2 - q[2] * X1, u1 = q[2] * X0 - q[0] * X2, u2 = q[0] * X1 - q[1] * X0;
-    u0 = u0 + u0; u1 = u1 + u1; u2 = u2 + u2;
-    const double c0 = q[1] * u2 - q[2] * u1, c1 = q[2] * u0 - q[0] * u2, c2 = q[0] * u1 - q[1] * u0;
-    o0 = (X0 + q[3] * u0) + c0; o1 = (X1 + q[3] * u1) + c1; o2 = (X2 + q[3] * u2) + c2;
-}
-
 // ---------------------------------------------------------------- the serial section's state, in LDS: lane 0 alone touches it between barriers
 struct PoseSerial {
     double sums[PO_TERMS];          // what the last pass left
@@ -84,65 +42,9 @@ struct PoseSerial {
     int n_init, n_bad;
 };
 
-// departure (c): LDLT with diagonal pivoting on A = H + lambda I; false: a negative pivot.  The solution replaces S.x only on success.
-// Every index is a compile-time constant after unrolling (the pivot's row is found by comparing with each candidate), so the matrix stays
-// in registers
+// departure (c): lm_device.h's pivoted LDLT on A = H + lambda I; false: a negative pivot.  The solution replaces S.x only on success
 __device__ bool po_solve(PoseSerial& S) {
-    double A[6][6], y[6], d[6];
-    int perm[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) A[i][j] = (i == j) ? S.H[i][j] + S.lambda : S.H[i][j];
-        perm[i] = i;
-        y[i] = S.b[i];                                   // permuted along with the rows: y[i] = b[perm[i]]
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        int p = k; double best = fabs(A[k][k]);
-#pragma unroll
-        for (int j = k + 1; j < 6; ++j) {
-            const double a = fabs(A[j][j]);
-            if (a > best) { p = j; best = a; }
-        }
-#pragma unroll
-        for (int r = k + 1; r < 6; ++r)
-            if (r == p) {
-#pragma unroll
-                for (int j = 0; j < 6; ++j) { const double t = A[k][j]; A[k][j] = A[r][j]; A[r][j] = t; }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { const double t = A[i][k]; A[i][k] = A[i][r]; A[i][r] = t; }
-                const int t = perm[k]; perm[k] = perm[r]; perm[r] = t;
-                const double u = y[k]; y[k] = y[r]; y[r] = u;
-            }
-        d[k] = A[k][k];
-        if (d[k] < 0.0) return false;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) A[i][k] = (d[k] != 0.0) ? A[i][k] / d[k] : 0.0;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i)
-#pragma unroll
-            for (int j = k + 1; j <= i; ++j) {
-                const double v = A[i][j] - A[i][k] * A[k][j];
-                A[i][j] = v; A[j][i] = v;
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j < i; ++j) y[i] = y[i] - A[i][j] * y[j];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = (d[i] != 0.0) ? y[i] / d[i] : 0.0;
-#pragma unroll
-    for (int i = 5; i >= 0; --i)
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) y[i] = y[i] - A[j][i] * y[j];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-            if (perm[i] == r) S.x[r] = y[i];
-    return true;
+    return lm_ldlt_solve<6>(S.H, S.lambda, S.b, S.x);
 }
 
 // SE3Quat::exp(x) * cur -> est (se3quat.h:223-257, :104-110)
@@ -169,45 +71,16 @@ __device__ void po_update(PoseSerial& S) {
     }
     double t1[3];
     for (int r = 0; r < 3; ++r) t1[r] = (V[r][0] * S.x[3] + V[r][1] * S.x[4]) + V[r][2] * S.x[5];
-    // Eigen's matrix -> quaternion
     double q1[4];
-    double t = (R[0][0] + R[1][1]) + R[2][2];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q1[3] = 0.5 * t;
-        t = 0.5 / t;
-        q1[0] = (R[2][1] - R[1][2]) * t; q1[1] = (R[0][2] - R[2][0]) * t; q1[2] = (R[1][0] - R[0][1]) * t;
-    } else {
-        int i = 0;
-        if (R[1][1] > R[0][0]) i = 1;
-        if (R[2][2] > (i == 1 ? R[1][1] : R[0][0])) i = 2;
-        // i, j = (i + 1) % 3, k = (j + 1) % 3, one branch per i so that no index is computed at run time
-        if (i == 0) {
-            t = sqrt(((R[0][0] - R[1][1]) - R[2][2]) + 1.0);
-            q1[0] = 0.5 * t; t = 0.5 / t;
-            q1[3] = (R[2][1] - R[1][2]) * t; q1[1] = (R[1][0] + R[0][1]) * t; q1[2] = (R[2][0] + R[0][2]) * t;
-        } else if (i == 1) {
-            t = sqrt(((R[1][1] - R[2][2]) - R[0][0]) + 1.0);
-            q1[1] = 0.5 * t; t = 0.5 / t;
-            q1[3] = (R[0][2] - R[2][0]) * t; q1[2] = (R[2][1] + R[1][2]) * t; q1[0] = (R[0][1] + R[1][0]) * t;
-        } else {
-            t = sqrt(((R[2][2] - R[0][0]) - R[1][1]) + 1.0);
-            q1[2] = 0.5 * t; t = 0.5 / t;
-            q1[3] = (R[1][0] - R[0][1]) * t; q1[0] = (R[0][2] + R[2][0]) * t; q1[1] = (R[1][2] + R[2][1]) * t;
-        }
-    }
+    po_mat_to_quat(R, q1);
     po_normalize(q1);
     // (q1, t1) * cur: t = t1 + q1 * t_cur, q = q1 q_cur, normalised
     const double* c = S.cur;
     double r0, r1, r2;
     po_rotate(q1, c[4], c[5], c[6], r0, r1, r2);
     S.est[4] = t1[0] + r0; S.est[5] = t1[1] + r1; S.est[6] = t1[2] + r2;
-    const double ax = q1[0], ay = q1[1], az = q1[2], aw = q1[3], bx = c[0], by = c[1], bz = c[2], bw = c[3];
     double q[4];
-    q[0] = ((aw * bx + ax * bw) + ay * bz) - az * by;
-    q[1] = ((aw * by + ay * bw) + az * bx) - ax * bz;
-    q[2] = ((aw * bz + az * bw) + ax * by) - ay * bx;
-    q[3] = ((aw * bw - ax * bx) - ay * by) - az * bz;
+    po_quat_mul(q1, c, q);
     po_normalize(q);
     bool fin = true;
     for (int i = 0; i < 4; ++i) { S.est[i] = q[i]; fin = fin && isfinite(q[i]); }
@@ -394,33 +267,6 @@ __device__ void po_edge_terms(const PoseCam& C, const PoseEdge& E, const double*
     acc[27] = acc[27] + rho0;
 }
 
-// the 256 partials by stride halving: 128 and 64 through LDS, 32 .. 1 inside wave 0; lane 0 leaves the totals in out
-__device__ void po_reduce(double (&acc)[PO_TERMS], double* red, double* out, int lane) {
-    if (lane >= 128)
-#pragma unroll
-        for (int c = 0; c < PO_TERMS; ++c) red[c * 128 + (lane - 128)] = acc[c];
-    __syncthreads();
-    if (lane < 128)
-#pragma unroll
-        for (int c = 0; c < PO_TERMS; ++c) acc[c] = acc[c] + red[c * 128 + lane];
-    __syncthreads();
-    if (lane >= 64 && lane < 128)
-#pragma unroll
-        for (int c = 0; c < PO_TERMS; ++c) red[c * 128 + (lane - 64)] = acc[c];
-    __syncthreads();
-    if (lane < 64) {
-#pragma unroll
-        for (int c = 0; c < PO_TERMS; ++c) acc[c] = acc[c] + red[c * 128 + lane];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1)
-#pragma unroll
-            for (int c = 0; c < PO_TERMS; ++c) acc[c] = acc[c] + __shfl_down(acc[c], s, 64);
-        if (lane == 0)
-#pragma unroll
-            for (int c = 0; c < PO_TERMS; ++c) out[c] = acc[c];
-    }
-}
-
 __global__ __launch_bounds__(PO_LANES) void pose_opt_kernel(rfe_pose_params P, PoseProblem pr0) {
     __shared__ double red[128 * PO_TERMS];
     __shared__ float chi2f[PO_MAX_N];               // (float) chi2 of the error the last computeActiveErrors left on the edge
@@ -498,7 +344,7 @@ __global__ __launch_bounds__(PO_LANES) void pose_opt_kernel(rfe_pose_params P, P
                 po_edge_terms(C, E, q, robust, acc, cf);
                 chi2f[i] = cf;
             }
-            po_reduce(acc, red, S.sums, lane);       // its barriers also order the reads of S.est above before lane 0's writes below
+            lm_reduce<PO_TERMS>(acc, red, S.sums, lane);       // its barriers also order the reads of S.est above before lane 0's writes below
             if (lane == 0) po_serial_step(S);
             __syncthreads();
             if (S.done) break;

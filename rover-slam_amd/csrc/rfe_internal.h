@@ -422,6 +422,15 @@ void launch_pose_opt(hipStream_t s, const rfe_pose_params& P, const float* pose0
                      const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose, float* pose_f32, uint8_t* outlier,
                      float* chi2, double* trace, int32_t* stats);
 
+// optimize_sim3.hip: Optimizer::OptimizeSim3, one workgroup per problem.  params is a HOST array: the kernel takes it by
+// value, OS_CHUNK problems per launch.  octave1 / octave2 / s12_f32 / chi2 / trace may be NULL (kpts2 too when N2 = 0); needs no workspace
+// and presets nothing
+constexpr int OS_CHUNK = 8;
+void launch_optimize_sim3(hipStream_t s, const rfe_optimize_sim3_params* params, const double* s12_0, const float* xw1, const float* xw2,
+                          const uint8_t* valid, const float* kpts1, const int32_t* octave1, const int32_t* idx2, const float* kpts2,
+                          const int32_t* octave2, int B, int N, int N2, double* s12, float* s12_f32, uint8_t* keep, double* chi2, double* trace,
+                          int32_t* stats);
+
 // sim3_solver.hip: Sim3Solver's RANSAC with every hypothesis at once.  params is a HOST array: the front takes it by value,
 // S3_FRONT_CHUNK problems per launch, and leaves prob [B]; front [B, 12, N], counts [B, H] and hyps [B, H, 32] are workspace (or the
 // caller's counts / hyps).  R / t / sc / inliers / best_inliers may be NULL; presets nothing
