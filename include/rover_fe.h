@@ -772,6 +772,66 @@ int rfe_optimize_sim3(rfe_ctx* ctx, const rfe_optimize_sim3_params* params, cons
                       const int32_t* octave2, int B, int N, int N2, double* s12, float* s12_f32, uint8_t* keep, double* chi2, double* trace,
                       int32_t* stats);
 
+/* ---- Optimizer::LocalBundleAdjustment on the device: the local-mapping thread's Schur-complement LM ----
+ * src/Optimizer.cc:1857-2150 over g2o's BlockSolver_6_3 and OptimizationAlgorithmLevenberg: P free and F fixed SE3 keyframe vertices, L
+ * marginalised 3-DoF point vertices, one mono (EdgeSE3ProjectXYZ) or stereo (EdgeStereoSE3ProjectXYZ) Huber edge per observation, ONE
+ * robust optimize(iterations) and one classification.  One problem per call.  Double precision throughout; every sum in one fixed order,
+ * so the outputs equal the restatement tests/local_ba_ref.py bit for bit (6l states the arithmetic and its departures from the
+ * reference's own build, among them a dense unpivoted LDLT for the reduced pose system).
+ *   K = P + F keyframes, the P free ones first in ascending mnId (g2o's Hessian order), then the fixed ones (the map's init keyframe
+ *   goes with the fixed ones):  kf_pose [K,7] qx qy qz qw tx ty tz of GetPose() (widened and normalised as 6i);  kf_cam [K,5] fx fy cx cy
+ *   mbf;  kf_nlevels [K] and kf_inv_level_sigma2 [K, RFE_MAX_LEVELS] (mvInvLevelSigma2);  kf_feat_off [K + 1]: keyframe k's features are
+ *   rows kf_feat_off[k] .. kf_feat_off[k + 1] - 1 of kpts_un [Nf,2] (mvKeysUn[.].pt), octave [Nf] (NULL = 0; outside 0..nlevels-1 reads
+ *   level 0) and uright [Nf] (mvuRight; NULL = all mono)
+ *   xw [L,3]: GetWorldPos() of the local map points in ascending mnId
+ *   edge_point / edge_kf / edge_feat [E]: one row per observation, point index, keyframe index, feature index INSIDE that keyframe; sorted
+ *   by (point, keyframe) strictly ascending.  uright < 0: a mono edge; otherwise (NaN too) stereo
+ * Outputs: pose [P,7] doubles and pose_f32 their cast (the free keyframes); point [L,3] and point_f32; erase [E] = chi2 > th2 ||
+ *   !isDepthPositive, where chi2 [E] is the value the last computeActiveErrors left on the edge (stale after a run that ends on a
+ *   rejected trial: flag 1) and the depth is taken at the final estimates; trace [iterations,4] per LM iteration run: trials, the lambda it
+ *   left, currentChi, 0 (rows of iterations not run are zero); stats [8]: 0 LM iterations, 1 trials, 2 rejected trials, 3 failed solves,
+ *   4 edges erased, 5 flags, 6 edges on free keyframes, 7 Schur pair-list entries.  Flags: 1 ended on a rejected trial, 2 a solve met a
+ *   zero or non-finite pivot, 4 a trial or the final estimate was not finite, 8 *stop was seen set, 16 no LM iteration ran (iterations
+ *   = 0 or stop preset): the reference would classify errors nobody computed; this entry evaluates them at the input estimate.
+ * BOTH forms are synchronous: the LM loop runs on the host, one plain launch per stage on the ctx stream and one small pinned read per
+ * trial, and `stop` (a HOST pointer, pbStopFlag, may be NULL) is read where g2o's terminate() is: before each iteration and after each
+ * trial.  rfe_local_ba_dev keeps every array on the device but returns only when the optimisation has finished -- the one _dev entry
+ * that is not asynchronous.  It validates the edge and keyframe tables in its first kernel and reads the verdict before anything else is
+ * launched, so a bad index is a refusal, never a stray access.  Both return the number of erased edges (>= 0).
+ * pose_f32, point_f32, chi2, trace, octave, uright may be NULL.
+ * Refused (RFE_ERR_INVALID): P outside 0..RFE_LBA_MAX_FREE, K = P + F outside 1..RFE_LBA_MAX_KF, L outside 0..RFE_LBA_MAX_POINTS, E outside
+ *   0..RFE_LBA_MAX_EDGES, Nf < 0; iterations outside 0..RFE_LBA_MAX_ITERATIONS, max_trials < 0; a non-finite th2 or user_lambda_init; a NULL
+ *   required pointer; an nlevels outside 1..RFE_MAX_LEVELS; a kf_feat_off that decreases or leaves 0..Nf; an edge index out of range;
+ *   edges not strictly ascending in (point, keyframe).  Nothing is written then.  The poses, positions and observations are not
+ *   checked: a NaN world position runs through as in the reference and raises flags 2 and 4.
+ * Out of scope: LocalInertialBA, the merge overload, global BundleAdjustment, EdgeSE3ProjectXYZToBody (two-camera rigs), KannalaBrandt8. */
+#define RFE_LBA_MAX_FREE 64
+#define RFE_LBA_MAX_KF 256
+#define RFE_LBA_MAX_POINTS 16384
+#define RFE_LBA_MAX_EDGES 131072
+#define RFE_LBA_MAX_ITERATIONS 64
+#define RFE_LBA_FLAG_ENDED_REJECTED 1
+#define RFE_LBA_FLAG_SOLVE_FAILED 2
+#define RFE_LBA_FLAG_NONFINITE 4
+#define RFE_LBA_FLAG_STOPPED 8
+#define RFE_LBA_FLAG_NO_ITERATION 16
+typedef struct rfe_local_ba_params {
+    int32_t iterations;          /* optimizer.optimize(10); 0 runs none */
+    int32_t max_trials;          /* 0 = g2o's 10 */
+    double user_lambda_init;     /* 0, or 100 for pMap->IsInertial() */
+    double th2_mono, th2_stereo; /* 5.991, 7.815: the classification compares doubles; the Huber deltas are (float) sqrt of them */
+    const volatile uint8_t* stop;/* HOST pointer or NULL: pbStopFlag */
+} rfe_local_ba_params;
+int rfe_local_ba_dev(rfe_ctx* ctx, rfe_local_ba_params params, const float* kf_pose_dev, const float* kf_cam_dev, const int32_t* kf_nlevels_dev,
+                     const float* kf_inv_level_sigma2_dev, const int32_t* kf_feat_off_dev, const float* kpts_un_dev, const int32_t* octave_dev,
+                     const float* uright_dev, const float* xw_dev, const int32_t* edge_point_dev, const int32_t* edge_kf_dev,
+                     const int32_t* edge_feat_dev, int P, int F, int L, int E, int Nf, double* pose_dev, float* pose_f32_dev, double* point_dev,
+                     float* point_f32_dev, uint8_t* erase_dev, double* chi2_dev, double* trace_dev, int32_t* stats_dev);
+int rfe_local_ba(rfe_ctx* ctx, rfe_local_ba_params params, const float* kf_pose, const float* kf_cam, const int32_t* kf_nlevels,
+                 const float* kf_inv_level_sigma2, const int32_t* kf_feat_off, const float* kpts_un, const int32_t* octave, const float* uright,
+                 const float* xw, const int32_t* edge_point, const int32_t* edge_kf, const int32_t* edge_feat, int P, int F, int L, int E, int Nf,
+                 double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* erase, double* chi2, double* trace, int32_t* stats);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates

@@ -26,7 +26,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -316,6 +316,27 @@ OPTIMIZE_SIM3_OUTPUTS = ("s12_f32", "chi2", "trace")
 _os3 = [C.c_void_p, C.c_void_p, _vp, _fp, _fp, _u8p, _fp, _ip, _ip, _fp, _ip, C.c_int, C.c_int, C.c_int, _vp, _fp, _u8p, _vp, _vp, _ip]
 lib.rfe_optimize_sim3.argtypes = _os3
 lib.rfe_optimize_sim3_dev.argtypes = _os3
+
+
+class LocalBaParams(C.Structure):
+    """include/rover_fe.h: rfe_local_ba_params, passed BY VALUE -- the LM schedule of one LocalBundleAdjustment, the two chi2 thresholds and
+    the host address of pbStopFlag (0 = none)."""
+    _fields_ = [("iterations", C.c_int32), ("max_trials", C.c_int32), ("user_lambda_init", C.c_double), ("th2_mono", C.c_double),
+                ("th2_stereo", C.c_double), ("stop", C.c_void_p)]
+
+
+def local_ba_params(iterations=10, max_trials=0, user_lambda_init=0.0, th2_mono=5.991, th2_stereo=7.815, stop=None):
+    """stop: None, or a numpy uint8 array of one element that the caller keeps alive (pbStopFlag)"""
+    return LocalBaParams(int(iterations), int(max_trials), float(user_lambda_init), float(th2_mono), float(th2_stereo),
+                         None if stop is None else stop.ctypes.data)
+
+
+LOCAL_BA_OUTPUTS = ("pose_f32", "point_f32", "chi2", "trace")
+LBA_MAX_FREE, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES, LBA_MAX_ITERATIONS = 64, 256, 16384, 131072, 64
+_lba = [C.c_void_p, LocalBaParams, _fp, _fp, _ip, _fp, _ip, _fp, _ip, _fp, _fp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+        _vp, _fp, _vp, _fp, _u8p, _vp, _vp, _ip]
+lib.rfe_local_ba.argtypes = _lba
+lib.rfe_local_ba_dev.argtypes = _lba
 
 
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
@@ -1249,6 +1270,41 @@ class Context:
         P = problems if isinstance(problems, C.Array) else optimize_sim3_params(problems)
         self._chk(lib.rfe_optimize_sim3_dev(self.h, C.addressof(P), a(s12_0), a(xw1), a(xw2), a(valid), a(kpts1), a(octave1), a(idx2), a(kpts2),
                                             a(octave2), int(B), int(N), int(N2), a(s12), a(s12_f32), a(keep), a(chi2), a(trace), a(stats)))
+
+    def local_ba(self, params, P, F, kf_pose, kf_cam, kf_nlevels, kf_sigma2, kf_feat_off, kpts, xw, edge_point, edge_kf, edge_feat, octave=None,
+                 uright=None, outputs=LOCAL_BA_OUTPUTS, shape=None):
+        """Optimizer::LocalBundleAdjustment for one problem (rfe_local_ba, host arrays; DESIGN.md 6l).  params: local_ba_params(); P free
+        keyframes first, then F fixed; kf_pose [K,7], kf_cam [K,5], kf_nlevels [K], kf_sigma2 [K,16], kf_feat_off [K+1]; kpts [Nf,2], octave /
+        uright [Nf]; xw [L,3]; edge_point / edge_kf / edge_feat [E].  shape: (L, E, Nf) when the arrays are longer than the problem (what
+        lies behind is not read).  outputs: the optional arrays to ask for.  Returns a dict: pose [P,7] and point [L,3] float64, erase [E],
+        stats [8], ret, and pose_f32 / point_f32 / chi2 [E] / trace [iterations,4] as asked."""
+        kp, kc, ks = _opt(kf_pose, np.float32), _opt(kf_cam, np.float32), _opt(kf_sigma2, np.float32)
+        nl, fo = _opt(kf_nlevels, np.int32), _opt(kf_feat_off, np.int32)
+        k, x = _opt(kpts, np.float32), _opt(xw, np.float32)
+        ep, ek, ef = _opt(edge_point, np.int32), _opt(edge_kf, np.int32), _opt(edge_feat, np.int32)
+        oc, ur = _opt(octave, np.int32), _opt(uright, np.float32)
+        L, E, Nf = (len(x) // 3, len(ep), len(k) // 2) if shape is None else shape
+        its = max(int(params.iterations), 0)
+        o = {"pose": np.zeros((max(P, 1), 7), np.float64), "pose_f32": np.zeros((max(P, 1), 7), np.float32),
+             "point": np.zeros((max(L, 1), 3), np.float64), "point_f32": np.zeros((max(L, 1), 3), np.float32),
+             "erase": np.zeros((max(E, 1),), np.uint8), "chi2": np.zeros((max(E, 1),), np.float64),
+             "trace": np.zeros((max(its, 1), 4), np.float64), "stats": np.zeros((8,), np.int32)}
+        ad = [o[n].ctypes.data if (n not in LOCAL_BA_OUTPUTS or n in outputs) else None for n in o]
+        ret = self._chk(lib.rfe_local_ba(self.h, params, _addr(kp), _addr(kc), _addr(nl), _addr(ks), _addr(fo), _addr(k), _addr(oc), _addr(ur),
+                                         _addr(x), _addr(ep), _addr(ek), _addr(ef), int(P), int(F), int(L), int(E), int(Nf), *ad))
+        n = {"pose": P, "pose_f32": P, "point": L, "point_f32": L, "erase": E, "chi2": E, "trace": its, "stats": 8}
+        r = {key: a[:n[key]] for key, a in o.items() if key not in LOCAL_BA_OUTPUTS or key in outputs}
+        r["ret"] = ret
+        return r
+
+    def local_ba_dev(self, params, P, F, L, E, Nf, kf_pose, kf_cam, kf_nlevels, kf_sigma2, kf_feat_off, kpts, xw, edge_point, edge_kf, edge_feat,
+                     pose, point, erase, stats, octave=None, uright=None, pose_f32=None, point_f32=None, chi2=None, trace=None):
+        """rfe_local_ba_dev: every array a DevBuf (or a raw device address / torch tensor).  SYNCHRONOUS: returns the number of erased
+        edges when the optimisation has finished."""
+        a = _dev
+        return self._chk(lib.rfe_local_ba_dev(self.h, params, a(kf_pose), a(kf_cam), a(kf_nlevels), a(kf_sigma2), a(kf_feat_off), a(kpts), a(octave),
+                                              a(uright), a(xw), a(edge_point), a(edge_kf), a(edge_feat), int(P), int(F), int(L), int(E), int(Nf),
+                                              a(pose), a(pose_f32), a(point), a(point_f32), a(erase), a(chi2), a(trace), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

@@ -1,5 +1,5 @@
-// lm_device.h -- device functions the one-workgroup Levenberg-Marquardt kernels share (pose_opt.hip; optimize_sim3.hip, 6k):
-// the explicit sin / cos of departure (b), Eigen's quaternion arithmetic, the pivoted LDLT of departure (c) on a D x D system and the
+// lm_device.h -- device functions the Levenberg-Marquardt kernels share (pose_opt.hip; optimize_sim3.hip, 6k; local_ba.hip, 6l):
+// the explicit sin / cos of departure (b), Eigen's quaternion arithmetic, SE3Quat's exp and product, the pivoted LDLT of departure (c) on a D x D system and the
 // stride-halving reduction of departure (a).  Everything is double, one rounding per operation (-ffp-contract=off); the numpy restatements
 // tests/pose_opt_ref.py and tests/optimize_sim3_ref.py state the same operations in the same order.
 #pragma once
@@ -107,6 +107,47 @@ __device__ inline void po_mat_to_quat(const double (&R)[3][3], double* q1) {
             q1[3] = (R[1][0] - R[0][1]) * t; q1[0] = (R[0][2] + R[2][0]) * t; q1[1] = (R[1][2] + R[2][1]) * t;
         }
     }
+}
+
+// ---------------------------------------------------------------- SE3Quat::exp(x) * cur -> est (se3quat.h:223-257, :104-110)
+// x: omega, upsilon; cur / est: q (x y z w), t.  false: est is not finite
+__device__ inline bool lm_se3_exp_mul(const double* x, const double* cur, double* est) {
+    const double o0 = x[0], o1 = x[1], o2 = x[2];
+    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
+    const double Om[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
+    double Om2[3][3], R[3][3], V[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Om2[r][c] = (Om[r][0] * Om[0][c] + Om[r][1] * Om[1][c]) + Om[r][2] * Om[2][c];
+    if (theta < 0.00001) {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) { R[r][c] = (((r == c) ? 1.0 : 0.0) + Om[r][c]) + Om2[r][c]; V[r][c] = R[r][c]; }
+    } else {
+        double sn, cs;
+        po_sincos(theta, sn, cs);
+        const double a = sn / theta, bq = (1.0 - cs) / (theta * theta), g = (theta - sn) / ((theta * theta) * theta);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const double e = (r == c) ? 1.0 : 0.0;
+                R[r][c] = (e + a * Om[r][c]) + bq * Om2[r][c];
+                V[r][c] = (e + bq * Om[r][c]) + g * Om2[r][c];
+            }
+    }
+    double t1[3];
+    for (int r = 0; r < 3; ++r) t1[r] = (V[r][0] * x[3] + V[r][1] * x[4]) + V[r][2] * x[5];
+    double q1[4];
+    po_mat_to_quat(R, q1);
+    po_normalize(q1);
+    // (q1, t1) * cur: t = t1 + q1 * t_cur, q = q1 q_cur, normalised
+    double r0, r1, r2;
+    po_rotate(q1, cur[4], cur[5], cur[6], r0, r1, r2);
+    est[4] = t1[0] + r0; est[5] = t1[1] + r1; est[6] = t1[2] + r2;
+    double q[4];
+    po_quat_mul(q1, cur, q);
+    po_normalize(q);
+    bool fin = true;
+    for (int i = 0; i < 4; ++i) { est[i] = q[i]; fin = fin && isfinite(q[i]); }
+    for (int i = 4; i < 7; ++i) fin = fin && isfinite(est[i]);
+    return fin;
 }
 
 // ---------------------------------------------------------------- departure (c): LDLT with diagonal pivoting on A = H + lambda I

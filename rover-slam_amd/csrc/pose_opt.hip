@@ -47,45 +47,9 @@ __device__ bool po_solve(PoseSerial& S) {
     return lm_ldlt_solve<6>(S.H, S.lambda, S.b, S.x);
 }
 
-// SE3Quat::exp(x) * cur -> est (se3quat.h:223-257, :104-110)
+// SE3Quat::exp(x) * cur -> est (lm_device.h)
 __device__ void po_update(PoseSerial& S) {
-    const double o0 = S.x[0], o1 = S.x[1], o2 = S.x[2];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
-    double Om2[3][3], R[3][3], V[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Om2[r][c] = (Om[r][0] * Om[0][c] + Om[r][1] * Om[1][c]) + Om[r][2] * Om[2][c];
-    if (theta < 0.00001) {
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) { R[r][c] = (((r == c) ? 1.0 : 0.0) + Om[r][c]) + Om2[r][c]; V[r][c] = R[r][c]; }
-    } else {
-        double sn, cs;
-        po_sincos(theta, sn, cs);
-        const double a = sn / theta, bq = (1.0 - cs) / (theta * theta), g = (theta - sn) / ((theta * theta) * theta);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                const double e = (r == c) ? 1.0 : 0.0;
-                R[r][c] = (e + a * Om[r][c]) + bq * Om2[r][c];
-                V[r][c] = (e + bq * Om[r][c]) + g * Om2[r][c];
-            }
-    }
-    double t1[3];
-    for (int r = 0; r < 3; ++r) t1[r] = (V[r][0] * S.x[3] + V[r][1] * S.x[4]) + V[r][2] * S.x[5];
-    double q1[4];
-    po_mat_to_quat(R, q1);
-    po_normalize(q1);
-    // (q1, t1) * cur: t = t1 + q1 * t_cur, q = q1 q_cur, normalised
-    const double* c = S.cur;
-    double r0, r1, r2;
-    po_rotate(q1, c[4], c[5], c[6], r0, r1, r2);
-    S.est[4] = t1[0] + r0; S.est[5] = t1[1] + r1; S.est[6] = t1[2] + r2;
-    double q[4];
-    po_quat_mul(q1, c, q);
-    po_normalize(q);
-    bool fin = true;
-    for (int i = 0; i < 4; ++i) { S.est[i] = q[i]; fin = fin && isfinite(q[i]); }
-    for (int i = 4; i < 7; ++i) fin = fin && isfinite(S.est[i]);
-    if (!fin) S.flags |= PO_FLAG_NONFINITE;
+    if (!lm_se3_exp_mul(S.x, S.cur, S.est)) S.flags |= PO_FLAG_NONFINITE;
 }
 
 // one trial of levenberg.cpp:102-124 up to the error pass: solve, update, publish the trial estimate

@@ -140,6 +140,11 @@ struct rfe_ctx {
     void* ws_tri = nullptr; size_t ws_tri_bytes = 0; // rfe_triangulate_neighbours*: per-slot results, claims, per-neighbour counts
     void* ws_bow = nullptr; size_t ws_bow_bytes = 0; // rfe_bow_transform*: per-feature word / node / weight the caller did not ask for
     void* ws_s3 = nullptr; size_t ws_s3_bytes = 0;   // rfe_sim3_ransac*: per-problem records, the front's rows, counts and hypotheses the caller did not ask for
+    // rfe_local_ba*: estimates, structure, per-edge terms, the dense reduced system (ws_lba); the Schur blocks' pair lists, sized from a
+    // count the first kernels leave, apart (ws_lba_pairs); a pinned block for the one small read per LM trial (h_lba)
+    void* ws_lba = nullptr; size_t ws_lba_bytes = 0;
+    void* ws_lba_pairs = nullptr; size_t ws_lba_pairs_bytes = 0;
+    void* h_lba = nullptr;
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -430,6 +435,31 @@ void launch_optimize_sim3(hipStream_t s, const rfe_optimize_sim3_params* params,
                           const uint8_t* valid, const float* kpts1, const int32_t* octave1, const int32_t* idx2, const float* kpts2,
                           const int32_t* octave2, int B, int N, int N2, double* s12, float* s12_f32, uint8_t* keep, double* chi2, double* trace,
                           int32_t* stats);
+
+// local_ba.hip: Optimizer::LocalBundleAdjustment, one problem per call, the LM loop on the host (api_local_ba.hip).
+// LbaDev: the caller's inputs, the shape, the kernel constants and ws_lba's carving.  ctl_d / ctl_i are one block the host reads with a
+// single copy: doubles LBA_D_*, then int32 LBA_I_*
+enum { LBA_D_CHI = 0, LBA_D_SCALE = 1, LBA_D_MAXDIAG = 2, LBA_CTL_D = 8 };
+enum { LBA_I_STATUS = 0, LBA_I_FLAGS = 1, LBA_I_ERASED = 2, LBA_I_SOLVED = 3, LBA_I_NFREE = 4, LBA_I_NPAIRS = 5, LBA_CTL_I = 16 };
+enum { LBA_BAD_RANGE = 1, LBA_BAD_ORDER = 2, LBA_BAD_KF = 4 };
+constexpr int LBA_LIN = 54;                          // doubles per edge of lba_linearise_kernel
+struct LbaDev {
+    const float *kf_pose, *kf_cam, *kf_sigma2, *kpts, *uright, *xw;
+    const int32_t *kf_nlevels, *kf_feat_off, *octave, *edge_point, *edge_kf, *edge_feat;
+    int P, K, L, E, Nf, NB;                          // NB = P (P + 1) / 2 Schur blocks
+    double delta_mono, dsqr_mono, delta_stereo, dsqr_stereo, th2_mono, th2_stereo;
+    double* ctl_d; int32_t* ctl_i;
+    double *pose[2], *pt[2];                         // [K, 7] and [L, 3], the estimate and the trial
+    int32_t *pt_start, *pose_start, *pose_cnt, *pose_list, *blk_start, *blk_cnt, *pairs;
+    double *lin, *chi2, *rho0, *Hll, *bl, *Dinv, *db, *xl, *Hpp, *bp, *bs, *xp, *BDinv, *Bdb, *S, *sterm;
+};
+void lba_launch_validate(hipStream_t s, const LbaDev& d);
+void lba_launch_structure(hipStream_t s, const LbaDev& d);
+void lba_launch_pairs(hipStream_t s, const LbaDev& d);
+void lba_launch_errors(hipStream_t s, const LbaDev& d, int cur, bool linearise, bool max_diagonal);
+void lba_launch_trial(hipStream_t s, const LbaDev& d, int cur, double lambda);
+void lba_launch_finish(hipStream_t s, const LbaDev& d, int cur, double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* erase,
+                       double* chi2);
 
 // sim3_solver.hip: Sim3Solver's RANSAC with every hypothesis at once.  params is a HOST array: the front takes it by value,
 // S3_FRONT_CHUNK problems per launch, and leaves prob [B]; front [B, 12, N], counts [B, H] and hyps [B, H, 32] are workspace (or the
