@@ -832,6 +832,56 @@ int rfe_local_ba(rfe_ctx* ctx, rfe_local_ba_params params, const float* kf_pose,
                  const float* xw, const int32_t* edge_point, const int32_t* edge_kf, const int32_t* edge_feat, int P, int F, int L, int E, int Nf,
                  double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* erase, double* chi2, double* trace, int32_t* stats);
 
+/* ---- Optimizer::OptimizeEssentialGraph on the device: the Sim3 pose graph that corrects the map after a loop ----
+ * src/Optimizer.cc:4509-4840 over g2o's BlockSolver_7_3 and OptimizationAlgorithmLevenberg: one VertexSim3Expmap per keyframe, one
+ * EdgeSim3 (identity information, no robust kernel, numeric Jacobians with delta 1e-9) per edge, optimize(iterations), then the poses
+ * and the map points' correction.  One graph per call.  Double precision throughout; every sum in one fixed order, so the outputs equal
+ * the restatement tests/essential_graph_ref.py bit for bit (6m states the arithmetic and its departures, among them a dense unpivoted
+ * LDLT that the kernels run over 28 x 28 tiles, skipping the tiles the pattern can never fill).
+ *   s_est [N,8] qx qy qz qw tx ty tz s: vScw, every keyframe's estimate (the CorrectedSim3 entry, or the SE3 pose at scale 1)
+ *   s_meas [N,8]: the NonCorrectedSim3 entry where there is one, a copy of s_est otherwise
+ *   fixed [N]: non-zero for mnId == GetInitKFid(); zero fixed vertices is accepted and runs
+ *   edge_i / edge_j / edge_from_est [E]: vertex 0 and vertex 1 of every edge in ascending (i, j), duplicates kept, i != j; the
+ *   measurement is Sji = Sjw Swi from s_est when edge_from_est is non-zero (loop connections), from s_meas otherwise
+ *   xw [L,3] float and point_ref [L]: the map points and the keyframe each is corrected through, -1 for a point that is copied
+ * Outputs: siw [N,8] the corrected Sim3; tiw_f32 [N,7] (float) q and (float) t / (float) s, what SetPose takes; swi [N,8] the inverses;
+ *   xw_out [L,3] = Swr'.map(Srw.map(X)) in double, Srw the INPUT s_est of the reference keyframe, cast to float; chi2 [E] at the final
+ *   estimate (the closing computeActiveErrors); trace [iterations,4] per LM iteration run: trials, the lambda it left, currentChi, 0;
+ *   stats [8]: 0 LM iterations, 1 trials, 2 rejected trials, 3 failed solves, 4 flags, 5 free vertices, 6 tiles the factorisation
+ *   processes, 7 tiles of the dense lower triangle.  Flags: 1 ended on a rejected trial, 2 a solve failed (a zero or non-finite pivot,
+ *   a non-finite entry of L or of the solution), 4 a trial or the final estimate was not finite, 16 no LM iteration ran.
+ * BOTH forms are synchronous, like rfe_local_ba: the LM loop runs on the host, plain launches on the ctx stream and one small pinned
+ * read per linearisation and per trial.  The _dev form validates the edge table and point_ref in its first kernels and reads the
+ * verdict before anything indexes by them.  Both return the number of LM iterations run (>= 0).
+ * tiw_f32, swi, chi2, trace may be NULL.
+ * Refused (RFE_ERR_INVALID): N outside 1..RFE_EG_MAX_KF, E outside 0..RFE_EG_MAX_EDGES, L outside 0..RFE_EG_MAX_POINTS, iterations
+ *   outside 0..RFE_EG_MAX_ITERATIONS, max_trials < 0, a non-finite user_lambda_init, a NULL required pointer, an edge index out of
+ *   range, an edge from a keyframe to itself, edges not ascending, a point_ref outside -1..N-1.  Nothing is written then.
+ * Out of scope: OptimizeEssentialGraph4DoF, the merge overload, the inertial edges. */
+#define RFE_EG_MAX_KF 1024
+#define RFE_EG_MAX_EDGES 16384
+#define RFE_EG_MAX_POINTS (1 << 20)
+#define RFE_EG_MAX_ITERATIONS 64
+#define RFE_EG_FLAG_ENDED_REJECTED 1
+#define RFE_EG_FLAG_SOLVE_FAILED 2
+#define RFE_EG_FLAG_NONFINITE 4
+#define RFE_EG_FLAG_NO_ITERATION 16
+typedef struct rfe_essential_graph_params {
+    int32_t iterations;          /* optimizer.optimize(20); 0 runs none */
+    int32_t max_trials;          /* 0 = g2o's 10 */
+    double user_lambda_init;     /* setUserLambdaInit(1e-16); <= 0: g2o's 1e-5 max |diagonal| */
+    int32_t fix_scale;           /* bFixScale */
+    int32_t reserved;
+} rfe_essential_graph_params;
+int rfe_essential_graph_dev(rfe_ctx* ctx, rfe_essential_graph_params params, const double* s_est_dev, const double* s_meas_dev,
+                            const uint8_t* fixed_dev, const int32_t* edge_i_dev, const int32_t* edge_j_dev, const uint8_t* edge_from_est_dev,
+                            const float* xw_dev, const int32_t* point_ref_dev, int N, int E, int L, double* siw_dev, float* tiw_f32_dev,
+                            double* swi_dev, float* xw_out_dev, double* chi2_dev, double* trace_dev, int32_t* stats_dev);
+int rfe_essential_graph(rfe_ctx* ctx, rfe_essential_graph_params params, const double* s_est, const double* s_meas, const uint8_t* fixed,
+                        const int32_t* edge_i, const int32_t* edge_j, const uint8_t* edge_from_est, const float* xw, const int32_t* point_ref,
+                        int N, int E, int L, double* siw, float* tiw_f32, double* swi, float* xw_out, double* chi2, double* trace,
+                        int32_t* stats);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates

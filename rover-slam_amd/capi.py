@@ -26,7 +26,7 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -337,6 +337,23 @@ _lba = [C.c_void_p, LocalBaParams, _fp, _fp, _ip, _fp, _ip, _fp, _ip, _fp, _fp, 
         _vp, _fp, _vp, _fp, _u8p, _vp, _vp, _ip]
 lib.rfe_local_ba.argtypes = _lba
 lib.rfe_local_ba_dev.argtypes = _lba
+
+
+class EssentialGraphParams(C.Structure):
+    """include/rover_fe.h: rfe_essential_graph_params, passed BY VALUE -- the LM schedule of one OptimizeEssentialGraph and bFixScale."""
+    _fields_ = [("iterations", C.c_int32), ("max_trials", C.c_int32), ("user_lambda_init", C.c_double), ("fix_scale", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def essential_graph_params(iterations=20, max_trials=0, user_lambda_init=1e-16, fix_scale=False):
+    return EssentialGraphParams(int(iterations), int(max_trials), float(user_lambda_init), 1 if fix_scale else 0, 0)
+
+
+ESSENTIAL_GRAPH_OUTPUTS = ("tiw_f32", "swi", "chi2", "trace")
+EG_MAX_KF, EG_MAX_EDGES, EG_MAX_POINTS, EG_MAX_ITERATIONS, EG_TILE_V = 1024, 16384, 1 << 20, 64, 4
+_eg = [C.c_void_p, EssentialGraphParams, _vp, _vp, _u8p, _ip, _ip, _u8p, _fp, _ip, C.c_int, C.c_int, C.c_int, _vp, _fp, _vp, _fp, _vp, _vp, _ip]
+lib.rfe_essential_graph.argtypes = _eg
+lib.rfe_essential_graph_dev.argtypes = _eg
 
 
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
@@ -1305,6 +1322,38 @@ class Context:
         return self._chk(lib.rfe_local_ba_dev(self.h, params, a(kf_pose), a(kf_cam), a(kf_nlevels), a(kf_sigma2), a(kf_feat_off), a(kpts), a(octave),
                                               a(uright), a(xw), a(edge_point), a(edge_kf), a(edge_feat), int(P), int(F), int(L), int(E), int(Nf),
                                               a(pose), a(pose_f32), a(point), a(point_f32), a(erase), a(chi2), a(trace), a(stats)))
+
+    def essential_graph(self, params, s_est, s_meas, fixed, edge_i, edge_j, edge_from_est, xw=None, point_ref=None,
+                        outputs=ESSENTIAL_GRAPH_OUTPUTS, shape=None):
+        """Optimizer::OptimizeEssentialGraph for one pose graph (rfe_essential_graph, host arrays; DESIGN.md 6m).  params:
+        essential_graph_params(); s_est / s_meas [N,8] float64 (q xyzw, t, s), fixed [N]; edge_i / edge_j / edge_from_est [E] in ascending
+        (i, j); xw [L,3] float32 with point_ref [L].  shape: (N, E, L) when the arrays are longer than the problem (what lies behind is
+        not read).  Returns a dict: siw [N,8], xw_out [L,3], stats [8], ret (LM iterations run), and tiw_f32 [N,7] / swi [N,8] / chi2 [E] /
+        trace [iterations,4] as asked."""
+        se, sm, fx = _opt(s_est, np.float64), _opt(s_meas, np.float64), _opt(fixed, np.uint8)
+        ei, ej, es = _opt(edge_i, np.int32), _opt(edge_j, np.int32), _opt(edge_from_est, np.uint8)
+        x, pr = _opt(xw, np.float32), _opt(point_ref, np.int32)
+        N, E, L = (len(fx), len(ei), 0 if pr is None else len(pr)) if shape is None else shape
+        its = max(int(params.iterations), 0)
+        o = {"siw": np.zeros((max(N, 1), 8), np.float64), "tiw_f32": np.zeros((max(N, 1), 7), np.float32),
+             "swi": np.zeros((max(N, 1), 8), np.float64), "xw_out": np.zeros((max(L, 1), 3), np.float32),
+             "chi2": np.zeros((max(E, 1),), np.float64), "trace": np.zeros((max(its, 1), 4), np.float64), "stats": np.zeros((8,), np.int32)}
+        ad = [o[n].ctypes.data if (n not in ESSENTIAL_GRAPH_OUTPUTS or n in outputs) else None for n in o]
+        ret = self._chk(lib.rfe_essential_graph(self.h, params, _addr(se), _addr(sm), _addr(fx), _addr(ei), _addr(ej), _addr(es), _addr(x),
+                                                _addr(pr), int(N), int(E), int(L), *ad))
+        n = {"siw": N, "tiw_f32": N, "swi": N, "xw_out": L, "chi2": E, "trace": its, "stats": 8}
+        r = {key: a[:n[key]] for key, a in o.items() if key not in ESSENTIAL_GRAPH_OUTPUTS or key in outputs}
+        r["ret"] = ret
+        return r
+
+    def essential_graph_dev(self, params, N, E, L, s_est, s_meas, fixed, edge_i, edge_j, edge_from_est, xw, point_ref, siw, xw_out, stats,
+                            tiw_f32=None, swi=None, chi2=None, trace=None):
+        """rfe_essential_graph_dev: every array a DevBuf (or a raw device address / torch tensor).  SYNCHRONOUS: returns the number of LM
+        iterations run when the optimisation has finished."""
+        a = _dev
+        return self._chk(lib.rfe_essential_graph_dev(self.h, params, a(s_est), a(s_meas), a(fixed), a(edge_i), a(edge_j), a(edge_from_est),
+                                                     a(xw), a(point_ref), int(N), int(E), int(L), a(siw), a(tiw_f32), a(swi), a(xw_out),
+                                                     a(chi2), a(trace), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

@@ -1,7 +1,9 @@
-// lm_device.h -- device functions the Levenberg-Marquardt kernels share (pose_opt.hip; optimize_sim3.hip, 6k; local_ba.hip, 6l):
-// the explicit sin / cos of departure (b), Eigen's quaternion arithmetic, SE3Quat's exp and product, the pivoted LDLT of departure (c) on a D x D system and the
-// stride-halving reduction of departure (a).  Everything is double, one rounding per operation (-ffp-contract=off); the numpy restatements
-// tests/pose_opt_ref.py and tests/optimize_sim3_ref.py state the same operations in the same order.
+// lm_device.h -- device functions the Levenberg-Marquardt kernels share (pose_opt.hip; optimize_sim3.hip, 6k; local_ba.hip, 6l;
+// essential_graph.hip, 6m): the explicit sin / cos of departure (b), exp, log and acos after fdlibm, Eigen's quaternion arithmetic, SE3Quat's
+// exp and product, Sim3's exp, product, inverse, map and log with its 3 x 3 elimination, the pivoted LDLT of departure (c) on a D x D
+// system and the stride-halving reduction of departure (a).  Everything is double, one rounding per operation (-ffp-contract=off); the
+// numpy restatements tests/pose_opt_ref.py, tests/optimize_sim3_ref.py and tests/essential_graph_ref.py state the same operations in the
+// same order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -148,6 +150,244 @@ __device__ inline bool lm_se3_exp_mul(const double* x, const double* cur, double
     for (int i = 0; i < 4; ++i) { est[i] = q[i]; fin = fin && isfinite(q[i]); }
     for (int i = 4; i < 7; ++i) fin = fin && isfinite(est[i]);
     return fin;
+}
+
+// ---------------------------------------------------------------- Sim3 (q x y z w, t, s): 6k's exp, product with an estimate and inverse
+// Sim3(update) (sim3.h:70-142): u = omega, upsilon, sigma -> q (not normalised), t, s
+__device__ inline void lm_sim3_exp(const double (&u)[7], double* q, double* t, double& s) {
+    const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
+    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
+    const double Om[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
+    double Om2[3][3], R[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Om2[r][c] = (Om[r][0] * Om[0][c] + Om[r][1] * Om[1][c]) + Om[r][2] * Om[2][c];
+    s = lm_exp(sigma);
+    const double eps = 0.00001;
+    double A, B, C;
+    double sn = 0.0, cs = 1.0;
+    const bool small = theta < eps;
+    if (!small) po_sincos(theta, sn, cs);
+    if (small) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) R[r][c] = (((r == c) ? 1.0 : 0.0) + Om[r][c]) + Om2[r][c];
+    } else {
+        const double a = sn / theta, bq = (1.0 - cs) / (theta * theta);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) R[r][c] = (((r == c) ? 1.0 : 0.0) + a * Om[r][c]) + bq * Om2[r][c];
+    }
+    if (fabs(sigma) < eps) {
+        C = 1.0;
+        if (small) {
+            A = 1. / 2.; B = 1. / 6.;
+        } else {
+            const double theta2 = theta * theta;
+            A = (1.0 - cs) / theta2;
+            B = (theta - sn) / (theta2 * theta);
+        }
+    } else {
+        C = (s - 1.0) / sigma;
+        if (small) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1.0) * s + 1.0) / sigma2;
+            B = (((0.5 * sigma2 - sigma) + 1.0) * s) / (sigma2 * sigma);
+        } else {
+            const double a = s * sn, b = s * cs, theta2 = theta * theta, sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1.0 - b) * theta) / (theta * c);
+            B = ((C - ((b - 1.0) * sigma + a * theta) / c) * 1.) / theta2;
+        }
+    }
+    po_mat_to_quat(R, q);
+    double W[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W[r][c] = (A * Om[r][c] + B * Om2[r][c]) + C * ((r == c) ? 1.0 : 0.0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) t[r] = (W[r][0] * u[3] + W[r][1] * u[4]) + W[r][2] * u[5];
+}
+
+// Sim3(u) * base (sim3.h:266-272): r = r1 r2, t = s1 (r1 * t2) + t1, s = s1 s2; nothing is normalised
+__device__ inline void lm_sim3_oplus(const double (&u)[7], const double* base, double* out) {
+    double q1[4], t1[3], s1;
+    lm_sim3_exp(u, q1, t1, s1);
+    po_quat_mul(q1, base, out);
+    double r0, r1, r2;
+    po_rotate(q1, base[4], base[5], base[6], r0, r1, r2);
+    out[4] = s1 * r0 + t1[0]; out[5] = s1 * r1 + t1[1]; out[6] = s1 * r2 + t1[2];
+    out[7] = s1 * base[7];
+}
+
+// inverse (sim3.h:233-236): (conj r, conj r * ((-1 / s) t), 1 / s)
+__device__ inline void lm_sim3_inverse(const double* in, double* out) {
+    out[0] = -in[0]; out[1] = -in[1]; out[2] = -in[2]; out[3] = in[3];
+    const double c = -1. / in[7];
+    po_rotate(out, c * in[4], c * in[5], c * in[6], out[4], out[5], out[6]);
+    out[7] = 1. / in[7];
+}
+
+// A * B (sim3.h:266-272): r = r1 r2, t = s1 (r1 * t2) + t1, s = s1 s2; nothing is normalised
+__device__ inline void lm_sim3_mul(const double* A, const double* B, double* out) {
+    po_quat_mul(A, B, out);
+    double r0, r1, r2;
+    po_rotate(A, B[4], B[5], B[6], r0, r1, r2);
+    out[4] = A[7] * r0 + A[4]; out[5] = A[7] * r1 + A[5]; out[6] = A[7] * r2 + A[6];
+    out[7] = A[7] * B[7];
+}
+// S.map(X) = s (r * X) + t
+__device__ inline void lm_sim3_map(const double* S, double X0, double X1, double X2, double& o0, double& o1, double& o2) {
+    double r0, r1, r2;
+    po_rotate(S, X0, X1, X2, r0, r1, r2);
+    o0 = S[7] * r0 + S[4]; o1 = S[7] * r1 + S[5]; o2 = S[7] * r2 + S[6];
+}
+
+// ---------------------------------------------------------------- log and acos (6m's departure (e)): fdlibm's e_log and e_acos without fma
+// x = 2^k (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2), split on the high word as fdlibm does; s = f / (2 + f), the two interleaved polynomials,
+// the k == 0 and k != 0 sums, none of fdlibm's short cuts.  x < 0 and NaN give NaN, 0 gives -inf, inf gives inf
+__device__ inline double lm_log(double x) {
+    if (x != x || x < 0) return __longlong_as_double(0x7ff8000000000000LL);
+    if (x == 0) return -HUGE_VAL;
+    if (x == HUGE_VAL) return x;
+    long long sub = 0;
+    if (x < 2.2250738585072014e-308) { x = x * 18014398509481984.0; sub = 54; }
+    const long long bits = __double_as_longlong(x);
+    long long k = (bits >> 52) - 1023 - sub;
+    const long long m = bits & 0xFFFFFFFFFFFFFLL;
+    const long long i = ((m >> 32) + 0x95F64) & 0x100000;
+    k += i >> 20;
+    const double f = __longlong_as_double(m | ((0x3FF00000LL ^ i) << 32)) - 1.0;
+    const double dk = (double)k;
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    const double w = z * z;
+    const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
+    const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
+    const double R = t2 + t1;
+    const double hfsq = (0.5 * f) * f;
+    if (k == 0) return f - (hfsq - s * (hfsq + R));
+    return dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
+}
+__device__ inline double lm_acos_r(double z) {
+    const double p = z * (1.66666666666666657415e-01 + z * (-3.25565818622400915405e-01 + z * (2.01212532134862925881e-01 +
+                     z * (-4.00555345006794114027e-02 + z * (7.91534994289814532176e-04 + z * 3.47933107596021167570e-05)))));
+    const double q = 1.0 + z * (-2.40339491173441421878e+00 + z * (2.02094576023350569471e+00 + z * (-6.88283971605453293030e-01 +
+                     z * 7.70381505559019352791e-02)));
+    return p / q;
+}
+// |x| < 0.5 through x^2; x < -0.5 and x > 0.5 through sqrt((1 -+ x) / 2), the latter with the root's low word cleared.  |x| > 1 and NaN
+// give NaN, acos(1) == 0
+__device__ inline double lm_acos(double x) {
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17, pi = 3.14159265358979311600e+00;
+    if (!(fabs(x) <= 1.0)) return __longlong_as_double(0x7ff8000000000000LL);
+    if (x == 1.0) return 0.0;
+    if (x == -1.0) return pi + 2.0 * pio2_lo;
+    if (fabs(x) < 0.5) {
+        if (fabs(x) < 6.938893903907228e-18) return pio2_hi + pio2_lo;
+        const double r = lm_acos_r(x * x);
+        return pio2_hi - (x - (pio2_lo - x * r));
+    }
+    if (x < 0) {
+        const double z = (1.0 + x) * 0.5;
+        const double s = sqrt(z);
+        const double w = lm_acos_r(z) * s - pio2_lo;
+        return pi - 2.0 * (s + w);
+    }
+    const double z = (1.0 - x) * 0.5;
+    const double s = sqrt(z);
+    const double df = __longlong_as_double((__double_as_longlong(s) >> 32) << 32);
+    const double c = (z - df * df) / (s + df);
+    const double w = lm_acos_r(z) * s + c;
+    return 2.0 * (df + w);
+}
+
+// ---------------------------------------------------------------- 6m's departure (f): W x = t, 3 x 3, partial pivoting
+// column 0: the row with the largest |W[r][0]| (the first maximum) comes first, rows 1 and 2 lose l = W[r][0] / W[0][0] times row 0;
+// column 1 likewise over rows 1, 2; then x2, x1, x0.  The swaps compare and exchange named rows, so every index is a constant
+__device__ inline void lm_lu3_swap(double (&W)[3][3], double (&t)[3], int a, int b) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { const double u = W[a][c]; W[a][c] = W[b][c]; W[b][c] = u; }
+    const double u = t[a]; t[a] = t[b]; t[b] = u;
+}
+__device__ inline void lm_lu3_solve(double (&W)[3][3], double (&t)[3], double (&x)[3]) {
+    const double a0 = fabs(W[0][0]), a1 = fabs(W[1][0]), a2 = fabs(W[2][0]);
+    const bool p1 = a1 > a0;
+    const bool p2 = a2 > (p1 ? a1 : a0);
+    if (p2) lm_lu3_swap(W, t, 0, 2);
+    else if (p1) lm_lu3_swap(W, t, 0, 1);
+#pragma unroll
+    for (int r = 1; r < 3; ++r) {
+        const double l = W[r][0] / W[0][0];
+        W[r][1] = W[r][1] - l * W[0][1];
+        W[r][2] = W[r][2] - l * W[0][2];
+        t[r] = t[r] - l * t[0];
+    }
+    if (fabs(W[2][1]) > fabs(W[1][1])) lm_lu3_swap(W, t, 1, 2);
+    const double l = W[2][1] / W[1][1];
+    W[2][2] = W[2][2] - l * W[1][2];
+    t[2] = t[2] - l * t[1];
+    x[2] = t[2] / W[2][2];
+    x[1] = (t[1] - W[1][2] * x[2]) / W[1][1];
+    x[0] = ((t[0] - W[0][1] * x[1]) - W[0][2] * x[2]) / W[0][0];
+}
+
+// ---------------------------------------------------------------- Sim3::log (sim3.h:148-230): S -> omega, upsilon, sigma
+__device__ inline void lm_sim3_log(const double* S, double* res) {
+    const double s = S[7];
+    const double sigma = lm_log(s);
+    const double qx = S[0], qy = S[1], qz = S[2], qw = S[3];
+    const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
+    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+    const double R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy, R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx,
+                 R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy);
+    const double d = 0.5 * (((R00 + R11) + R22) - 1);
+    const double dR0 = R21 - R12, dR1 = R02 - R20, dR2 = R10 - R01;
+    const double eps = 0.00001;
+    const bool near = d > 1 - eps;
+    double A, B, C, k;
+    double theta = 0.0, theta2 = 0.0, sn = 0.0, cs = 1.0;
+    if (near) {
+        k = 0.5;
+    } else {
+        theta = lm_acos(d);
+        theta2 = theta * theta;
+        k = theta / (2 * sqrt(1 - d * d));
+        po_sincos(theta, sn, cs);
+    }
+    const double o0 = k * dR0, o1 = k * dR1, o2 = k * dR2;
+    if (fabs(sigma) < eps) {
+        C = 1.0;
+        if (near) { A = 1. / 2.; B = 1. / 6.; }
+        else { A = (1 - cs) / theta2; B = (theta - sn) / (theta2 * theta); }
+    } else {
+        C = (s - 1) / sigma;
+        if (near) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * s + 1) / sigma2;
+            B = (((0.5 * sigma2 - sigma) + 1) * s) / (sigma2 * sigma);
+        } else {
+            const double a = s * sn, b = s * cs;
+            const double c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = ((C - ((b - 1) * sigma + a * theta) / c) * 1.) / theta2;
+        }
+    }
+    const double Om[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
+    double W[3][3], t[3] = {S[4], S[5], S[6]}, x[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double om2 = (Om[r][0] * Om[0][c] + Om[r][1] * Om[1][c]) + Om[r][2] * Om[2][c];
+            W[r][c] = (A * Om[r][c] + B * om2) + C * ((r == c) ? 1.0 : 0.0);
+        }
+    lm_lu3_solve(W, t, x);
+    res[0] = o0; res[1] = o1; res[2] = o2; res[3] = x[0]; res[4] = x[1]; res[5] = x[2]; res[6] = sigma;
 }
 
 // ---------------------------------------------------------------- departure (c): LDLT with diagonal pivoting on A = H + lambda I

@@ -34,89 +34,10 @@ struct OsSerial {
     int iters, trials, rejected, flags, ended_rejected;
 };
 
-// Sim3(update) (sim3.h:70-142): u = omega, upsilon, sigma -> q (not normalised), t, s
-__device__ void os_exp(const double (&u)[7], double* q, double* t, double& s) {
-    const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
-    const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-    const double Om[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
-    double Om2[3][3], R[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Om2[r][c] = (Om[r][0] * Om[0][c] + Om[r][1] * Om[1][c]) + Om[r][2] * Om[2][c];
-    s = lm_exp(sigma);
-    const double eps = 0.00001;
-    double A, B, C;
-    double sn = 0.0, cs = 1.0;
-    const bool small = theta < eps;
-    if (!small) po_sincos(theta, sn, cs);
-    if (small) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) R[r][c] = (((r == c) ? 1.0 : 0.0) + Om[r][c]) + Om2[r][c];
-    } else {
-        const double a = sn / theta, bq = (1.0 - cs) / (theta * theta);
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) R[r][c] = (((r == c) ? 1.0 : 0.0) + a * Om[r][c]) + bq * Om2[r][c];
-    }
-    if (fabs(sigma) < eps) {
-        C = 1.0;
-        if (small) {
-            A = 1. / 2.; B = 1. / 6.;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1.0 - cs) / theta2;
-            B = (theta - sn) / (theta2 * theta);
-        }
-    } else {
-        C = (s - 1.0) / sigma;
-        if (small) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1.0) * s + 1.0) / sigma2;
-            B = (((0.5 * sigma2 - sigma) + 1.0) * s) / (sigma2 * sigma);
-        } else {
-            const double a = s * sn, b = s * cs, theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1.0 - b) * theta) / (theta * c);
-            B = ((C - ((b - 1.0) * sigma + a * theta) / c) * 1.) / theta2;
-        }
-    }
-    po_mat_to_quat(R, q);
-    double W[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) W[r][c] = (A * Om[r][c] + B * Om2[r][c]) + C * ((r == c) ? 1.0 : 0.0);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) t[r] = (W[r][0] * u[3] + W[r][1] * u[4]) + W[r][2] * u[5];
-}
-
-// Sim3(u) * base (sim3.h:266-272): r = r1 r2, t = s1 (r1 * t2) + t1, s = s1 s2; nothing is normalised
-__device__ void os_oplus(const double (&u)[7], const double* base, double* out) {
-    double q1[4], t1[3], s1;
-    os_exp(u, q1, t1, s1);
-    po_quat_mul(q1, base, out);
-    double r0, r1, r2;
-    po_rotate(q1, base[4], base[5], base[6], r0, r1, r2);
-    out[4] = s1 * r0 + t1[0]; out[5] = s1 * r1 + t1[1]; out[6] = s1 * r2 + t1[2];
-    out[7] = s1 * base[7];
-}
-
-// inverse (sim3.h:233-236): (conj r, conj r * ((-1 / s) t), 1 / s)
-__device__ void os_inverse(const double* in, double* out) {
-    out[0] = -in[0]; out[1] = -in[1]; out[2] = -in[2]; out[3] = in[3];
-    const double c = -1. / in[7];
-    po_rotate(out, c * in[4], c * in[5], c * in[6], out[4], out[5], out[6]);
-    out[7] = 1. / in[7];
-}
-
 // oplusImpl on the solver's x: update[6] = 0 in place under fix_scale, then Sim3(x) * cur -> est
 __device__ void os_update(OsSerial& S) {
     if (S.fix_scale) S.x[6] = 0.0;
-    os_oplus(S.x, S.cur, S.est);
+    lm_sim3_oplus(S.x, S.cur, S.est);
     bool fin = true;
     for (int i = 0; i < 8; ++i) fin = fin && isfinite(S.est[i]);
     if (!fin) S.flags |= OS_FLAG_NONFINITE;
@@ -377,9 +298,9 @@ __global__ __launch_bounds__(LM_LANES) void optimize_sim3_kernel(OsChunk PC, OsP
 #pragma unroll
                     for (int j = 0; j < 7; ++j) u[j] = (j == d) ? step : 0.0;
                     if (S.fix_scale) u[6] = 0.0;
-                    os_oplus(u, est, out);
+                    lm_sim3_oplus(u, est, out);
                 }
-                os_inverse(out, out + 8);
+                lm_sim3_inverse(out, out + 8);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) E[lane][i] = out[i];
             }
@@ -432,7 +353,7 @@ __global__ __launch_bounds__(LM_LANES) void optimize_sim3_kernel(OsChunk PC, OsP
             if (lane == 0) {
                 double out[16];
                 for (int i = 0; i < 8; ++i) out[i] = S.cur[i];
-                os_inverse(out, out + 8);
+                lm_sim3_inverse(out, out + 8);
                 for (int i = 0; i < 16; ++i) E[0][i] = out[i];
             }
             __syncthreads();

@@ -145,6 +145,11 @@ struct rfe_ctx {
     void* ws_lba = nullptr; size_t ws_lba_bytes = 0;
     void* ws_lba_pairs = nullptr; size_t ws_lba_pairs_bytes = 0;
     void* h_lba = nullptr;
+    // rfe_essential_graph*: estimates, structure, per-edge terms and the solve's vectors (ws_eg); the dense 7 Nf x 7 Nf matrix, sized from
+    // the number of free vertices the front leaves, apart (ws_eg_mat); the pinned block of the small reads (h_eg)
+    void* ws_eg = nullptr; size_t ws_eg_bytes = 0;
+    void* ws_eg_mat = nullptr; size_t ws_eg_mat_bytes = 0;
+    void* h_eg = nullptr;
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -460,6 +465,35 @@ void lba_launch_errors(hipStream_t s, const LbaDev& d, int cur, bool linearise, 
 void lba_launch_trial(hipStream_t s, const LbaDev& d, int cur, double lambda);
 void lba_launch_finish(hipStream_t s, const LbaDev& d, int cur, double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* erase,
                        double* chi2);
+
+// essential_graph.hip: Optimizer::OptimizeEssentialGraph, the Sim3 pose graph, the LM loop on the host (api_essential_graph.hip; DESIGN.md
+// 6m).  EgDev: the caller's inputs, the shape and ws_eg's carving.  ctl_d / ctl_i are one block the host reads with a single copy.  The
+// factorisation works on square tiles of EG_TILE rows (EG_TILE_V vertices); NT tiles a side, NP = NT EG_TILE padded rows
+constexpr int EG_TILE_V = 4, EG_TILE = 28, EG_CON = 119, EG_JAC = 105;
+enum { EG_D_CHI = 0, EG_D_SCALE = 1, EG_D_MAXDIAG = 2, EG_CTL_D = 8 };
+enum { EG_I_STATUS = 0, EG_I_FLAGS = 1, EG_I_FAIL = 2, EG_I_NFREE = 3, EG_I_TILES = 4, EG_CTL_I = 16 };
+enum { EG_BAD_RANGE = 1, EG_BAD_ORDER = 2, EG_BAD_REF = 4 };
+struct EgDev {
+    const double *s_est, *s_meas;
+    const uint8_t *fixed, *edge_src;
+    const int32_t *edge_i, *edge_j, *point_ref;
+    const float* xw;
+    int N, E, L, fix_scale, Nf, NT, NP;              // Nf, NT, NP: known after the front
+    double* ctl_d; int32_t* ctl_i;
+    double* est[2];                                  // [N, 8], the estimate and the trial
+    double *meas, *pert;                             // [E, 8] Sji; [14, 8] Sim3(+-delta e_d)
+    int32_t *free_index, *free_list, *inc_start, *inc_list;   // inc_list: edge * 2 + side, ascending inside a vertex
+    int32_t *col_start, *col_tiles, *row_start, *row_tiles;   // per tile column: its non-zero tiles, the diagonal first; per tile row likewise
+    uint8_t* fill;                                   // [NT, NT]
+    double *jac, *con, *chi2;                        // [EG_JAC, E] e | A | B; [EG_CON, E] Hii | bi | Hjj | bj | Hij; [E]
+    double *b, *x, *z, *y, *xs, *dvec, *sterm;       // [NP] each
+    double* mat;                                     // [NP, NP]: H in the upper triangle with the diagonal, L strictly below
+};
+void eg_launch_front(hipStream_t s, const EgDev& d);
+void eg_launch_structure(hipStream_t s, const EgDev& d);
+void eg_launch_errors(hipStream_t s, const EgDev& d, int cur, bool linearise, bool max_diagonal);
+void eg_launch_trial(hipStream_t s, const EgDev& d, int cur, double lambda, const int32_t* col_start, const int32_t* row_start);
+void eg_launch_finish(hipStream_t s, const EgDev& d, int cur, double* siw, float* tiw_f32, double* swi, float* xw_out, double* chi2);
 
 // sim3_solver.hip: Sim3Solver's RANSAC with every hypothesis at once.  params is a HOST array: the front takes it by value,
 // S3_FRONT_CHUNK problems per launch, and leaves prob [B]; front [B, 12, N], counts [B, H] and hyps [B, H, 32] are workspace (or the
