@@ -882,6 +882,69 @@ int rfe_essential_graph(rfe_ctx* ctx, rfe_essential_graph_params params, const d
                         int N, int E, int L, double* siw, float* tiw_f32, double* swi, float* xw_out, double* chi2, double* trace,
                         int32_t* stats);
 
+/* ---- Optimizer::GlobalBundleAdjustemnt on the device: the full bundle adjustment behind a loop closure ----
+ * src/Optimizer.cc:2832-3220 (BundleAdjustment, reached from GlobalBundleAdjustemnt and from the monocular initialisation) over g2o's
+ * BlockSolver_6_3 and OptimizationAlgorithmLevenberg: one SE3 vertex per keyframe, one marginalised 3-DoF vertex per map point, one mono
+ * or stereo edge per observation, ONE optimize(iterations); no classification.  One problem per call.  It is rfe_local_ba's arithmetic up
+ * to the reduced system (6l) behind a structure front whose work scales with the Schur pairs, and rfe_essential_graph's tiled LDLT (6m)
+ * on 24 x 24 tiles over the fill of the covisibility pattern, so it runs past 64 free keyframes.  Double precision throughout; every sum
+ * in one fixed order, so the outputs equal the restatement tests/global_ba_ref.py bit for bit.
+ *   K keyframes in ascending mnId:  kf_pose [K,7] qx qy qz qw tx ty tz (the layout of rfe_essential_graph's tiw_f32; widened and normalised
+ *   as 6i), kf_cam [K,5], kf_nlevels [K], kf_inv_level_sigma2 [K, RFE_MAX_LEVELS], kf_feat_off [K + 1] as rfe_local_ba;  fixed [K]: non-zero
+ *   for mnId == GetInitKFid() -- none or several are accepted and run.  The free keyframes in ascending index are the Hessian order
+ *   kpts_un [Nf,2], octave [Nf] (NULL = 0), uright [Nf] (NULL = all mono) as rfe_local_ba;  xw [L,3]: the map points in ascending mnId (the
+ *   layout of rfe_essential_graph's xw_out);  edge_point / edge_kf / edge_feat [E] sorted by (point, keyframe) strictly ascending
+ *   params.robust != 0: Huber edges with deltas (float) sqrt(huber2_mono / huber2_stereo), 6l's quadratic form entry for entry;
+ *   robust == 0 (the loop path): base_binary_edge.hpp:75-90 with Omega = invSigma2 I, and activeChi2 sums chi2 itself
+ * Outputs: pose [K,7] doubles and pose_f32 their cast -- a fixed keyframe's row is its widened, normalised input; point [L,3] and
+ *   point_f32; included [L]: 0 for a point without an edge (vbNotIncludedMP: the reference removes the vertex, this entry keeps it with
+ *   zero blocks and x = 0; the caller does not write it back); chi2 [E] as the last computeActiveErrors left it; trace [iterations,4] per
+ *   LM iteration run: trials, the lambda it left, currentChi, 0; stats [8]: 0 LM iterations, 1 trials, 2 rejected trials, 3 failed solves,
+ *   4 flags, 5 free keyframes, 6 tiles the factorisation processes, 7 tiles of the dense lower triangle.  Flags: rfe_local_ba's 1, 2, 4, 8
+ *   and 16; a solve also fails on a non-finite entry of L or of the solution (6m).
+ * BOTH forms are synchronous, like rfe_local_ba: the LM loop runs on the host, plain launches on the ctx stream and one small pinned
+ * read per linearisation and per trial; `stop` (a HOST pointer, pbStopFlag, may be NULL) is read where g2o's terminate() is.  The first
+ * kernels validate the keyframe and edge tables and the host reads the verdict before anything indexes by them.  Both return the number
+ * of LM iterations run (>= 0).  pose_f32, point_f32, chi2, trace, octave, uright may be NULL.
+ * Refused (RFE_ERR_INVALID): K outside 1..RFE_GBA_MAX_KF, L outside 0..RFE_GBA_MAX_POINTS, E outside 0..RFE_GBA_MAX_EDGES, Nf < 0;
+ *   iterations outside 0..RFE_GBA_MAX_ITERATIONS, max_trials < 0; a non-finite huber2 or user_lambda_init; a NULL required pointer, `fixed`
+ *   among them; an nlevels outside 1..RFE_MAX_LEVELS; a kf_feat_off that decreases or leaves 0..Nf; an edge index out of range; edges not
+ *   strictly ascending in (point, keyframe); more than RFE_GBA_MAX_PAIRS Schur pair entries (sum over the points of n (n + 1) / 2, n the
+ *   point's edges on free keyframes; the cap keeps the pair workspace at 512 MiB).  Nothing is written then.
+ * Workspace, grow-only: 648 bytes an observation, 268 a point, 12 K^2 for the block keys, 16 a Schur pair, and (24 ceil(P / 4))^2 doubles for the
+ *   matrix of P free keyframes: about 2.3 GB with every cap reached (1.36 GB of it for E = 2^21 observations).
+ * Out of scope: FullInertialBA, the merge overloads, EdgeSE3ProjectXYZToBody, KannalaBrandt8, the spanning-tree propagation of
+ *   RunGlobalBundleAdjustment, an ordering other than ascending keyframe index. */
+#define RFE_GBA_MAX_KF 1024
+#define RFE_GBA_MAX_POINTS (1 << 18)
+#define RFE_GBA_MAX_EDGES (1 << 21)
+#define RFE_GBA_MAX_ITERATIONS 64
+#define RFE_GBA_MAX_PAIRS (1 << 25)
+#define RFE_GBA_FLAG_ENDED_REJECTED 1
+#define RFE_GBA_FLAG_SOLVE_FAILED 2
+#define RFE_GBA_FLAG_NONFINITE 4
+#define RFE_GBA_FLAG_STOPPED 8
+#define RFE_GBA_FLAG_NO_ITERATION 16
+typedef struct rfe_global_ba_params {
+    int32_t iterations;          /* optimizer.optimize(nIterations): 10 behind a loop, 20 at the monocular initialisation; 0 runs none */
+    int32_t max_trials;          /* 0 = g2o's 10 */
+    double user_lambda_init;     /* <= 0: g2o's 1e-5 max |diagonal| */
+    int32_t robust;              /* bRobust */
+    int32_t reserved;
+    double huber2_mono, huber2_stereo; /* 5.99, 7.815: the Huber deltas are (float) sqrt of them; read when robust != 0 */
+    const volatile uint8_t* stop;/* HOST pointer or NULL: pbStopFlag */
+} rfe_global_ba_params;
+int rfe_global_ba_dev(rfe_ctx* ctx, rfe_global_ba_params params, const float* kf_pose_dev, const float* kf_cam_dev, const int32_t* kf_nlevels_dev,
+                      const float* kf_inv_level_sigma2_dev, const int32_t* kf_feat_off_dev, const uint8_t* fixed_dev, const float* kpts_un_dev,
+                      const int32_t* octave_dev, const float* uright_dev, const float* xw_dev, const int32_t* edge_point_dev,
+                      const int32_t* edge_kf_dev, const int32_t* edge_feat_dev, int K, int L, int E, int Nf, double* pose_dev, float* pose_f32_dev,
+                      double* point_dev, float* point_f32_dev, uint8_t* included_dev, double* chi2_dev, double* trace_dev, int32_t* stats_dev);
+int rfe_global_ba(rfe_ctx* ctx, rfe_global_ba_params params, const float* kf_pose, const float* kf_cam, const int32_t* kf_nlevels,
+                  const float* kf_inv_level_sigma2, const int32_t* kf_feat_off, const uint8_t* fixed, const float* kpts_un, const int32_t* octave,
+                  const float* uright, const float* xw, const int32_t* edge_point, const int32_t* edge_kf, const int32_t* edge_feat, int K, int L,
+                  int E, int Nf, double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* included, double* chi2, double* trace,
+                  int32_t* stats);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates
@@ -1081,6 +1144,11 @@ int rfe_k_lightglue_assign(rfe_ctx* ctx, const float* sim_dev, const float* x_de
  * pair's keypoint counts are padding) and its log-assignment matrix to scores_dev ([L,L], row stride L; only the m x n block is
  * written).  Any pointer may be NULL; pair < 0 disarms.  A pair index >= P of the next forward is ignored. */
 int rfe_k_set_lightglue_tap(rfe_ctx* ctx, int pair, float* x0_dev, float* x1_dev, float* scores_dev);
+/* One-shot hook for the NEXT rfe_global_ba / rfe_global_ba_dev of this ctx: when that call is given a `stop` pointer, the library
+ * itself writes 1 through it behind the call's `trials`-th trial (counted over the whole call), in front of the read of `stop` that
+ * follows a trial -- "pbStopFlag set while the optimisation runs", at a known trial.  trials <= 0 disarms.  The hook is taken by the
+ * first call that passes its argument checks, whatever becomes of that call. */
+int rfe_k_global_ba_stop_after(rfe_ctx* ctx, int trials);
 /* Fault injection for the pool's RCCL gather: the NEXT gather of `member` fails inside its ncclGroup (as a refused ncclSend would).  The
  * failing member aborts every member's communicator, nobody is left waiting in a collective, and the call delivers its results through
  * the COPY transport (RFE_POOL_AUTO) or reports the failure (RFE_POOL_RCCL); later calls use COPY.  tests/test_pool.py. */

@@ -26,14 +26,14 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev", "rfe_global_ba", "rfe_global_ba_dev",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
     "rfe_pool_create", "rfe_pool_destroy", "rfe_pool_last_error", "rfe_pool_size", "rfe_pool_ctx", "rfe_pool_has_rccl", "rfe_pool_set_weights",
     "rfe_pool_load_weights", "rfe_pool_set_option", "rfe_pool_set_hparams", "rfe_pool_shard", "rfe_pool_extract_match_stream",
     "rfe_profile_enable", "rfe_profile_filter", "rfe_profile_reset", "rfe_profile_read",
-    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_cross_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert", "rfe_k_bow_vocab_read",
+    "rfe_k_conv3x3", "rfe_k_linear", "rfe_k_scoremap", "rfe_k_sparse_desc", "rfe_k_select", "rfe_k_select_keys", "rfe_k_lightglue_taps", "rfe_k_set_lightglue_tap", "rfe_k_global_ba_stop_after", "rfe_k_lightglue_ffn", "rfe_k_attention", "rfe_k_cross_attention", "rfe_k_lightglue_self_attention", "rfe_k_lightglue_assign", "rfe_k_pool_inject_gather_failure", "rfe_k_onnx_convert", "rfe_k_bow_vocab_read",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -354,6 +354,28 @@ EG_MAX_KF, EG_MAX_EDGES, EG_MAX_POINTS, EG_MAX_ITERATIONS, EG_TILE_V = 1024, 163
 _eg = [C.c_void_p, EssentialGraphParams, _vp, _vp, _u8p, _ip, _ip, _u8p, _fp, _ip, C.c_int, C.c_int, C.c_int, _vp, _fp, _vp, _fp, _vp, _vp, _ip]
 lib.rfe_essential_graph.argtypes = _eg
 lib.rfe_essential_graph_dev.argtypes = _eg
+
+
+class GlobalBaParams(C.Structure):
+    """include/rover_fe.h: rfe_global_ba_params, passed BY VALUE -- the LM schedule of one GlobalBundleAdjustemnt, bRobust with the two Huber
+    thresholds and the host address of pbStopFlag (0 = none)."""
+    _fields_ = [("iterations", C.c_int32), ("max_trials", C.c_int32), ("user_lambda_init", C.c_double), ("robust", C.c_int32),
+                ("reserved", C.c_int32), ("huber2_mono", C.c_double), ("huber2_stereo", C.c_double), ("stop", C.c_void_p)]
+
+
+def global_ba_params(iterations=10, max_trials=0, user_lambda_init=0.0, robust=False, huber2_mono=5.99, huber2_stereo=7.815, stop=None):
+    """stop: None, or a numpy uint8 array of one element that the caller keeps alive (pbStopFlag)"""
+    return GlobalBaParams(int(iterations), int(max_trials), float(user_lambda_init), 1 if robust else 0, 0, float(huber2_mono),
+                          float(huber2_stereo), None if stop is None else stop.ctypes.data)
+
+
+GLOBAL_BA_OUTPUTS = ("pose_f32", "point_f32", "chi2", "trace")
+GBA_MAX_KF, GBA_MAX_POINTS, GBA_MAX_EDGES, GBA_MAX_ITERATIONS, GBA_MAX_PAIRS, GBA_TILE_V = 1024, 1 << 18, 1 << 21, 64, 1 << 25, 4
+_gba = [C.c_void_p, GlobalBaParams, _fp, _fp, _ip, _fp, _ip, _u8p, _fp, _ip, _fp, _fp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int,
+        _vp, _fp, _vp, _fp, _u8p, _vp, _vp, _ip]
+lib.rfe_global_ba.argtypes = _gba
+lib.rfe_global_ba_dev.argtypes = _gba
+lib.rfe_k_global_ba_stop_after.argtypes = [C.c_void_p, C.c_int]
 
 
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
@@ -1354,6 +1376,42 @@ class Context:
         return self._chk(lib.rfe_essential_graph_dev(self.h, params, a(s_est), a(s_meas), a(fixed), a(edge_i), a(edge_j), a(edge_from_est),
                                                      a(xw), a(point_ref), int(N), int(E), int(L), a(siw), a(tiw_f32), a(swi), a(xw_out),
                                                      a(chi2), a(trace), a(stats)))
+
+    def global_ba(self, params, kf_pose, kf_cam, kf_nlevels, kf_sigma2, kf_feat_off, fixed, kpts, xw, edge_point, edge_kf, edge_feat, octave=None,
+                  uright=None, outputs=GLOBAL_BA_OUTPUTS, shape=None):
+        """Optimizer::GlobalBundleAdjustemnt for one problem (rfe_global_ba, host arrays; DESIGN.md 6n).  params: global_ba_params();
+        kf_pose [K,7], kf_cam [K,5], kf_nlevels [K], kf_sigma2 [K,16], kf_feat_off [K+1], fixed [K]; kpts [Nf,2], octave / uright [Nf];
+        xw [L,3]; edge_point / edge_kf / edge_feat [E].  shape: (L, E, Nf) when the arrays are longer than the problem (what lies behind is
+        not read).  outputs: the optional arrays to ask for.  Returns a dict: pose [K,7] and point [L,3] float64, included [L], stats [8],
+        ret (LM iterations run), and pose_f32 / point_f32 / chi2 [E] / trace [iterations,4] as asked."""
+        kp, kc, ks = _opt(kf_pose, np.float32), _opt(kf_cam, np.float32), _opt(kf_sigma2, np.float32)
+        nl, fo, fx = _opt(kf_nlevels, np.int32), _opt(kf_feat_off, np.int32), _opt(fixed, np.uint8)
+        k, x = _opt(kpts, np.float32), _opt(xw, np.float32)
+        ep, ek, ef = _opt(edge_point, np.int32), _opt(edge_kf, np.int32), _opt(edge_feat, np.int32)
+        oc, ur = _opt(octave, np.int32), _opt(uright, np.float32)
+        K = 0 if fx is None else len(fx)
+        L, E, Nf = (len(x) // 3, len(ep), len(k) // 2) if shape is None else shape
+        its = max(int(params.iterations), 0)
+        o = {"pose": np.zeros((max(K, 1), 7), np.float64), "pose_f32": np.zeros((max(K, 1), 7), np.float32),
+             "point": np.zeros((max(L, 1), 3), np.float64), "point_f32": np.zeros((max(L, 1), 3), np.float32),
+             "included": np.zeros((max(L, 1),), np.uint8), "chi2": np.zeros((max(E, 1),), np.float64),
+             "trace": np.zeros((max(its, 1), 4), np.float64), "stats": np.zeros((8,), np.int32)}
+        ad = [o[n].ctypes.data if (n not in GLOBAL_BA_OUTPUTS or n in outputs) else None for n in o]
+        ret = self._chk(lib.rfe_global_ba(self.h, params, _addr(kp), _addr(kc), _addr(nl), _addr(ks), _addr(fo), _addr(fx), _addr(k), _addr(oc),
+                                          _addr(ur), _addr(x), _addr(ep), _addr(ek), _addr(ef), int(K), int(L), int(E), int(Nf), *ad))
+        n = {"pose": K, "pose_f32": K, "point": L, "point_f32": L, "included": L, "chi2": E, "trace": its, "stats": 8}
+        r = {key: a[:n[key]] for key, a in o.items() if key not in GLOBAL_BA_OUTPUTS or key in outputs}
+        r["ret"] = ret
+        return r
+
+    def global_ba_dev(self, params, K, L, E, Nf, kf_pose, kf_cam, kf_nlevels, kf_sigma2, kf_feat_off, fixed, kpts, xw, edge_point, edge_kf,
+                      edge_feat, pose, point, included, stats, octave=None, uright=None, pose_f32=None, point_f32=None, chi2=None, trace=None):
+        """rfe_global_ba_dev: every array a DevBuf (or a raw device address / torch tensor).  SYNCHRONOUS: returns the number of LM
+        iterations run when the optimisation has finished."""
+        a = _dev
+        return self._chk(lib.rfe_global_ba_dev(self.h, params, a(kf_pose), a(kf_cam), a(kf_nlevels), a(kf_sigma2), a(kf_feat_off), a(fixed), a(kpts),
+                                               a(octave), a(uright), a(xw), a(edge_point), a(edge_kf), a(edge_feat), int(K), int(L), int(E), int(Nf),
+                                               a(pose), a(pose_f32), a(point), a(point_f32), a(included), a(chi2), a(trace), a(stats)))
 
     def bow_transform(self, vocab, desc, levelsup=0):
         """Frame::ComputeBoW3 behind binarize_descriptors (rfe_bow_transform, host arrays; DESIGN.md 6h).  desc: float32 [N,256] SuperPoint

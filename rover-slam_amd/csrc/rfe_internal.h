@@ -150,6 +150,14 @@ struct rfe_ctx {
     void* ws_eg = nullptr; size_t ws_eg_bytes = 0;
     void* ws_eg_mat = nullptr; size_t ws_eg_mat_bytes = 0;
     void* h_eg = nullptr;
+    // rfe_global_ba*: estimates, structure, per-edge terms and the solve's vectors (ws_gba); the Schur blocks' pair lists with their
+    // sorting copy, sized from a count the front leaves (ws_gba_pairs); the dense 6 P x 6 P matrix in tiles, of which only the tiles of
+    // the pattern's fill are touched (ws_gba_mat); the pinned block of the small reads (h_gba)
+    void* ws_gba = nullptr; size_t ws_gba_bytes = 0;
+    void* ws_gba_pairs = nullptr; size_t ws_gba_pairs_bytes = 0;
+    void* ws_gba_mat = nullptr; size_t ws_gba_mat_bytes = 0;
+    void* h_gba = nullptr;
+    int gba_stop_after = 0;              // one-shot test hook (rfe_k_global_ba_stop_after): the next call sets *stop behind this many trials
     void* ws_st = nullptr; size_t ws_st_bytes = 0;   // stereo stream state: staged views, previous left view's features
     int st_H = 0, st_W = 0, st_K = 0; bool st_have_prev = false; int st_flip = 0; std::string st_pyr_key;   // st_flip: which of the two state slots holds the previous left view
     // one-shot test tap (rfe_k_set_lightglue_tap): the next LightGlue forward of this ctx, whatever entry point runs it,
@@ -494,6 +502,40 @@ void eg_launch_structure(hipStream_t s, const EgDev& d);
 void eg_launch_errors(hipStream_t s, const EgDev& d, int cur, bool linearise, bool max_diagonal);
 void eg_launch_trial(hipStream_t s, const EgDev& d, int cur, double lambda, const int32_t* col_start, const int32_t* row_start);
 void eg_launch_finish(hipStream_t s, const EgDev& d, int cur, double* siw, float* tiw_f32, double* swi, float* xw_out, double* chi2);
+
+// global_ba.hip: Optimizer::BundleAdjustment behind GlobalBundleAdjustemnt, one problem per call, the LM loop on the host
+// (api_global_ba.hip): 6l's per-edge terms and Schur complement behind a structure front whose work scales with the pairs,
+// and 6m's tiled LDLT (tile_ldlt.h) on GBA_TILE rows, GBA_TILE_V poses a tile.  GbaDev: the caller's inputs, the shape and ws_gba's carving
+constexpr int GBA_TILE_V = 4, GBA_TILE = 24;
+enum { GBA_D_CHI = 0, GBA_D_SCALE = 1, GBA_D_MAXDIAG = 2, GBA_CTL_D = 8 };
+enum { GBA_I_STATUS = 0, GBA_I_FLAGS = 1, GBA_I_FAIL = 2, GBA_I_NFREE = 3, GBA_I_NPAIRS = 4, GBA_I_NBLOCKS = 5, GBA_I_TILES = 6, GBA_CTL_I = 16 };
+struct GbaDev {
+    const float *kf_pose, *kf_cam, *kf_sigma2, *kpts, *uright, *xw;
+    const int32_t *kf_nlevels, *kf_feat_off, *octave, *edge_point, *edge_kf, *edge_feat;
+    const uint8_t* fixed;
+    int K, L, E, Nf, robust;
+    int P, NB, NT, NP;                               // known after the front: free poses, non-empty Schur blocks, tiles a side, padded rows
+    double delta_mono, dsqr_mono, delta_stereo, dsqr_stereo;
+    double* ctl_d; int32_t* ctl_i;
+    double *pose[2], *pt[2];                         // [K, 7] and [L, 3], the estimate and the trial
+    int32_t *free_index, *free_list;                 // [K] each
+    int32_t *pt_start, *pose_start, *pose_cnt, *pose_list, *pose_tmp;   // [L + 1], [K + 1], [K], [E], [E]
+    int32_t *key_cnt, *key_start;                    // [K K]: per dense block key i1 P + i2 the pairs still to place, the list's start
+    int32_t *blk_key, *blk_start;                    // [K (K + 1) / 2 (+ 1)]: the non-empty blocks in ascending key
+    unsigned long long *pairs, *pairs_tmp;           // [NPAIRS]: e1 << 32 | e2, ascending inside a block
+    int32_t *col_start, *col_tiles, *row_start, *row_tiles;
+    uint8_t* fill;                                   // [NT, NT]
+    double *lin, *chi2, *rho0, *Hll, *bl, *Dinv, *db, *xl, *Hpp, *bp, *xp, *BDinv, *Bdb, *sterm;
+    double *b, *z, *y, *xs, *dvec;                   // [NP] each
+    double* mat;                                     // [NP, NP]: Hschur in the upper triangle with the diagonal, L strictly below
+};
+void gba_launch_validate(hipStream_t s, const GbaDev& d);
+void gba_launch_count(hipStream_t s, const GbaDev& d);
+void gba_launch_structure(hipStream_t s, const GbaDev& d);
+void gba_launch_errors(hipStream_t s, const GbaDev& d, int cur, bool linearise, bool max_diagonal);
+void gba_launch_trial(hipStream_t s, const GbaDev& d, int cur, double lambda, const int32_t* col_start, const int32_t* row_start);
+void gba_launch_finish(hipStream_t s, const GbaDev& d, int cur, double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* included,
+                       double* chi2);
 
 // sim3_solver.hip: Sim3Solver's RANSAC with every hypothesis at once.  params is a HOST array: the front takes it by value,
 // S3_FRONT_CHUNK problems per launch, and leaves prob [B]; front [B, 12, N], counts [B, H] and hyps [B, H, 32] are workspace (or the
