@@ -945,6 +945,52 @@ int rfe_global_ba(rfe_ctx* ctx, rfe_global_ba_params params, const float* kf_pos
                   int E, int Nf, double* pose, float* pose_f32, double* point, float* point_f32, uint8_t* included, double* chi2, double* trace,
                   int32_t* stats);
 
+/* ---- TwoViewReconstruction on the device: the monocular initialisation's H and F RANSAC in one call ----
+ * TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:49-1221) behind the matcher: B problems (two frames each) per call.
+ * The front normalises both frames' keypoints (Normalize, over ALL n1 / n2 keypoints), lays the matches out and resolves every
+ * iteration's 8-set from the raw draws; one wave per (iteration, model) runs the 8-point DLT (ComputeH21 / ComputeF21) and scores it
+ * over every match (CheckHomography / CheckFundamental); one workgroup per problem takes the FIRST maximum of each model, RH = SH /
+ * (SH + SF), recomputes the winner's inlier flags and decomposes the chosen model into its 8 (ReconstructH) or 4 (ReconstructF) motion
+ * hypotheses; one thread per (hypothesis, match) runs CheckRT's Triangulate and gates; one workgroup per problem makes the
+ * reference's decision.  fp32, one rounding per operation; the outputs equal tests/two_view_ref.py bit for bit (6o states the
+ * arithmetic and its departures: fixed-schedule one-sided Jacobi for Eigen's JacobiSVD, fixed evaluation orders, acos in double).
+ * params [B] is a HOST array in both forms:
+ *   fx fy cx cy; sigma (0 = 1.0); rh_threshold (0 = the reference's 0.50); min_parallax (0 = 1.0); min_triangulated (0 = 50);
+ *   its = mMaxIterations (0 = 200; at most H); n1, n2: the keypoint counts of frame 1 and 2 (within N1max, N2max)
+ *   kpts1 [B,N1max,2], kpts2 [B,N2max,2]  mvKeysUn of both frames
+ *   S [B], pairs [B,Kmax,2]  the matches (i in frame 1, j in frame 2), i strictly ascending: exactly what rfe_match_dev writes; S is
+ *                  clamped to 0..Kmax
+ *   draws [B,H,8]  the raw rand() results (0 .. 2^31 - 1) of every iteration, in the reference's order: a draw r picks position
+ *                  (int)(((double)r / 2147483648.0) * size) (clamped to the list) of the swap-with-back list of :99-115.  Exactly 8 its
+ *                  draws are consumed.
+ * Outputs per problem: R21 [9] row-major, t21 [3] (the identity and 0 when the call answers false); p3d [N1max,3] and triangulated
+ *   [N1max] indexed by the feature of frame 1 (rows 0..n1-1 are written: zero where nothing was triangulated and when the call answers
+ *   false); inliers_h, inliers_f [Kmax] the best hypothesis' vbMatchesInliers per match (rows 0..S-1); scores [H,2] currentScore of every
+ *   iteration < its, H then F; models [2,9] the chosen H21 and F21 (zero when no iteration won); cand [8,16] per motion hypothesis R
+ *   [9], t [3], nGood, parallax, 0, 0 (the rows of the hypotheses that ran);
+ *   stats [16]: 0 the return value, 1 model (0 none, 1 H, 2 F), 2 N, 3 / 4 the winning iteration of H / F (-1 none), 5 / 6 their inlier
+ *   counts, 7 the chosen motion hypothesis (-1 none), 8 / 9 / 10 the bits of SH / SF / RH, 11 the exit (0 success, 1 SH + SF == 0, 2 the
+ *   singular-value ratios of ReconstructH, 3 no clear winner, 4 too few points, 5 parallax), 12 flags (1 N < 8, 2 a pair index outside
+ *   n1 / n2 -- either answers false without an iteration --, 4 a non-finite score), 13.. 0.
+ * Every output except R21, t21 and stats may be NULL.  The _dev form is asynchronous on the ctx stream: no host synchronisation, no
+ * host read of device data, no allocation once the workspace has the call's size; five launches.  The host form stages its arrays and
+ * returns stats[0] of problem 0 (0 when B = 0).
+ * Refused (RFE_ERR_INVALID): B outside 0..16; N1max, N2max or Kmax outside 0..4096; H outside 1..1024; its outside 0..H (200 > H when
+ *   its = 0); n1 / n2 outside their capacities; min_triangulated < 0; a NULL required pointer; host form only: a non-finite intrinsic
+ *   or sigma.  Keypoints are not checked: a NaN runs through (every score is NaN, no iteration wins, the call answers false).
+ * Out of scope: KannalaBrandt8::ReconstructWithTwoViews (it undistorts, then runs the same class). */
+typedef struct rfe_two_view_params {
+    float fx, fy, cx, cy, sigma, rh_threshold, min_parallax;
+    int32_t min_triangulated, its, n1, n2;
+} rfe_two_view_params;
+int rfe_two_view_dev(rfe_ctx* ctx, const rfe_two_view_params* params, const float* kpts1_dev, const float* kpts2_dev, const int32_t* S_dev,
+                     const int32_t* pairs_dev, const int32_t* draws_dev, int B, int N1max, int N2max, int Kmax, int H, float* R21_dev,
+                     float* t21_dev, float* p3d_dev, uint8_t* triangulated_dev, uint8_t* inliers_h_dev, uint8_t* inliers_f_dev,
+                     float* scores_dev, float* models_dev, float* cand_dev, int32_t* stats_dev);
+int rfe_two_view(rfe_ctx* ctx, const rfe_two_view_params* params, const float* kpts1, const float* kpts2, const int32_t* S,
+                 const int32_t* pairs, const int32_t* draws, int B, int N1max, int N2max, int Kmax, int H, float* R21, float* t21, float* p3d,
+                 uint8_t* triangulated, uint8_t* inliers_h, uint8_t* inliers_f, float* scores, float* models, float* cand, int32_t* stats);
+
 /* ---- place recognition: ComputeBoW3 and the keyframe database's scores on the device ----
  * Frame::ComputeBoW3 / KeyFrame::ComputeBoW3 (src/Frame.cc:1044-1054) = binarize_descriptors + DBoW3::Vocabulary::transform
  * (Thirdparty/DBoW3/src/Vocabulary.cpp:752-874); KeyFrameDatabase::DetectNBestCandidates / DetectRelocalizationCandidates
@@ -1138,6 +1184,15 @@ int rfe_k_lightglue_self_attention(rfe_ctx* ctx, int layer, const float* x_dev, 
 int rfe_k_lightglue_assign(rfe_ctx* ctx, const float* sim_dev, const float* x_dev, const float* wm_dev, const float* bm_dev, const int32_t* lens_dev,
                            int P, int L, float thr, int cap, int scores_pair, int32_t sentinel, float* z_dev, float* rowlse_dev, float* collse_dev,
                            float* mx0_dev, int32_t* a0_dev, int32_t* a1_dev, int32_t* S_dev, int32_t* pairs_dev, float* ms_dev, float* scores_dev);
+/* The gates of rfe_two_view without an SVD in front of them, through the device functions the kernels use.  HOST pointers,
+ * synchronous, n <= 4096; pts [n,4] = u1 v1 u2 v2 of every match.
+ * rfe_k_two_view_check: CheckHomography (model 0; H12 is the cofactor inverse of M) or CheckFundamental (model 1) of ONE model M [9]:
+ *   contrib [n] what each match adds to the score, inl [n] its flag.
+ * rfe_k_two_view_check_rt: CheckRT of ONE motion hypothesis Rt [12] = R row-major | t with K4 = fx fy cx cy and th2: code [n] (0 not
+ *   counted, 1 counted in nGood without vbGood, 2 counted and vbGood), cosp [n] cosParallax, p3d [n,3]. */
+int rfe_k_two_view_check(rfe_ctx* ctx, int model, const float* M, float sigma, const float* pts, int n, float* contrib, uint8_t* inl);
+int rfe_k_two_view_check_rt(rfe_ctx* ctx, const float* Rt, const float* K4, float th2, const float* pts, int n, uint8_t* code, float* cosp,
+                            float* p3d);
 /* One-shot tap for the NEXT LightGlue forward of this ctx, whichever entry point runs it (rfe_match[_dev] with P pairs,
  * rfe_extract_match_stream_dev, rfe_stereo_frame_dev) and therefore whichever tiling it selects: after the last layer the final
  * token states of pair `pair` are copied to x0_dev / x1_dev ([L,256] each, L = max(Mmax,Nmax) rounded up to 4; rows past the

@@ -27,6 +27,7 @@ EXPORTS = [
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
     "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev", "rfe_global_ba", "rfe_global_ba_dev",
+    "rfe_two_view", "rfe_two_view_dev", "rfe_k_two_view_check", "rfe_k_two_view_check_rt",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -279,6 +280,31 @@ lib.rfe_sim3_ransac_iterations.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int
 def sim3_ransac_iterations(probability, min_inliers, n, max_its):
     """SetRansacParameters' mRansacMaxIts (rfe_sim3_ransac_iterations; needs no device)"""
     return int(lib.rfe_sim3_ransac_iterations(float(probability), int(min_inliers), int(n), int(max_its)))
+
+
+class TwoViewParams(C.Structure):
+    """include/rover_fe.h: rfe_two_view_params -- camera, sigma, rh_threshold, min_parallax, min_triangulated, its, n1, n2 of one
+    TwoViewReconstruction problem (0 = the reference's default, for every field behind cy but n1 / n2)."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("sigma", C.c_float), ("rh_threshold", C.c_float),
+                ("min_parallax", C.c_float), ("min_triangulated", C.c_int32), ("its", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32)]
+
+
+def two_view_params(problems):
+    """an rfe_two_view_params array from dicts with the structure's field names (missing fields are 0)"""
+    arr = (TwoViewParams * max(len(problems), 1))()
+    for p, d in zip(arr, problems):
+        for k, t in TwoViewParams._fields_:
+            setattr(p, k, (float if t is C.c_float else int)(d.get(k, 0)))
+    return arr
+
+
+TWO_VIEW_OUTPUTS = ("p3d", "triangulated", "inliers_h", "inliers_f", "scores", "models", "cand")
+_tv = [C.c_void_p, C.c_void_p, _fp, _fp, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _u8p, _u8p, _u8p, _fp, _fp,
+       _fp, _ip]
+lib.rfe_two_view.argtypes = _tv
+lib.rfe_two_view_dev.argtypes = _tv
+lib.rfe_k_two_view_check.argtypes = [C.c_void_p, C.c_int, _fp, C.c_float, _fp, C.c_int, _fp, _u8p]
+lib.rfe_k_two_view_check_rt.argtypes = [C.c_void_p, _fp, _fp, C.c_float, _fp, C.c_int, _u8p, _fp, _fp]
 class OptimizeSim3Params(C.Structure):
     """include/rover_fe.h: rfe_optimize_sim3_params -- both keyframes' poses, cameras and level tables, th2, the flags, n / n2 and the LM
     schedule of one OptimizeSim3 problem."""
@@ -1261,6 +1287,64 @@ class Context:
         P = problems if isinstance(problems, C.Array) else sim3_solver_params(problems)
         self._chk(lib.rfe_sim3_ransac_dev(self.h, C.addressof(P), a(xw1), a(xw2), a(sigma2_1), a(sigma2_2), a(draws), int(B), int(N), int(H),
                                           a(T12), a(R), a(t), a(s), a(inliers), a(best_inliers), a(counts), a(hyps), a(stats)))
+
+    def two_view(self, problems, kpts1, kpts2, S, pairs, draws, fill=None, outputs=TWO_VIEW_OUTPUTS):
+        """TwoViewReconstruction for B problems (rfe_two_view, host arrays).  problems: B dicts (two_view_params()) or the
+        ctypes array with B given by S; kpts1 [B,N1max,2], kpts2 [B,N2max,2], S [B], pairs [B,Kmax,2], draws [B,H,8].  fill: what the
+        optional arrays hold where the call does not write (default 0).  outputs: the optional arrays to ask for (the others are passed
+        as NULL).  Returns a dict: R21 [B,9], t21 [B,3], stats [B,16], ret and the optional arrays."""
+        s = np.ascontiguousarray(S, np.int32).reshape(-1)
+        B = len(s)
+        P = problems if isinstance(problems, C.Array) else two_view_params(problems)
+        assert len(P) >= B
+        k1, k2 = np.ascontiguousarray(kpts1, np.float32), np.ascontiguousarray(kpts2, np.float32)
+        pr, d = np.ascontiguousarray(pairs, np.int32), np.ascontiguousarray(draws, np.int32)
+        N1, N2, K = (a.size // (2 * B) if B else 0 for a in (k1, k2, pr))
+        H = d.size // (8 * B) if B else 1
+        assert k1.size == B * N1 * 2 and k2.size == B * N2 * 2 and pr.size == B * K * 2 and d.size == B * H * 8
+        b1 = max(B, 1)
+        shape = {"R21": (b1, 9), "t21": (b1, 3), "p3d": (b1, max(N1, 1), 3), "triangulated": (b1, max(N1, 1)), "inliers_h": (b1, max(K, 1)),
+                 "inliers_f": (b1, max(K, 1)), "scores": (b1, H, 2), "models": (b1, 2, 9), "cand": (b1, 8, 16), "stats": (b1, 16)}
+        dt = {"triangulated": np.uint8, "inliers_h": np.uint8, "inliers_f": np.uint8, "stats": np.int32}
+        o = {k: np.zeros(shape[k], dt.get(k, np.float32)) for k in shape}
+        for k, v in (fill or {}).items():
+            v = np.asarray(v)
+            o[k][:B, :v.shape[1]] = v
+        arg = lambda k: o[k].ctypes.data if k in outputs else None   # noqa: E731
+        ret = self._chk(lib.rfe_two_view(self.h, C.addressof(P), _addr(k1), _addr(k2), _addr(s), _addr(pr), _addr(d), B, N1, N2, K, H,
+                                         o["R21"].ctypes.data, o["t21"].ctypes.data, *(arg(k) for k in TWO_VIEW_OUTPUTS), o["stats"].ctypes.data))
+        cut = {"p3d": N1, "triangulated": N1, "inliers_h": K, "inliers_f": K}
+        r = {k: (o[k][:B, :cut[k]] if k in cut else o[k][:B]) for k in ("R21", "t21", "stats") + tuple(outputs)}
+        r["ret"] = ret
+        return r
+
+    def two_view_dev(self, problems, kpts1, kpts2, S, pairs, draws, B, N1max, N2max, Kmax, H, R21, t21, stats, p3d=None, triangulated=None,
+                     inliers_h=None, inliers_f=None, scores=None, models=None, cand=None):
+        """rfe_two_view_dev: problems is a HOST array (two_view_params()), every other array a DevBuf (or a raw device address / torch
+        tensor); asynchronous on the ctx stream."""
+        a = _dev
+        P = problems if isinstance(problems, C.Array) else two_view_params(problems)
+        self._chk(lib.rfe_two_view_dev(self.h, C.addressof(P), a(kpts1), a(kpts2), a(S), a(pairs), a(draws), int(B), int(N1max), int(N2max),
+                                       int(Kmax), int(H), a(R21), a(t21), a(p3d), a(triangulated), a(inliers_h), a(inliers_f), a(scores),
+                                       a(models), a(cand), a(stats)))
+
+    def k_two_view_check(self, model, M, pts, sigma=1.0):
+        """rfe_k_two_view_check: CheckHomography (model 0) / CheckFundamental (1) of ONE model M [9] over pts [n,4] -> contrib [n], inl [n]"""
+        M, pts = np.ascontiguousarray(M, np.float32).reshape(9), np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        n = len(pts)
+        contrib, inl = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.uint8)
+        self._chk(lib.rfe_k_two_view_check(self.h, int(model), _addr(M), float(sigma), _addr(pts), n, contrib.ctypes.data, inl.ctypes.data))
+        return contrib[:n], inl[:n]
+
+    def k_two_view_check_rt(self, R, t, K4, th2, pts):
+        """rfe_k_two_view_check_rt: CheckRT of ONE (R, t) over pts [n,4] -> code [n], cosParallax [n], p3d [n,3]"""
+        Rt = np.concatenate([np.asarray(R, np.float32).reshape(9), np.asarray(t, np.float32).reshape(3)])
+        K4, pts = np.ascontiguousarray(K4, np.float32).reshape(4), np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        n = len(pts)
+        code, cosp, p3d = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32), np.zeros((max(n, 1), 3), np.float32)
+        self._chk(lib.rfe_k_two_view_check_rt(self.h, _addr(Rt), _addr(K4), float(th2), _addr(pts), n, code.ctypes.data, cosp.ctypes.data,
+                                              p3d.ctypes.data))
+        return code[:n], cosp[:n], p3d[:n]
 
     def optimize_sim3(self, problems, s12_0, xw1, xw2, valid, kpts1, idx2, kpts2, octave1=None, octave2=None, keep=None, chi2=None,
                       outputs=OPTIMIZE_SIM3_OUTPUTS):

@@ -208,7 +208,7 @@ extern "C" void rfe_destroy(rfe_ctx* c) {
     host_graph_release(c->g_match);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     c->sp_hold.reset(); c->lg_hold.reset();   // the last ctx holding a device copy frees it
-    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->ws_ps); fr(c->ws_tri); fr(c->ws_bow); fr(c->ws_s3); fr(c->ws_lba); fr(c->ws_lba_pairs); fr(c->ws_eg); fr(c->ws_eg_mat); fr(c->ws_gba); fr(c->ws_gba_pairs); fr(c->ws_gba_mat); fr(c->sp_cnt); fr(c->ws_pyr); fr(c->ws_ptab);
+    fr(c->ws_sp); fr(c->ws_lg); fr(c->ws_io); fr(c->ws_tmp); fr(c->ws_st); fr(c->ws_ps); fr(c->ws_tri); fr(c->ws_bow); fr(c->ws_s3); fr(c->ws_tv); fr(c->ws_lba); fr(c->ws_lba_pairs); fr(c->ws_eg); fr(c->ws_eg_mat); fr(c->ws_gba); fr(c->ws_gba_pairs); fr(c->ws_gba_mat); fr(c->sp_cnt); fr(c->ws_pyr); fr(c->ws_ptab);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_lba) (void)hipHostFree(c->h_lba);
     if (c->h_eg) (void)hipHostFree(c->h_eg);
@@ -300,7 +300,7 @@ extern "C" void rfe_host_free(void* p) {
 }
 
 extern "C" int64_t rfe_workspace_bytes(rfe_ctx* c) {
-    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes + c->ws_ps_bytes + c->ws_tri_bytes + c->ws_bow_bytes + c->ws_s3_bytes + c->ws_lba_bytes + c->ws_lba_pairs_bytes + c->ws_eg_bytes + c->ws_eg_mat_bytes + c->ws_gba_bytes + c->ws_gba_pairs_bytes + c->ws_gba_mat_bytes + c->ws_pyr_bytes + c->ws_ptab_bytes) : 0;
+    return c ? (int64_t)(c->ws_sp_bytes + c->ws_lg_bytes + c->ws_io_bytes + c->ws_tmp_bytes + c->ws_st_bytes + c->ws_ps_bytes + c->ws_tri_bytes + c->ws_bow_bytes + c->ws_s3_bytes + c->ws_tv_bytes + c->ws_lba_bytes + c->ws_lba_pairs_bytes + c->ws_eg_bytes + c->ws_eg_mat_bytes + c->ws_gba_bytes + c->ws_gba_pairs_bytes + c->ws_gba_mat_bytes + c->ws_pyr_bytes + c->ws_ptab_bytes) : 0;
 }
 
 // =====================================================================================

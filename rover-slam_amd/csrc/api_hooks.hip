@@ -265,6 +265,40 @@ extern "C" int rfe_k_lightglue_assign(rfe_ctx* c, const float* sim, const float*
     return RFE_OK;
 }
 
+// CheckHomography (model 0; H12 is the cofactor inverse of M) or CheckFundamental (model 1) of ONE model M [9] over pts [n,4] = u1 v1 u2 v2:
+// contrib [n] what each match adds to the score, inl [n] its flag.  HOST pointers, synchronous; n <= 4096.
+extern "C" int rfe_k_two_view_check(rfe_ctx* c, int model, const float* M, float sigma, const float* pts, int n, float* contrib, uint8_t* inl) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!M || !pts || !contrib || !inl || n < 0 || n > 4096 || model < 0 || model > 1) return fail(c, RFE_ERR_INVALID, "k_two_view_check: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dM, *dp, *dc; uint8_t* di;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dM, M, (size_t)9); io.in(dp, pts, (size_t)n * 4); io.out(dc, contrib, (size_t)n); io.out(di, inl, (size_t)n);
+    int rc = io.upload();
+    if (rc) return rc;
+    const float s2 = sigma * sigma;
+    launch_two_view_hook_check(c->stream, model, dM, 1.f / s2, dp, n, dc, di);
+    RFE_HIP(c, hipGetLastError());
+    return io.download();
+}
+
+// CheckRT of ONE motion hypothesis Rt [12] = R row-major | t over pts [n,4] with K = (fx, fy, cx, cy) and th2: code [n] (0 not counted, 1
+// counted without vbGood, 2 counted and vbGood), cosp [n], p3d [n,3].  HOST pointers, synchronous; n <= 4096.
+extern "C" int rfe_k_two_view_check_rt(rfe_ctx* c, const float* Rt, const float* K4, float th2, const float* pts, int n, uint8_t* code, float* cosp,
+                                       float* p3d) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!Rt || !K4 || !pts || !code || !cosp || !p3d || n < 0 || n > 4096) return fail(c, RFE_ERR_INVALID, "k_two_view_check_rt: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    float *dR, *dp, *dc, *dx; uint8_t* dk;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dR, Rt, (size_t)12); io.in(dp, pts, (size_t)n * 4); io.out(dk, code, (size_t)n); io.out(dc, cosp, (size_t)n); io.out(dx, p3d, (size_t)n * 3);
+    int rc = io.upload();
+    if (rc) return rc;
+    launch_two_view_hook_check_rt(c->stream, dR, K4[0], K4[1], K4[2], K4[3], th2, dp, n, dk, dc, dx);
+    RFE_HIP(c, hipGetLastError());
+    return io.download();
+}
+
 extern "C" int rfe_k_lightglue_taps(rfe_ctx* c, const float* k0n, const float* k1n, const float* d0, const float* d1,
                                     int M, int N, float* x0, float* x1, float* scores) {
     int rc = lg_check(c, 1, M, N);

@@ -140,6 +140,7 @@ struct rfe_ctx {
     void* ws_tri = nullptr; size_t ws_tri_bytes = 0; // rfe_triangulate_neighbours*: per-slot results, claims, per-neighbour counts
     void* ws_bow = nullptr; size_t ws_bow_bytes = 0; // rfe_bow_transform*: per-feature word / node / weight the caller did not ask for
     void* ws_s3 = nullptr; size_t ws_s3_bytes = 0;   // rfe_sim3_ransac*: per-problem records, the front's rows, counts and hypotheses the caller did not ask for
+    void* ws_tv = nullptr; size_t ws_tv_bytes = 0;   // rfe_two_view*: per-problem records, match rows, 8-sets, per-iteration models, CheckRT's per-match results
     // rfe_local_ba*: estimates, structure, per-edge terms, the dense reduced system (ws_lba); the Schur blocks' pair lists, sized from a
     // count the first kernels leave, apart (ws_lba_pairs); a pinned block for the one small read per LM trial (h_lba)
     void* ws_lba = nullptr; size_t ws_lba_bytes = 0;
@@ -548,5 +549,24 @@ void launch_sim3_hypotheses(hipStream_t s, const Sim3Prob* prob, const float* fr
                             float* hyps);
 void launch_sim3_select(hipStream_t s, const Sim3Prob* prob, const float* front, const int32_t* counts, const float* hyps, int B, int N, int H,
                         float* T12, float* R, float* t, float* sc, uint8_t* inliers, uint8_t* best_inliers, int32_t* stats);
+
+// two_view.hip: TwoViewReconstruction with every RANSAC iteration of both models at once.  params is a HOST array: the front
+// takes it by value (B <= TV_MAX_B) and leaves prob [B].  Workspace: soa [B, 4, Ks] the matches' u1 | v1 | u2 | v2 rows (Ks = Kmax rounded up
+// to 4: 16-byte loads), sets [B, H, 8], hmodels [B, H, 2, 9] every iteration's H21 | F21, sel [B] the selection's record, winl [B, 2, Kmax]
+// the winners' flags, rcode / rcos / rp [B, 8, Kmax (, 3)] CheckRT per motion hypothesis and match; scores [B, H, 2] is the caller's or
+// workspace.  Every output but R21, t21 and stats may be NULL; presets nothing
+constexpr int TV_MAX_B = 16;
+struct TvProb { float fx, fy, cx, cy, invs2, th2, rh_threshold, min_parallax, T1[4], T2[4], T2inv[9]; int32_t min_triangulated, N, its, n1, n2, flags; };
+struct TvSel { float cand[8][12], SH, SF, RH; int32_t win_h, win_f, cnt_h, cnt_f, ncand, model, exit, flags; };
+struct TvBuffers { TvProb* prob; TvSel* sel; float *soa, *hmodels, *scores, *rcos, *rp; int32_t* sets; uint8_t *winl, *rcode; };
+inline int tv_soa_stride(int Kmax) { return (Kmax + 3) & ~3; }
+void launch_two_view(hipStream_t s, const rfe_two_view_params* params, const float* kpts1, const float* kpts2, const int32_t* S,
+                     const int32_t* pairs, const int32_t* draws, int B, int N1max, int N2max, int Kmax, int H, const TvBuffers& w, float* R21,
+                     float* t21, float* p3d, uint8_t* triangulated, uint8_t* inliers_h, uint8_t* inliers_f, float* scores, float* models,
+                     float* cand, int32_t* stats);
+// the test hooks' kernels: CheckHomography / CheckFundamental of one model (0 H, 1 F) and CheckRT of one (R | t) [12] over pts [n,4]
+void launch_two_view_hook_check(hipStream_t s, int model, const float* M9, float invs2, const float* pts, int n, float* contrib, uint8_t* inl);
+void launch_two_view_hook_check_rt(hipStream_t s, const float* Rt, float fx, float fy, float cx, float cy, float th2, const float* pts, int n,
+                                   uint8_t* code, float* cosp, float* p3d);
 
 }  // namespace rfe

@@ -1,7 +1,7 @@
 // triangulate.hip -- LocalMapping::CreateNewMapPoints behind the matcher (reference src/LocalMapping.cc:662-943, the filter of
 // SPmatcher::SearchForTriangulation at src/Matchers/SPmatcher.cc:1376-1393, GeometricTools::Triangulate, KeyFrame::UnprojectStereo) for the
 // matches of all neighbours at once:
-//   * tri_eval_kernel:    one thread per match slot (n, k): the filter, parallax, Triangulate (a one-sided Jacobi null vector, fully unrolled:
+//   * tri_eval_kernel:    one thread per match slot (n, k): the filter, parallax, Triangulate (jacobi_null.h: a one-sided Jacobi null vector, fully unrolled:
 //                         A and V stay in registers) or UnprojectStereo, and every gate in the reference's order.  fp32, one rounding per
 //                         written operation (-ffp-contract=off, plain / and sqrtf); the reference's three double expressions in double.  A
 //                         slot that passes claims its feature with atomicMin(claim[i], n): integer, so the outcome has no order in it.
@@ -10,6 +10,7 @@
 //   * tri_compact_kernel: one workgroup per neighbour: the exclusive prefix of the neighbours' counts, then the winners in slot order by a
 //                         workgroup scan -- the list in creation order.
 #include "rfe_internal.h"
+#include "jacobi_null.h"
 
 namespace rfe {
 
@@ -28,48 +29,6 @@ __device__ __forceinline__ float tri_norm3(float x, float y, float z) { return s
 __device__ __forceinline__ float tri_stereo_parallax(float mb, float d) {
     const float h = mb / 2.f, dd = d * d, hh = h * h;
     return (dd - hh) / (dd + hh);
-}
-
-// Null vector of the 4 x 4 matrix A: one-sided Jacobi on its columns, V accumulated; every index below is a compile-time constant once the
-// loops are unrolled, so A and V are 32 registers.
-__device__ __forceinline__ void tri_null_vector(float (&A)[4][4], float (&h)[4]) {
-    float V[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) V[r][c] = r == c ? 1.f : 0.f;
-#pragma unroll
-    for (int sweep = 0; sweep < TRI_SWEEPS; ++sweep)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const float alpha = ((A[0][p] * A[0][p] + A[1][p] * A[1][p]) + A[2][p] * A[2][p]) + A[3][p] * A[3][p];
-                const float beta = ((A[0][q] * A[0][q] + A[1][q] * A[1][q]) + A[2][q] * A[2][q]) + A[3][q] * A[3][q];
-                const float gamma = ((A[0][p] * A[0][q] + A[1][p] * A[1][q]) + A[2][p] * A[2][q]) + A[3][p] * A[3][q];
-                const bool rot = gamma != 0.f;                           // NaN rotates (and spreads)
-                const float zeta = (beta - alpha) / (2.f * gamma);
-                const float t = (zeta >= 0.f ? 1.f : -1.f) / (fabsf(zeta) + sqrtf(1.f + zeta * zeta));
-                const float c = 1.f / sqrtf(1.f + t * t);
-                const float s = c * t;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float ap = A[r][p], aq = A[r][q], vp = V[r][p], vq = V[r][q];
-                    A[r][p] = rot ? c * ap - s * aq : ap; A[r][q] = rot ? s * ap + c * aq : aq;
-                    V[r][p] = rot ? c * vp - s * vq : vp; V[r][q] = rot ? s * vp + c * vq : vq;
-                }
-            }
-    float nb = ((A[0][0] * A[0][0] + A[1][0] * A[1][0]) + A[2][0] * A[2][0]) + A[3][0] * A[3][0];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) h[r] = V[r][0];
-#pragma unroll
-    for (int c = 1; c < 4; ++c) {
-        const float nc = ((A[0][c] * A[0][c] + A[1][c] * A[1][c]) + A[2][c] * A[2][c]) + A[3][c] * A[3][c];
-        const bool less = nc < nb;                                       // the first minimum stays; a NaN norm is never smaller
-        nb = less ? nc : nb;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h[r] = less ? V[r][c] : h[r];
-    }
 }
 
 // reprojection gate of one view (LocalMapping.cc:842-867 / 875-893): true = the slot fails.  mbf is the CURRENT keyframe's in both views (:886)
@@ -147,7 +106,7 @@ __global__ __launch_bounds__(256) void tri_eval_kernel(const rfe_tri_params P, c
                 A[0][c] = a1 * t12 - t10; A[1][c] = b1 * t12 - t11;
                 A[2][c] = a2 * t22 - t20; A[3][c] = b2 * t22 - t21;
             }
-            tri_null_vector(A, h);
+            jacobi_null4<TRI_SWEEPS>(A, h);
             code = 4;
             if (h[3] == 0.f) break;
             X = h[0] / h[3]; Y = h[1] / h[3]; Z = h[2] / h[3];
