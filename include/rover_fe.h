@@ -647,8 +647,8 @@ int rfe_triangulate_neighbours(rfe_ctx* ctx, const rfe_tri_params* params, const
  *   max_trials; a NULL required pointer (params, pose0, pose, outlier, stats; kpts_un, xw, has_mp when B N > 0); host form only: a
  *   non-finite fx, fy, cx, cy, bf, inv_level_sigma2 or pose0.  The per-feature arrays are not checked: a NaN world position runs through
  *   as in the reference and raises flag 4.
- * Out of scope: two-camera rigs (mpCamera2, EdgeSE3ProjectXYZOnlyPoseToBody), KannalaBrandt8 and the inertial variants
- *   (PoseInertialOptimization*) -- the caller keeps the reference's function for those. */
+ * Out of scope: two-camera rigs (mpCamera2, EdgeSE3ProjectXYZOnlyPoseToBody) and KannalaBrandt8 -- the caller keeps the reference's
+ *   function for those.  The inertial variants (PoseInertialOptimization*) are rfe_pose_inertial_optimization, below. */
 typedef struct rfe_pose_params {
     float fx, fy, cx, cy, bf;
     int32_t nlevels;                          /* 1..RFE_MAX_LEVELS */
@@ -663,6 +663,69 @@ int rfe_pose_optimization_dev(rfe_ctx* ctx, const rfe_pose_params* params, const
 int rfe_pose_optimization(rfe_ctx* ctx, const rfe_pose_params* params, const float* pose0, const float* kpts_un, const int32_t* octave,
                           const float* uright, const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose,
                           float* pose_f32, uint8_t* outlier, float* chi2, double* trace, int32_t* stats);
+
+/* ---- Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame on the device: visual-inertial Gauss-Newton ----
+ * src/Optimizer.cc:416-968 and :983-1623 with Marginalize (:1644-1725) over g2o's OptimizationAlgorithmGaussNewton and LinearSolverDense:
+ * B problems per call, one workgroup each; the four rounds of ten Gauss-Newton iterations, the float chi2 classification between them,
+ * the recovery pass, the final Hessian, the marginalisation of the previous frame and ConstraintPoseImu's eigenvalue clipping all run
+ * inside the kernel.  Double precision (the preintegration's bias correction in float, as ImuTypes.cc:377-427 has it); every sum in one
+ * fixed order, so the outputs equal the restatement tests/pose_inertial_ref.py bit for bit (6p states the arithmetic and its departures
+ * from the reference's own build).  Single pinhole camera.
+ * Per problem, of N rows the first n (n_dev, clamped to 0..N; NULL = N) are features:
+ *   mode           RFE_PIO_LAST_KEYFRAME: the previous state is fixed, 15 free dimensions, no prior edge;  RFE_PIO_LAST_FRAME: the previous
+ *                  state is free, 30 dimensions, EdgePriorPoseImu under Huber 5 and Marginalize(H, 0, 14) at the end
+ *   rec_init       bRecInit (NULL = 0): != 0 skips the recovery pass
+ *   cam [36]       floats, row-major rotations: the frame's GetPose() as Rcw 9, tcw 3 (read until the first update, as ImuCamPose's
+ *                  constructor does); mImuCalib.mTcb as Rcb 9, tcb 3; mImuCalib.mTbc as Rbc 9 (not read: Rbc = Rcb^T), tbc 3
+ *   state [21], prev_state [21]   floats: Rwb 9, twb 3, velocity 3, gyro bias 3, accelerometer bias 3 of the frame and of mpLastKeyFrame /
+ *                  mpPrevFrame -- what the vertex constructors cast
+ *   preint [RFE_PIO_PREINT_FLOATS]   the preintegration EdgeInertial is built from (mpImuPreintegrated / mpImuPreintegratedFrame): dT, dR 9,
+ *                  dV 3, dP 3, JRg 9, JVg 9, JVa 9, JPg 9, JPa 9, its bias b as bax bay baz bwx bwy bwz, C's leading 9 x 9 block
+ *   cov_rw [18]    C(9..11, 9..11) and C(12..14, 12..14) of mpImuPreintegrated, which InfoG / InfoA invert (LastFrame takes them from a
+ *                  different preintegration than the edge, :1213 against :1233, :1246; the two arrays let the caller reproduce that)
+ *   prior_in [RFE_PIO_PRIOR_DOUBLES]   LastFrame only: the previous frame's ConstraintPoseImu as doubles Rwb 9, twb 3, vwb 3, bg 3, ba 3, H 225
+ *   kpts_un, octave, uright, xw, has_mp   as rfe_pose_optimization;  track_depth [N] the map point's mTrackDepth (bClose = < 10.f)
+ * params: fx, fy, cx, cy, bf = mbf; inv_level_sigma2 = mvInvLevelSigma2.
+ * Outputs: state_out [21] doubles, the optimised Rwb, twb, velocity, bg, ba; state_f32 their float casts (what SetImuPoseVelocity and
+ *   IMU::Bias receive), which a later call takes as prev_state; outlier [N] and chi2 [N] written where has_mp is set among the n features
+ *   (chi2: the float the last classification or the recovery pass compared); prior_out [RFE_PIO_PRIOR_DOUBLES]: the state and the 15 x 15 H
+ *   after ConstraintPoseImu's constructor, in prior_in's layout, so frame k's prior_out_dev is frame k + 1's prior_in_dev without leaving
+ *   the device; trace [4,8] per round: iterations run, the active robust chi2 the first and the last iteration saw, 1 if every solve
+ *   succeeded, inliers after the round, 0, 0, 0; stats [16]: 0 the return value nInitialCorrespondences - nBad, 1 nInitialCorrespondences,
+ *   2 nBad, 3 mono edges, 4 stereo edges, 5 rounds run, 6 iterations run, 7 failed solves, 8 flags, 9 nInliers of the last round, 10..15 0.
+ *   flags: 1 a solve found the system not positive (the stale x was applied and the round ended), 2 a non-finite output, 4 fewer than
+ *   10 edges ended the rounds after the first, 8 the recovery pass ran, 16 an eigenvalue of EdgeInertial's information was clipped,
+ *   32 the marginalisation cut a singular value, 64 an eigenvalue of prior_out's H was clipped, 128 the prior's Huber weight was below 1.
+ *   256 (the _dev form only, which reads mode on the device and so cannot refuse it) the problem ran as LastKeyFrame because its mode was
+ *   neither value or because it was LastFrame and prior_in_dev was NULL.
+ * The _dev form is asynchronous on the ctx stream: no host synchronisation, no host read of device data, no workspace.  The host
+ *   form stages its arrays (outlier and chi2 go in and out) and returns stats[0] of problem 0 (0 when B = 0).
+ * Refused (RFE_ERR_INVALID), nothing written: B outside 0..64; N outside 0..4096; nlevels outside 1..RFE_MAX_LEVELS; a NULL required
+ *   pointer (params, mode, cam, state, prev_state, preint, cov_rw, state_out, outlier, stats; kpts_un, xw, has_mp, track_depth when
+ *   B N > 0); host form only: a mode that is neither value, LastFrame without prior_in, a dT that is not positive.
+ * Out of scope: two-camera rigs (mpCamera2), KannalaBrandt8. */
+enum { RFE_PIO_LAST_KEYFRAME = 0, RFE_PIO_LAST_FRAME = 1 };
+#define RFE_PIO_CAM_FLOATS 36
+#define RFE_PIO_STATE_FLOATS 21
+#define RFE_PIO_PREINT_FLOATS 148
+#define RFE_PIO_COV_RW_FLOATS 18
+#define RFE_PIO_PRIOR_DOUBLES 246
+typedef struct rfe_pose_inertial_params {
+    float fx, fy, cx, cy, bf;
+    int32_t nlevels;                          /* 1..RFE_MAX_LEVELS */
+    float inv_level_sigma2[RFE_MAX_LEVELS];   /* mvInvLevelSigma2 */
+} rfe_pose_inertial_params;
+int rfe_pose_inertial_optimization_dev(rfe_ctx* ctx, const rfe_pose_inertial_params* params, const int32_t* mode_dev, const int32_t* rec_init_dev,
+                                       const float* cam_dev, const float* state_dev, const float* prev_state_dev, const float* preint_dev,
+                                       const float* cov_rw_dev, const double* prior_in_dev, const float* kpts_un_dev, const int32_t* octave_dev,
+                                       const float* uright_dev, const float* xw_dev, const uint8_t* has_mp_dev, const float* track_depth_dev,
+                                       const int32_t* n_dev, int B, int N, double* state_out_dev, float* state_f32_dev, uint8_t* outlier_dev,
+                                       float* chi2_dev, double* prior_out_dev, double* trace_dev, int32_t* stats_dev);
+int rfe_pose_inertial_optimization(rfe_ctx* ctx, const rfe_pose_inertial_params* params, const int32_t* mode, const int32_t* rec_init,
+                                   const float* cam, const float* state, const float* prev_state, const float* preint, const float* cov_rw,
+                                   const double* prior_in, const float* kpts_un, const int32_t* octave, const float* uright, const float* xw,
+                                   const uint8_t* has_mp, const float* track_depth, const int32_t* n, int B, int N, double* state_out,
+                                   float* state_f32, uint8_t* outlier, float* chi2, double* prior_out, double* trace, int32_t* stats);
 
 /* ---- Sim3Solver on the device: every RANSAC hypothesis of a loop-closing candidate in one call ----
  * src/Sim3Solver.cc:61-483 as LoopClosing::DetectCommonRegionsFromBoW drives it (SetRansacParameters, then iterate(20, ..) until bConverge
@@ -1193,6 +1256,14 @@ int rfe_k_lightglue_assign(rfe_ctx* ctx, const float* sim_dev, const float* x_de
 int rfe_k_two_view_check(rfe_ctx* ctx, int model, const float* M, float sigma, const float* pts, int n, float* contrib, uint8_t* inl);
 int rfe_k_two_view_check_rt(rfe_ctx* ctx, const float* Rt, const float* K4, float th2, const float* pts, int n, uint8_t* code, float* cosp,
                             float* p3d);
+/* The float chi2 classification of rfe_pose_inertial_optimization behind round `round` (0..3) or its recovery pass (round 4),
+ * through the device functions the kernel uses, of n edges at ONE camera pose view [12] = Rcw row-major | tcw (doubles).  HOST pointers,
+ * synchronous, 1 <= n <= 4096; every row is an edge.  outlier_in [n]: the flags before (a flagged edge recomputes its error at the view, any
+ * other is compared at chi2_in [n]).  code [n]: rounds 0..3 the new flag; round 4 bit 0 the flag afterwards, bit 1 the edge counts in nBad.
+ * chi2_out [n]: the float that was compared. */
+int rfe_k_pose_inertial_classify(rfe_ctx* ctx, const rfe_pose_inertial_params* params, int mode, int round, const double* view, const float* kpts_un,
+                                 const int32_t* octave, const float* uright, const float* xw, const float* track_depth, const uint8_t* outlier_in,
+                                 const float* chi2_in, int n, uint8_t* code, float* chi2_out);
 /* One-shot tap for the NEXT LightGlue forward of this ctx, whichever entry point runs it (rfe_match[_dev] with P pairs,
  * rfe_extract_match_stream_dev, rfe_stereo_frame_dev) and therefore whichever tiling it selects: after the last layer the final
  * token states of pair `pair` are copied to x0_dev / x1_dev ([L,256] each, L = max(Mmax,Nmax) rounded up to 4; rows past the

@@ -26,8 +26,8 @@ EXPORTS = [
     "rfe_l2_distance_matrix_dev", "rfe_binarize_descriptors_dev", "rfe_search_candidates_dev", "rfe_distinctive_descriptors_dev",
     "rfe_search_by_projection", "rfe_search_by_projection_dev", "rfe_search_by_projection_sim3", "rfe_search_by_projection_sim3_dev",
     "rfe_search_local_points", "rfe_search_local_points_dev", "rfe_triangulate_neighbours", "rfe_triangulate_neighbours_dev",
-    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev", "rfe_global_ba", "rfe_global_ba_dev",
-    "rfe_two_view", "rfe_two_view_dev", "rfe_k_two_view_check", "rfe_k_two_view_check_rt",
+    "rfe_pose_optimization", "rfe_pose_optimization_dev", "rfe_pose_inertial_optimization", "rfe_pose_inertial_optimization_dev", "rfe_sim3_ransac", "rfe_sim3_ransac_dev", "rfe_sim3_ransac_iterations", "rfe_optimize_sim3", "rfe_optimize_sim3_dev", "rfe_local_ba", "rfe_local_ba_dev", "rfe_essential_graph", "rfe_essential_graph_dev", "rfe_global_ba", "rfe_global_ba_dev",
+    "rfe_two_view", "rfe_two_view_dev", "rfe_k_two_view_check", "rfe_k_two_view_check_rt", "rfe_k_pose_inertial_classify",
     "rfe_bow_vocab_create", "rfe_bow_vocab_load", "rfe_bow_vocab_destroy", "rfe_bow_vocab_info", "rfe_bow_transform", "rfe_bow_transform_dev",
     "rfe_bow_db_create", "rfe_bow_db_destroy", "rfe_bow_db_add", "rfe_bow_db_add_dev", "rfe_bow_db_erase", "rfe_bow_db_clear", "rfe_bow_db_size",
     "rfe_bow_db_query", "rfe_bow_db_query_dev",
@@ -247,6 +247,33 @@ POSE_OUTPUTS = ("pose_f32", "chi2", "trace")
 _pose = [C.c_void_p, C.POINTER(PoseParams), _fp, _fp, _ip, _fp, _fp, _u8p, _ip, C.c_int, C.c_int, _vp, _fp, _u8p, _fp, _vp, _ip]
 lib.rfe_pose_optimization.argtypes = _pose
 lib.rfe_pose_optimization_dev.argtypes = _pose
+
+
+class PoseInertialParams(C.Structure):
+    """include/rover_fe.h: rfe_pose_inertial_params -- intrinsics, mbf and mvInvLevelSigma2 of one PoseInertialOptimization call."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("nlevels", C.c_int32),
+                ("inv_level_sigma2", C.c_float * MAX_LEVELS)]
+
+
+def pose_inertial_params(fx, fy, cx, cy, bf, inv_level_sigma2=(1.0,), nlevels=None):
+    """rfe_pose_inertial_params from plain values"""
+    p = PoseInertialParams()
+    p.fx, p.fy, p.cx, p.cy, p.bf = (float(v) for v in (fx, fy, cx, cy, bf))
+    p.nlevels = len(inv_level_sigma2) if nlevels is None else int(nlevels)
+    for l, v in enumerate(list(inv_level_sigma2)[:MAX_LEVELS]):
+        p.inv_level_sigma2[l] = float(v)
+    return p
+
+
+PIO_LAST_KEYFRAME, PIO_LAST_FRAME = 0, 1
+PIO_CAM_FLOATS, PIO_STATE_FLOATS, PIO_PREINT_FLOATS, PIO_COV_RW_FLOATS, PIO_PRIOR_DOUBLES = 36, 21, 148, 18, 246
+PIO_OUTPUTS = ("state_f32", "chi2", "prior_out", "trace")
+_pio = [C.c_void_p, C.POINTER(PoseInertialParams), _ip, _ip, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _ip, _fp, _fp, _u8p, _fp, _ip, C.c_int, C.c_int,
+        _vp, _fp, _u8p, _fp, _vp, _vp, _ip]
+lib.rfe_pose_inertial_optimization.argtypes = _pio
+lib.rfe_pose_inertial_optimization_dev.argtypes = _pio
+lib.rfe_k_pose_inertial_classify.argtypes = [C.c_void_p, C.POINTER(PoseInertialParams), C.c_int, C.c_int, _vp, _fp, _ip, _fp, _fp, _fp, _u8p, _fp,
+                                             C.c_int, _u8p, _fp]
 
 
 class Sim3SolverParams(C.Structure):
@@ -1250,6 +1277,70 @@ class Context:
         a = _dev
         self._chk(lib.rfe_pose_optimization_dev(self.h, C.byref(params), a(pose0), a(kpts_un), a(octave), a(uright), a(xw), a(has_mp), a(n),
                                                 int(B), int(N), a(pose), a(pose_f32), a(outlier), a(chi2), a(trace), a(stats)))
+
+    def pose_inertial_optimization(self, params, mode, cam, state, prev_state, preint, cov_rw, kpts_un, xw, has_mp, track_depth, prior_in=None,
+                                   rec_init=None, octave=None, uright=None, n=None, outlier=None, chi2=None, outputs=PIO_OUTPUTS):
+        """Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame for B problems (rfe_pose_inertial_optimization, host arrays; DESIGN.md
+        6p).  params: a PoseInertialParams (pose_inertial_params()); mode [B] PIO_LAST_KEYFRAME / PIO_LAST_FRAME; cam [B,36], state /
+        prev_state [B,21], preint [B,148], cov_rw [B,18] float32; prior_in [B,246] float64 or None; kpts_un [B,N,2], xw [B,N,3], has_mp /
+        track_depth / octave / uright [B,N]; rec_init / n [B] or None.  outlier / chi2: what those arrays hold where the call does not write
+        (default 0).  outputs: the optional arrays to ask for (the others are passed as NULL).  Returns a dict: state [B,21] float64,
+        outlier [B,N], stats [B,16], ret, and state_f32 / chi2 / prior_out [B,246] / trace [B,4,8] as asked."""
+        md = np.ascontiguousarray(mode, np.int32).reshape(-1)
+        B = md.size
+        k = np.ascontiguousarray(kpts_un, np.float32)
+        N = k.size // (2 * B) if B else 0
+        f = B * N
+        cm, st, ps, pr, cv = (_opt(v, np.float32) for v in (cam, state, prev_state, preint, cov_rw))
+        assert len(cm) == B * PIO_CAM_FLOATS and len(st) == len(ps) == B * PIO_STATE_FLOATS and len(pr) == B * PIO_PREINT_FLOATS
+        assert len(cv) == B * PIO_COV_RW_FLOATS
+        pin, rc = _opt(prior_in, np.float64), _opt(rec_init, np.int32)
+        x, m, td = _opt(xw, np.float32), _opt(has_mp, np.uint8), _opt(track_depth, np.float32)
+        o, u, nn = _opt(octave, np.int32), _opt(uright, np.float32), _opt(n, np.int32)
+        assert len(x) == f * 3 and len(m) == f and len(td) == f and (o is None or len(o) == f) and (u is None or len(u) == f)
+        assert (nn is None or len(nn) == B) and (rc is None or len(rc) == B) and (pin is None or len(pin) == B * PIO_PRIOR_DOUBLES)
+        b1, f1 = max(B, 1), max(f, 1)
+        out = np.zeros((f1,), np.uint8)
+        c2 = np.zeros((f1,), np.float32)
+        if outlier is not None:
+            out[:f] = np.asarray(outlier, np.uint8).reshape(-1)
+        if chi2 is not None:
+            c2[:f] = np.asarray(chi2, np.float32).reshape(-1)
+        so, sf = np.zeros((b1, PIO_STATE_FLOATS), np.float64), np.zeros((b1, PIO_STATE_FLOATS), np.float32)
+        po, tr, sts = np.zeros((b1, PIO_PRIOR_DOUBLES), np.float64), np.zeros((b1, 4, 8), np.float64), np.zeros((b1, 16), np.int32)
+        opt = {"state_f32": sf, "chi2": c2, "prior_out": po, "trace": tr}
+        want = {key: (a.ctypes.data if key in outputs else None) for key, a in opt.items()}
+        ret = self._chk(lib.rfe_pose_inertial_optimization(self.h, C.byref(params), _addr(md), _addr(rc), _addr(cm), _addr(st), _addr(ps), _addr(pr),
+                                                           _addr(cv), _addr(pin), _addr(k), _addr(o), _addr(u), _addr(x), _addr(m), _addr(td),
+                                                           _addr(nn), B, N, so.ctypes.data, want["state_f32"], out.ctypes.data, want["chi2"],
+                                                           want["prior_out"], want["trace"], sts.ctypes.data))
+        r = {"state": so[:B], "outlier": out[:f].reshape(B, N), "stats": sts[:B], "ret": ret}
+        r.update({key: (a[:f].reshape(B, N) if key == "chi2" else a[:B]) for key, a in opt.items() if key in outputs})
+        return r
+
+    def pose_inertial_optimization_dev(self, params, mode, cam, state, prev_state, preint, cov_rw, kpts_un, xw, has_mp, track_depth, B, N,
+                                       state_out, outlier, stats, prior_in=None, rec_init=None, octave=None, uright=None, n=None,
+                                       state_f32=None, chi2=None, prior_out=None, trace=None):
+        """rfe_pose_inertial_optimization_dev: params is a host structure, every array a DevBuf (or a raw device address / torch tensor);
+        asynchronous on the ctx stream."""
+        a = _dev
+        self._chk(lib.rfe_pose_inertial_optimization_dev(self.h, C.byref(params), a(mode), a(rec_init), a(cam), a(state), a(prev_state),
+                                                         a(preint), a(cov_rw), a(prior_in), a(kpts_un), a(octave), a(uright), a(xw), a(has_mp),
+                                                         a(track_depth), a(n), int(B), int(N), a(state_out), a(state_f32), a(outlier), a(chi2),
+                                                         a(prior_out), a(trace), a(stats)))
+
+    def k_pose_inertial_classify(self, params, mode, rnd, view, kpts_un, xw, track_depth, outlier_in, chi2_in, octave=None, uright=None):
+        """rfe_k_pose_inertial_classify: the float classification behind round rnd (0..3) or the recovery pass (4) of n edges at the camera
+        pose view [12] -> code [n], chi2 [n]"""
+        v = np.ascontiguousarray(view, np.float64).reshape(12)
+        k, x, td = (_opt(a, np.float32) for a in (kpts_un, xw, track_depth))
+        oi, ci = _opt(outlier_in, np.uint8), _opt(chi2_in, np.float32)
+        o, u = _opt(octave, np.int32), _opt(uright, np.float32)
+        n = len(td)
+        code, c2 = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+        self._chk(lib.rfe_k_pose_inertial_classify(self.h, C.byref(params), int(mode), int(rnd), v.ctypes.data, _addr(k), _addr(o), _addr(u), _addr(x),
+                                                   _addr(td), _addr(oi), _addr(ci), n, code.ctypes.data, c2.ctypes.data))
+        return code, c2
 
     def sim3_ransac(self, problems, xw1, xw2, sigma2_1, sigma2_2, draws, fill=None, outputs=SIM3_RANSAC_OUTPUTS):
         """Sim3Solver's RANSAC for B problems (rfe_sim3_ransac, host arrays).  problems: B dicts (sim3_solver_params()) or the

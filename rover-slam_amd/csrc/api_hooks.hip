@@ -323,3 +323,29 @@ extern "C" int rfe_k_lightglue_taps(rfe_ctx* c, const float* k0n, const float* k
     RFE_HIP(c, hipStreamSynchronize(c->stream));
     return RFE_OK;
 }
+
+// The float classification of rfe_pose_inertial_optimization behind round `round` (0..3) or its recovery pass (round 4) of n edges at ONE
+// camera pose view [12] = Rcw row-major | tcw (doubles), through the device functions the kernel uses.  Every row is an edge;
+// outlier_in [n] the flags before (a flagged edge recomputes its error, any other is compared at chi2_in [n]).  code [n]: rounds 0..3 the new
+// flag; round 4 bit 0 the flag afterwards, bit 1 the edge counts in nBad.  chi2_out [n] the float compared.  HOST pointers, synchronous.
+extern "C" int rfe_k_pose_inertial_classify(rfe_ctx* c, const rfe_pose_inertial_params* P, int mode, int round, const double* view, const float* kpts,
+                                            const int32_t* octave, const float* uright, const float* xw, const float* track_depth,
+                                            const uint8_t* outlier_in, const float* chi2_in, int n, uint8_t* code, float* chi2_out) {
+    if (!c) return RFE_ERR_INVALID;
+    if (!P || !view || !kpts || !xw || !track_depth || !outlier_in || !chi2_in || !code || !chi2_out || n < 1 || n > 4096 || round < 0 || round > 4 ||
+        (mode != RFE_PIO_LAST_KEYFRAME && mode != RFE_PIO_LAST_FRAME) || P->nlevels < 1 || P->nlevels > RFE_MAX_LEVELS)
+        return fail(c, RFE_ERR_INVALID, "k_pose_inertial_classify: bad argument");
+    RFE_HIP(c, hipSetDevice(c->device));
+    double* dv; float *dk, *du, *dx, *dt, *dci, *dco; int32_t* doct; uint8_t *doi, *dcode;
+    HostIo io(c, HostIo::DIRECT);
+    io.in(dv, view, (size_t)12); io.in(dk, kpts, (size_t)n * 2); io.in_opt(doct, octave, (size_t)n); io.in_opt(du, uright, (size_t)n);
+    io.in(dx, xw, (size_t)n * 3); io.in(dt, track_depth, (size_t)n); io.in(doi, outlier_in, (size_t)n); io.in(dci, chi2_in, (size_t)n);
+    io.out(dcode, code, (size_t)n); io.out(dco, chi2_out, (size_t)n);
+    int rc = io.upload();
+    if (rc) return rc;
+    PioArgs a = PioArgs();
+    a.kpts = dk; a.octave = doct; a.uright = du; a.xw = dx; a.track_depth = dt; a.chi2 = dco; a.N = n;
+    launch_pose_inertial_classify(c->stream, *P, a, dv, mode == RFE_PIO_LAST_FRAME ? 1 : 0, round, doi, dci, dcode);
+    RFE_HIP(c, hipGetLastError());
+    return io.download();
+}

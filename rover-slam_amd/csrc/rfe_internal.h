@@ -441,6 +441,25 @@ void launch_pose_opt(hipStream_t s, const rfe_pose_params& P, const float* pose0
                      const float* xw, const uint8_t* has_mp, const int32_t* n, int B, int N, double* pose, float* pose_f32, uint8_t* outlier,
                      float* chi2, double* trace, int32_t* stats);
 
+// pose_inertial.hip: Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame, one workgroup per problem.  The optional
+// pointers of PioArgs may be NULL; needs no workspace and presets nothing
+struct PioArgs {
+    const int32_t *mode, *rec_init, *octave, *n;
+    const float *cam, *state, *prev_state, *preint, *cov_rw, *kpts, *uright, *xw, *track_depth;
+    const double* prior_in;
+    const uint8_t* has_mp;
+    double *state_out, *prior_out, *trace;
+    float *state_f32, *chi2;
+    uint8_t* outlier;
+    int32_t* stats;
+    int N;
+};
+void launch_pose_inertial(hipStream_t s, const rfe_pose_inertial_params& P, const PioArgs& a, int B);
+// test hook: the float classification behind round rnd (0..3) or the recovery pass (rnd 4) of a.N edges at the camera pose view [12]; reads
+// a.kpts / octave / uright / xw / track_depth, writes a.chi2 and code
+void launch_pose_inertial_classify(hipStream_t s, const rfe_pose_inertial_params& P, const PioArgs& a, const double* view, int lf, int rnd,
+                                   const uint8_t* outlier_in, const float* chi2_in, uint8_t* code);
+
 // optimize_sim3.hip: Optimizer::OptimizeSim3, one workgroup per problem.  params is a HOST array: the kernel takes it by
 // value, OS_CHUNK problems per launch.  octave1 / octave2 / s12_f32 / chi2 / trace may be NULL (kpts2 too when N2 = 0); needs no workspace
 // and presets nothing
